@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — GB/s of input scanned per GPU on gen-data.pl-style streams.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json):
   N == 1  configs[1]: ONE 4 GiB stream  "abccc" x k . "aaabbccb"  (bench/gen-data.pl:9
@@ -18,6 +18,13 @@ roofline.frac is the WHOLE step against the HBM peak (all kernels, copies and ga
 of a step: bytes / wall time per step); roofline.kernel_frac is the dominant scan
 kernel alone (hipEvents around its launch).
 Rank 0 prints ONE JSON line.
+
+A plain run measures the headline workload alone.  --full adds what takes runs of
+its own: the measured read / staging ceilings (roofline.measured_*), the other
+configurations and sizes (config.variants) and the CPU baselines (cpu_baseline);
+--no-variants / --no-cpu-baseline leave parts of it out.  --dump-outputs DIR writes
+the per-stream result records of the last timed step to DIR/records.npy (float64,
+one row per stream: the slots sre_hip_scan_results returns).
 """
 import argparse
 import ctypes
@@ -445,6 +452,17 @@ def roofline(m):
             "algorithmic_bytes_per_launch": m["total"]}
 
 
+def dump_outputs(path, recs, rank, world):
+    """the records the caller of the timed path receives from its last step, one row per stream
+    of this rank (int64 slots, exact in float64)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arr = np.asarray(recs, dtype=np.int64)
+    assert arr.ndim == 2 and arr.nbytes <= (64 << 20), arr.shape
+    name = "records.npy" if world == 1 else "records_rank%d.npy" % rank
+    np.save(os.path.join(path, name), arr.astype(np.float64))
+
+
 def git_commit():
     try:
         return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True,
@@ -460,9 +478,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bytes", type=int, default=0,
                     help="bytes per GPU (default: 4 GiB single stream at N=1, 8 GiB = 128 x 64 MiB streams at N>1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: read / staging ceilings, the other "
+                         "configurations (config.variants), the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result records of the last timed step to DIR/records.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-variants", action="store_true",
-                    help="N=1: do not measure the other configurations beside the headline (config.variants)")
+                    help="with --full, N=1: do not measure the other configurations beside the headline (config.variants)")
     ap.add_argument("--config", default="cfg2", choices=["cfg1", "cfg2", "cfg2m", "cfg3", "cfg4", "nfa", "nfala", "nfa37", "nfa60", "nfa57w", "count_nfa", "dense", "densef", "densela", "floor", "floorla", "words"],
                     help="N=1 headline workload: cfg2 = BASELINE configs[1] (default); cfg2m = same with a "
                          "matching tail (captures span the whole stream); cfg3 = configs[2] multi-regex "
@@ -506,6 +529,8 @@ def main():
     res = Resident(torch, lib, hstream)
     head = workload_spec("many" if many else args.config, S, args.bytes, rank, world)
     m = measure(head, S, torch, res, hstream, stream, args.steps, args.warmup, barrier)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["recs"], rank, world)
 
     dt = shard.allreduce_max(m["dt"], "cuda")                        # slowest rank
     matches, total_all = shard.allreduce_counts([m["matches"], m["total"]], "cuda")   # the path's only exchange step
@@ -547,7 +572,7 @@ def main():
                 line["roofline"]["traffic"] = (2 * pm[("FETCH_SIZE", True)] + pm[("WRITE_SIZE", True)]) * 1024
                 line["roofline"]["traffic_source"] = "profiles/r03_pmc_hbm.json (commit %s, %s)" % (
                     pj.get("commit"), pj.get("date"))
-        if world == 1 and not many:
+        if args.full and world == 1 and not many:
             # measured streaming-read ceiling of this box, same buffer
             ptr0, len0 = res.bufs[0].data_ptr(), head["lens"][0]
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -570,7 +595,7 @@ def main():
                 torch.cuda.synchronize()
                 line["roofline"]["measured_staging_ceiling"] = \
                     (len0 // seg * seg) * 5 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-        if world == 1 and not args.no_variants and head["name"] == "cfg2" and not args.many_streams:
+        if args.full and world == 1 and not args.no_variants and head["name"] == "cfg2" and not args.many_streams:
             # the other configurations of BASELINE.json on this GPU, same harness: whole-step
             # time and whole-step fraction of the HBM peak (every kernel of the step), the
             # dominant kernel alone beside it
@@ -595,7 +620,7 @@ def main():
                 except Exception as e:          # noqa: BLE001 - a variant must not take the headline down
                     variants[name] = {"error": repr(e)}
             line["config"]["variants"] = variants
-        if world == 1 and not many and not args.no_cpu_baseline:
+        if args.full and world == 1 and not many and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()
         print(json.dumps(line))
     if world > 1:

@@ -13,6 +13,9 @@ The GPU box gets the committed outputs only:
   tests/golden/gen_data.jsonl      bench/gen-data.pl-style streams x config patterns:
                                    reference Thompson status + Pike rc/ovector
   tests/golden/findall.jsonl       iterated-exec (find-all) traces from the reference
+  tests/golden/reference_fuzz.jsonl.gz   (--fuzz-only) the reference's replies to the inputs of the
+                                   randomised tests (test_frontend_fuzz.py, test_oracle.py's
+                                   differential): {k: harness.reply_key(...), v: reply}
 
 How the reference is driven mirrors t/SRegex.pm:73-84:
    ./sregex-cli --stdin [--flags F] [-n N] RE...   with stdin "<len>\\n<bytes>"
@@ -317,7 +320,39 @@ def newline_goldens(path):
             L.sre_destroy_pool(pool)
 
 
+# ---------------------------------------------------------------- replies to the randomised tests
+
+def live_differential_replies(ref, pats, subjects):
+    """the real reference library's find-all trace and Thompson verdict for every subject"""
+    rpool, rprog, ncaps = ref.compile(pats)
+    out = {"ncaps": ncaps, "runs": [[ref.pike_findall(rprog, ncaps, data), ref.thompson(rprog, data)]
+                                    for data in subjects]}
+    ref.L.sre_destroy_pool(rpool)
+    return out
+
+
+def fuzz_goldens(path):
+    sys.path[:0] = [ROOT, os.path.dirname(HERE)]
+    import harness
+    seed = harness.FUZZ_SEED
+    out = {}
+    for pat, caseless in harness.frontend_fuzz_cases(seed):
+        out[harness.reply_key("parse", [pat], caseless)] = harness.cli_parse_reply(pat, caseless)
+    for pats, subject in harness.oracle_fuzz_cases(seed):
+        out[harness.reply_key("exec", pats, subject)] = harness.cli_exec_reply(pats, subject)
+    ref = RefLib()
+    for pats, subjects in harness.live_differential_cases():
+        out[harness.reply_key("live", pats, *subjects)] = live_differential_replies(ref, pats, subjects)
+    with gzip.GzipFile(path, "wb", mtime=0) as f:
+        for k, v in out.items():
+            f.write((json.dumps({"k": k, "v": v}, sort_keys=True) + "\n").encode())
+    print("replies", len(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--fuzz-only":
+        fuzz_goldens(os.path.join(HERE, "reference_fuzz.jsonl.gz"))
+        return
     if len(sys.argv) > 1 and sys.argv[1] == "--newline-only":
         newline_goldens(os.path.join(HERE, "newline_flag.jsonl"))
         return

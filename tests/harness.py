@@ -272,12 +272,14 @@ def findall(engine, prog, ncaps, data, limit=1 << 30):
 
 # ------------------------------------------------------------------ random patterns
 
-def random_regex(rng, depth=0):
+def random_regex(rng, depth=0, wide=None):
     """A random pattern over a small alphabet, from the constructs the reference
     parser accepts: literals, classes, '.', groups, alternation, greedy and lazy
     quantifiers, counted repeats, and every assertion."""
     atoms = [b"a", b"b", b"c", b"x", b".", b"[ab]", b"[^a]", b"\\w", b"\\s", b"\\n", b"[a-c]"]
-    if os.environ.get("SRE_FUZZ_WIDE"):
+    if wide is None:
+        wide = bool(os.environ.get("SRE_FUZZ_WIDE"))
+    if wide:
         # more of the lexer: escapes, negated shorthands, upper case (for caseless flags), high bytes
         atoms += [b"A", b"X", b"\\.", b"\\W", b"\\S", b"\\d", b"\\D", b"[^\\s]", b"[\\w.]", b"\\x41",
                   b"\\xff", b"[\\x80-\\xff]", b"_", b"[A-C]"]
@@ -289,9 +291,9 @@ def random_regex(rng, depth=0):
         if r < 0.12:
             piece = rng.choice(asserts)
         elif r < 0.30 and depth < 2:
-            inner = random_regex(rng, depth + 1)
+            inner = random_regex(rng, depth + 1, wide)
             if rng.random() < 0.5:
-                inner += b"|" + random_regex(rng, depth + 1)
+                inner += b"|" + random_regex(rng, depth + 1, wide)
             piece = (b"(" if rng.random() < 0.7 else b"(?:") + inner + b")"
         else:
             piece = rng.choice(atoms)
@@ -299,3 +301,138 @@ def random_regex(rng, depth=0):
             piece += rng.choice([b"*", b"+", b"?", b"*?", b"+?", b"??", b"{2}", b"{1,3}", b"{0,2}?"])
         seq.append(piece)
     return b"".join(seq)
+
+
+# ------------------------------------------------------------------ recorded replies of the reference
+
+# The randomised differential tests (test_frontend_fuzz.py, test_oracle.py's live differential) put
+# their inputs to the real reference.  Its replies to the inputs of the fixed seeds are recorded in
+# tests/golden/reference_fuzz.jsonl.gz (tests/golden/make_goldens.py --fuzz-only, from oracle/_ref),
+# so that these tests run without the reference; an input without a recorded reply (another
+# SRE_FUZZ_SEED) is put to the live reference in oracle/_ref, when that is built.
+REF_DIR = os.path.join(ORACLE_DIR, "_ref")
+REF_CLI = os.path.join(REF_DIR, "sregex-cli")
+REF_SO = os.path.join(REF_DIR, "libsregex_ref.so")
+REPLIES = "reference_fuzz.jsonl.gz"
+FUZZ_SEED = 99                  # test_frontend_fuzz.py's sequence unless SRE_FUZZ_SEED says otherwise
+LIVE_DIFF_SEED = 20261004       # test_oracle.py's live differential
+
+
+def reply_key(kind, pats, *rest):
+    return json.dumps([kind, [p.hex() for p in pats]] + [r.hex() if isinstance(r, bytes) else r for r in rest])
+
+
+_replies = None
+
+
+def recorded_replies():
+    global _replies
+    if _replies is None:
+        with gzip.open(os.path.join(GOLDEN, REPLIES), "rt") as f:
+            _replies = {r["k"]: r["v"] for r in map(json.loads, f)}
+    return _replies
+
+
+def reference_reply(key, live, needs):
+    """the recorded reply to `key`, else live() when the reference binary `needs` is built"""
+    rec = recorded_replies()
+    if key in rec:
+        return rec[key]
+    if not os.path.exists(needs):
+        import pytest
+        pytest.skip("no recorded reply of the reference to this input (another SRE_FUZZ_SEED?) "
+                    "and %s is not built" % os.path.relpath(needs, ROOT))
+    return live()
+
+
+def cli_parse_reply(pat, caseless=False):
+    """AST dump / capture count / program dump of one pattern, or its syntax error, as the reference
+    CLI prints them; None where the reference crashed or the argument is not taken as a pattern"""
+    try:
+        p = subprocess.run([REF_CLI] + (["--flags", "i"] if caseless else []) + [pat, b""], capture_output=True,
+                           timeout=20)
+    except subprocess.TimeoutExpired:
+        return None
+    if p.returncode < 0:
+        return None                      # the reference crashed on this one
+    err = p.stderr.decode("latin-1").strip()
+    if "[error]" in err:
+        return {"err": err.splitlines()[0]}
+    if p.returncode != 0 and not p.stdout:
+        return None                      # an option-like argument, not a pattern
+    out = p.stdout.decode("latin-1").split("\n## ")[0].split("\n")
+    return {"ast": out[0], "ncaps": int(out[1].split(":")[1]), "prog": "\n".join(out[2:]).rstrip("\n")}
+
+
+def cli_exec_reply(pats, subject):
+    """the reference CLI's thompson / splitted thompson / pike / splitted pike lines for the subject
+    (its JIT lines left out); None where the reference crashed or timed out"""
+    argv = [REF_CLI] + (["-n", str(len(pats))] if len(pats) > 1 else []) + pats + [subject]
+    try:
+        p = subprocess.run(argv, capture_output=True, timeout=20)
+    except subprocess.TimeoutExpired:
+        return None
+    if p.returncode != 0:
+        return None                      # the reference crashes on some programs (DESIGN.md §5)
+    # the six engine lines close the output (the subject itself may hold newlines)
+    lines = [l for l in p.stdout.decode("latin-1").split("\n") if l][-6:]
+    return [l for l in lines if "jitted" not in l]
+
+
+def frontend_fuzz_cases(seed):
+    """test_frontend_fuzz.py: random and randomly damaged patterns (SRE_FUZZ_WIDE atoms), and
+    whether the caseless flag is given"""
+    import random
+    rng = random.Random(seed)
+    junk = b"()[]{}*+?|\\^$.,-0123456789abx:=!<>"
+    for _ in range(1200):
+        pat = random_regex(rng, wide=True)
+        if rng.random() < 0.4:           # damage it: insert / delete / replace a byte
+            b = bytearray(pat)
+            for _ in range(rng.randrange(1, 3)):
+                k = rng.randrange(0, len(b) + 1)
+                op = rng.randrange(3)
+                if op == 0 or not b:
+                    b.insert(k, rng.choice(junk))
+                elif op == 1:
+                    del b[min(k, len(b) - 1)]
+                else:
+                    b[min(k, len(b) - 1)] = rng.choice(junk)
+            pat = bytes(b)
+        if not pat or b"\0" in pat or pat.startswith(b"-"):
+            continue
+        caseless = rng.random() < 0.3       # applied at parse time (sre_yyparser.y:244-279, sre_regex.c:170-214)
+        yield pat, caseless
+
+
+def oracle_fuzz_cases(seed):
+    """test_frontend_fuzz.py: random patterns (one, or two or three of them) and subjects"""
+    import random
+    rng = random.Random(seed + 1000)
+    alphabet = b"abcx \n_."
+    for _ in range(500):
+        pats = [random_regex(rng) for _ in range(1 if rng.random() < 0.75 else rng.randrange(2, 4))]
+        if any(p.startswith(b"-") for p in pats):
+            continue
+        subject = bytes(rng.choice(alphabet) for _ in range(rng.choice([0, 1, 3, 9, 20, 33])))
+        if subject.startswith(b"-"):
+            continue
+        yield pats, subject
+
+
+LIVE_DIFF_ZOO = [
+    [rb"(a*)*b"], [rb"(a*)+"], [rb"(a|b)*?c"], [rb"\bfoo\b"], [rb"^a|b$"], [rb"a$|ab"],
+    [rb"(?:a$|a)b?"], [rb"\Ba\B|c\b"], [rb"(a+)(b+)?"], [rb"x*"], [rb"(|a)+"], [rb"a{2,3}b{0,2}"],
+    [rb"\Aab|\n^b"], [rb"[^a]\z|a"], [rb"a", rb"ab", rb"\s+", rb"b$"], [rb"(a)|b", rb"(b)(c)?"],
+    [rb"$"], [rb"^"], [rb"\b"], [rb"(a?)*?b"], [rb"((a)|b)+"], [rb"a.c"], [rb"[a-c]+\.[^b]"],
+]
+
+
+def live_differential_cases():
+    """test_oracle.py: a pattern zoo that leans on assertions, empty matches, nested stars and
+    multi-regex, each with 60 random subjects over a small alphabet"""
+    import random
+    rng = random.Random(LIVE_DIFF_SEED)
+    alphabet = b"ab c\n.x"
+    for pats in LIVE_DIFF_ZOO:
+        yield pats, [bytes(rng.choice(alphabet) for _ in range(rng.randrange(0, 24))) for _ in range(60)]

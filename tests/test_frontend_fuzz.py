@@ -1,18 +1,13 @@
-"""Front end (parser + compiler) against the LIVE reference CLI on random and
-randomly damaged patterns (build container only: needs oracle/_ref/sregex-cli,
+"""Front end (parser + compiler) against the reference CLI on random and
+randomly damaged patterns: its replies to the fixed seed's inputs are recorded
+in tests/golden/reference_fuzz.jsonl.gz (tests/golden/make_goldens.py
+--fuzz-only), another SRE_FUZZ_SEED asks the live CLI (oracle/_ref/sregex-cli,
 the real reference compiled by oracle/Makefile).  Compared: AST dump, capture
 count, program dump — or the syntax-error offset."""
 import os
-import random
-import subprocess
-
-import pytest
 
 import sregex_amd as S
 import harness
-
-CLI = os.path.join(harness.ROOT, "oracle", "_ref", "sregex-cli")
-pytestmark = pytest.mark.skipif(not os.path.exists(CLI), reason="oracle/_ref/sregex-cli not built")
 
 
 def _ours(pat, caseless=False):
@@ -26,46 +21,15 @@ def _ours(pat, caseless=False):
 
 
 def _theirs(pat, caseless=False):
-    p = subprocess.run([CLI] + (["--flags", "i"] if caseless else []) + [pat, b""], capture_output=True, timeout=20)
-    if p.returncode < 0:
-        return None                      # the reference crashed on this one
-    err = p.stderr.decode("latin-1").strip()
-    if "[error]" in err:
-        return {"err": err.splitlines()[0]}
-    if p.returncode != 0 and not p.stdout:
-        return None                      # an option-like argument, not a pattern
-    out = p.stdout.decode("latin-1").split("\n## ")[0].split("\n")
-    return {"ast": out[0], "ncaps": int(out[1].split(":")[1]), "prog": "\n".join(out[2:]).rstrip("\n")}
+    return harness.reference_reply(harness.reply_key("parse", [pat], caseless),
+                                   lambda: harness.cli_parse_reply(pat, caseless), harness.REF_CLI)
 
 
-def test_random_and_damaged_patterns_parse_like_the_reference(monkeypatch):
-    monkeypatch.setenv("SRE_FUZZ_WIDE", "1")
-    rng = random.Random(int(os.environ.get("SRE_FUZZ_SEED", "99")))
-    junk = b"()[]{}*+?|\\^$.,-0123456789abx:=!<>"
+def test_random_and_damaged_patterns_parse_like_the_reference():
     bad = []
     n = crashed = rejected = 0
-    for _ in range(1200):
-        pat = harness.random_regex(rng)
-        if rng.random() < 0.4:           # damage it: insert / delete / replace a byte
-            b = bytearray(pat)
-            for _ in range(rng.randrange(1, 3)):
-                k = rng.randrange(0, len(b) + 1)
-                op = rng.randrange(3)
-                if op == 0 or not b:
-                    b.insert(k, rng.choice(junk))
-                elif op == 1:
-                    del b[min(k, len(b) - 1)]
-                else:
-                    b[min(k, len(b) - 1)] = rng.choice(junk)
-            pat = bytes(b)
-        if not pat or b"\0" in pat or pat.startswith(b"-"):
-            continue
-        caseless = rng.random() < 0.3       # applied at parse time (sre_yyparser.y:244-279, sre_regex.c:170-214)
-        try:
-            want = _theirs(pat, caseless)
-        except subprocess.TimeoutExpired:
-            crashed += 1
-            continue
+    for pat, caseless in harness.frontend_fuzz_cases(int(os.environ.get("SRE_FUZZ_SEED", harness.FUZZ_SEED))):
+        want = _theirs(pat, caseless)
         if want is None:
             crashed += 1
             continue
@@ -79,38 +43,23 @@ def test_random_and_damaged_patterns_parse_like_the_reference(monkeypatch):
 
 
 def test_oracle_matches_the_live_reference_on_random_patterns():
-    """The oracle (oracle/*.c) against the real reference executors, through the
-    reference CLI's own call sequence: thompson / splitted thompson / pike /
+    """The oracle (oracle/*.c) against the real reference executors (their recorded
+    replies), through the reference CLI's own call sequence: thompson / splitted thompson / pike /
     splitted pike lines (captures, temp captures, pending matches) on random
     patterns — assertions, lazy quantifiers, counted repeats — and subjects."""
     ora = harness.OracleEngine()
-    rng = random.Random(int(os.environ.get("SRE_FUZZ_SEED", "99")) + 1000)
-    alphabet = b"abcx \n_."
     bad = []
     n = crashed = 0
-    for _ in range(500):
-        pats = [harness.random_regex(rng) for _ in range(1 if rng.random() < 0.75 else rng.randrange(2, 4))]
-        if any(p.startswith(b"-") for p in pats):
-            continue
-        subject = bytes(rng.choice(alphabet) for _ in range(rng.choice([0, 1, 3, 9, 20, 33])))
-        if subject.startswith(b"-"):
-            continue
+    for pats, subject in harness.oracle_fuzz_cases(int(os.environ.get("SRE_FUZZ_SEED", harness.FUZZ_SEED))):
         pat = pats
         with S.Pool() as pool:
             re = S.parse(pool, pats)
             prog = S.compile(pool, re)
-            argv = [CLI] + (["-n", str(len(pats))] if len(pats) > 1 else []) + pats + [subject]
-            try:
-                p = subprocess.run(argv, capture_output=True, timeout=20)
-            except subprocess.TimeoutExpired:
-                crashed += 1
-                continue
-            if p.returncode != 0:
+            want = harness.reference_reply(harness.reply_key("exec", pats, subject),
+                                           lambda: harness.cli_exec_reply(pats, subject), harness.REF_CLI)
+            if want is None:
                 crashed += 1                # the reference crashes on some programs (DESIGN.md §5)
                 continue
-            # the six engine lines close the output (the subject itself may hold newlines)
-            lines = [l for l in p.stdout.decode("latin-1").split("\n") if l][-6:]
-            want = [l for l in lines if "jitted" not in l]
             got = harness.cli_lines(ora, prog, subject, re.ncaps)
             n += 1
             if got != want:

@@ -8,14 +8,10 @@ trusts it:
   (b) the explicit expectations stored in the .t files themselves
       (`--- cap`, `--- match_id`, `--- temp_cap`, `--- no_match`);
   (c) reference runs over gen-data streams and find-all iteration traces;
-  (d) when oracle/_ref exists (build container, or shipped to the GPU box as a
-      binary), live differential runs against the real reference library.
+  (d) differential runs against the real reference library on random subjects
+      (its replies recorded in tests/golden/reference_fuzz.jsonl.gz).
 """
-import ctypes
 import os
-import random
-
-import pytest
 
 import sregex_amd as S
 import harness
@@ -105,35 +101,31 @@ def test_findall_iteration_matches_reference(lib):
 
 # ---------------------------------------------------------------- live vs _ref
 
-REF_SO = os.path.join(harness.ORACLE_DIR, "_ref", "libsregex_ref.so")
 
-
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (needs /root/reference)")
-def test_live_differential_against_reference_library(lib):
-    """Random subjects over a small alphabet, random chunkings, a pattern zoo
-    that leans on assertions, empty matches, nested stars and multi-regex."""
+def _live_replies(pats, subjects):
     import importlib.util
     spec = importlib.util.spec_from_file_location(
         "make_goldens", os.path.join(harness.GOLDEN, "make_goldens.py"))
     mg = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mg)
-    ref = mg.RefLib()
-    rng = random.Random(20261004)
-    zoo = [
-        [rb"(a*)*b"], [rb"(a*)+"], [rb"(a|b)*?c"], [rb"\bfoo\b"], [rb"^a|b$"], [rb"a$|ab"],
-        [rb"(?:a$|a)b?"], [rb"\Ba\B|c\b"], [rb"(a+)(b+)?"], [rb"x*"], [rb"(|a)+"], [rb"a{2,3}b{0,2}"],
-        [rb"\Aab|\n^b"], [rb"[^a]\z|a"], [rb"a", rb"ab", rb"\s+", rb"b$"], [rb"(a)|b", rb"(b)(c)?"],
-        [rb"$"], [rb"^"], [rb"\b"], [rb"(a?)*?b"], [rb"((a)|b)+"], [rb"a.c"], [rb"[a-c]+\.[^b]"],
-    ]
-    alphabet = b"ab c\n.x"
-    for pats in zoo:
-        rpool, rprog, ncaps = ref.compile(pats)
+    return mg.live_differential_replies(mg.RefLib(), pats, subjects)
+
+
+def test_live_differential_against_reference_library(lib):
+    """Random subjects over a small alphabet, random chunkings, a pattern zoo
+    that leans on assertions, empty matches, nested stars and multi-regex —
+    against the real reference library's replies (recorded in
+    tests/golden/reference_fuzz.jsonl.gz; the live library in oracle/_ref for
+    inputs without a recorded reply)."""
+    for pats, subjects in harness.live_differential_cases():
+        want = harness.reference_reply(harness.reply_key("live", pats, *subjects),
+                                       lambda: _live_replies(pats, subjects), harness.REF_SO)
+        ncaps = want["ncaps"]
+        assert len(want["runs"]) == len(subjects) == 60, pats
         with S.Pool() as pool:
             prog = S.compile(pool, S.parse(pool, pats))
-            for _ in range(60):
-                data = bytes(rng.choice(alphabet) for _ in range(rng.randrange(0, 24)))
-                assert harness.findall(ENG, prog, ncaps, data) == ref.pike_findall(rprog, ncaps, data), (pats, data)
+            for data, (findall, thompson) in zip(subjects, want["runs"]):
+                assert harness.findall(ENG, prog, ncaps, data) == findall, (pats, data)
                 t = ENG.thompson(prog)
-                assert t.exec(data, True) == ref.thompson(rprog, data), (pats, data)
+                assert t.exec(data, True) == thompson, (pats, data)
                 t.close()
-        ref.L.sre_destroy_pool(rpool)
