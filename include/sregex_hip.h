@@ -176,6 +176,53 @@ SRE_API int sre_hip_scan_batch(sre_hip_scanner_t *sc,
     const void *const *d_streams, const size_t *lens, size_t nstreams,
     sre_int_t *results, void *hip_stream);
 
+/* ---- line mode: one device buffer of delimited records, each record its own stream ---- */
+
+enum { SRE_HIP_LINES_ALL = 1 };   /* report every line, not only the lines with a match */
+
+/*
+ * Line mode.  d_buf is a DEVICE pointer to len bytes of records separated by the byte
+ * `delim` (0..255), at any alignment.  Each line is matched as an independent stream with
+ * a fresh context, exactly as sre_hip_scan_batch matches it.  Synchronous: returns when the
+ * rows are in `out`.  Everything runs on hip_stream.
+ *
+ * How the buffer is split (the rules of grep and wc -l):
+ *   - a line is a maximal run of bytes between delimiters; the delimiter belongs to no line;
+ *   - a buffer that ends with the delimiter has no empty line after it; one that does not
+ *     end with it has a final line without a delimiter;
+ *   - len == 0 gives 0 lines, "\n" one empty line, "a\n\nb" the lines "a", "" and "b";
+ *   - an empty line is a stream of length 0 and takes its EOF step, as an empty stream of
+ *     the batched API does;
+ *   - '\r' is an ordinary byte.
+ *
+ * *nlines    = number of lines in the buffer.
+ * *nreported = number of reported lines: every line with SRE_HIP_LINES_ALL, otherwise the
+ *              lines whose rc is not SRE_DECLINED (COUNT mode's SRE_ERROR lines are reported).
+ * The first min(cap, *nreported) reported lines are written to `out` in line order,
+ * 3 + sre_hip_scanner_result_slots(sc) sre_int_t each:
+ *   [0] line number (0-based)   [1] offset of the line's first byte in the buffer
+ *   [2] line length
+ *   [3..] exactly the record sre_hip_scan_batch returns for (d_buf + [1], [2]) as one
+ *         stream: rc, count, ovector (offsets relative to the line's first byte).
+ * out may be NULL when cap == 0 (counts only).  nlines / nreported may be NULL.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ *
+ * The table-driven scanner does the whole call on the device (split, per-line geometry,
+ * fix-up rounds, compaction of the rows); the NFA tier and the exact VM take each batch of
+ * lines through sre_hip_scan_enqueue / sre_hip_scan_results.  Line mode ignores
+ * sre_hip_scanner_set_tail_stream.  A call of either kind replaces the scanner's last
+ * call: after a line-mode call sre_hip_scan_results returns -1, and the diagnostics
+ * (last_fixups, last_exact_passes, last_lineage_passes: sums over the call's batches;
+ * last_kernel_ms: the summed scan kernels of all batches, or -1) describe the whole call.
+ * SRE_HIP_LINES_BATCH (environment, read on every call) caps the lines per internal batch.
+ */
+SRE_API int sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    int flags, sre_int_t *out, size_t cap, size_t *nlines, size_t *nreported, void *hip_stream);
+
+/* diagnostics: internal batches of lines the last sre_hip_scan_lines call ran (0 before the
+ * first call) */
+SRE_API int sre_hip_scanner_last_line_batches(sre_hip_scanner_t *sc);
+
 /* ---- helpers for drivers that have no HIP runtime binding of their own ---- */
 
 /* device buffer management (hipMalloc / hipFree / hipMemcpy) */

@@ -24,6 +24,7 @@ SRE_OK, SRE_ERROR, SRE_AGAIN, SRE_BUSY, SRE_DONE, SRE_DECLINED = 0, -1, -2, -3, 
 SRE_REGEX_CASELESS, SRE_REGEX_NEWLINE = 1, 2
 HIP_THOMPSON, HIP_PIKE_FIRST, HIP_PIKE_COUNT = 0, 1, 2
 ENGINE_AUTO, ENGINE_VM, ENGINE_SCAN, ENGINE_NFA = 0, 1, 2, 3
+HIP_LINES_ALL = 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -73,6 +74,9 @@ API = {
     "sre_hip_scan_enqueue": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _sz, _vp]),
     "sre_hip_scan_results": (ctypes.c_int, [_vp, _pssz]),
     "sre_hip_scan_batch": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _sz, _pssz, _vp]),
+    "sre_hip_scan_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _pssz, _sz,
+                                          ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
+    "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_alloc": (_vp, [_sz]),
     "sre_hip_free": (None, [_vp]),
     "sre_hip_upload": (ctypes.c_int, [_vp, _vp, _sz]),
@@ -363,6 +367,24 @@ class Scanner:
     def scan(self, d_ptrs, lens, hip_stream=None):
         self.enqueue(d_ptrs, lens, hip_stream)
         return self.results()
+
+    def scan_lines(self, ptr, length, delim=0x0A, all_lines=False, cap=1 << 20, hip_stream=None):
+        """sre_hip_scan_lines: every line of the device buffer (ptr, length) as its own stream.
+        Returns (nlines, nreported, rows); a row is [line no, start, length] + the line's record,
+        and rows holds the first min(cap, nreported) reported lines in order."""
+        width = 3 + self.slots
+        out = (ctypes.c_ssize_t * (cap * width))() if cap else None
+        nl, nr = _sz(), _sz()
+        if self.lib.sre_hip_scan_lines(self.h, ptr, length, delim, HIP_LINES_ALL if all_lines else 0, out, cap,
+                                       ctypes.byref(nl), ctypes.byref(nr), hip_stream) != 0:
+            raise RuntimeError("sre_hip_scan_lines failed")
+        take = min(cap, nr.value)
+        rows = [list(out[i * width:(i + 1) * width]) for i in range(take)]
+        return nl.value, nr.value, rows
+
+    @property
+    def last_line_batches(self):
+        return self.lib.sre_hip_scanner_last_line_batches(self.h)
 
 
 class DeviceBuffer:

@@ -17,6 +17,7 @@
 #include "sre_nfa.h"
 #include "sre_hip_nfa.h"
 #include "sre_pwave.h"
+#include "sre_hip_lines.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -105,6 +106,17 @@ struct sre_hip_scanner_s {
     size_t                    nmat_cap;
     void                     *d_nacc;
     sre_nfa_status_t         *d_nstatus, *h_nstatus;
+    /* line mode (sre_hip_scan_lines), grown on demand */
+    uint64_t                 *d_ends;           /* line table: one end offset per line */
+    size_t                    ends_cap;
+    uint64_t                 *d_lblk;           /* tile counts / per-workgroup sums of the geometry and compaction */
+    size_t                    lblk_cap;
+    int64_t                  *d_rows;           /* reported rows */
+    size_t                    rows_cap;         /* (caps in bytes) */
+    sre_lines_info_t         *d_linfo, *h_linfo;
+    bool                      last_lines;       /* the last call was a line-mode call */
+    int                       line_batches;     /* of the last line-mode call */
+    double                    lines_kernel_ms;  /* ... the sum of its scan kernels, -1 unknown */
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -157,6 +169,11 @@ scanner_release(void *data)
     if (sc->d_bvalid) (void) hipFree(sc->d_bvalid);
     if (sc->d_nmat) (void) hipFree(sc->d_nmat);
     if (sc->d_nacc) (void) hipFree(sc->d_nacc);
+    if (sc->d_ends) (void) hipFree(sc->d_ends);
+    if (sc->d_lblk) (void) hipFree(sc->d_lblk);
+    if (sc->d_rows) (void) hipFree(sc->d_rows);
+    if (sc->d_linfo) (void) hipFree(sc->d_linfo);
+    if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
     if (sc->ntab.follow) (void) hipFree(const_cast<uint64_t *>(sc->ntab.follow));
     if (sc->ntab.expand) (void) hipFree(const_cast<uint64_t *>(sc->ntab.expand));
@@ -482,6 +499,7 @@ extern "C" SRE_API double
 sre_hip_scanner_last_kernel_ms(sre_hip_scanner_t *sc)
 {
     float ms = 0.0f;
+    if (sc->last_lines) return sc->lines_kernel_ms;
     if (!sc->ev_valid) return -1.0;
     if (hipEventSynchronize(sc->ev1) != hipSuccess) return -1.0;
     if (hipEventElapsedTime(&ms, sc->ev0, sc->ev1) != hipSuccess) return -1.0;
@@ -581,6 +599,35 @@ hip_failed:
     return -1;
 }
 
+/* the fixed segment size (sre_hip_scanner_set_segment_bytes, else the experiment knob
+ * SRE_HIP_SEG_BYTES), 0 = automatic; also reads SRE_HIP_SEG_CAP */
+static uint64_t
+scan_seg_knobs(sre_hip_scanner_t *sc)
+{
+    uint64_t seg = sc->seg_override;
+    const char *e = getenv("SRE_HIP_SEG_BYTES");        /* experiment knobs */
+    if (seg == 0 && e && atoi(e) > 0 && atoi(e) % 256 == 0) seg = (uint64_t) atoi(e);
+    e = getenv("SRE_HIP_SEG_CAP");
+    sc->seg_cap_env = e && atoi(e) > 0 ? (uint64_t) atoi(e) : 0;
+    return seg;
+}
+
+/* lanes the chip holds at once with this scanner's kernel */
+static uint64_t
+scan_resident(sre_hip_scanner_t *sc)
+{
+    if (sc->blocks_per_cu == 0) {
+        sc->blocks_per_cu = sc->engine == SRE_HIP_ENGINE_NFA
+                                ? (sc->use_sa ? sre_nfa_sa_blocks_per_cu(&sc->satab)
+                                              : sre_nfa_blocks_per_cu(sc->mode == SRE_HIP_THOMPSON ? 0 : 1, sc->ntab.nslices,
+                                                                      sc->ntab.nassert != 0))
+                                                             : sre_scan_blocks_per_cu(&sc->tab->h);
+    }
+    return (uint64_t) sre_hip_cu_count() * (uint64_t) sc->blocks_per_cu * SRE_SCAN_BLOCK;
+}
+
+static int scan_buffers(sre_hip_scanner_t *sc, size_t nstreams, uint64_t seg, uint64_t nsegs);
+
 /* segment geometry: one lane per segment, 256 lanes per workgroup.  The number
  * of workgroups is steered towards a whole multiple of what the chip holds at
  * once (LDS-limited: 160 KiB per CU), so the last round of workgroups is not
@@ -591,44 +638,26 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
 {
     uint64_t total = 0;
     for (size_t i = 0; i < nstreams; i++) total += sc->h_lens[i];
-    uint64_t seg = sc->seg_override;
-    {
-        const char *e = getenv("SRE_HIP_SEG_BYTES");        /* experiment knobs */
-        if (seg == 0 && e && atoi(e) > 0 && atoi(e) % 256 == 0) seg = (uint64_t) atoi(e);
-        e = getenv("SRE_HIP_SEG_CAP");
-        sc->seg_cap_env = e && atoi(e) > 0 ? (uint64_t) atoi(e) : 0;
-    }
+    uint64_t seg = scan_seg_knobs(sc);
     if (seg == 0) {
         /* as few rounds of resident workgroups as keep a segment <= ~40 KiB: longer
          * segments mean fewer summaries to verify and a smaller share of warm-up,
          * shorter ones keep every CU busy on small batches */
-        if (sc->blocks_per_cu == 0) {
-            sc->blocks_per_cu = sc->engine == SRE_HIP_ENGINE_NFA
-                                    ? (sc->use_sa ? sre_nfa_sa_blocks_per_cu(&sc->satab)
-                                                  : sre_nfa_blocks_per_cu(sc->mode == SRE_HIP_THOMPSON ? 0 : 1, sc->ntab.nslices,
-                                                                          sc->ntab.nassert != 0))
-                                                                 : sre_scan_blocks_per_cu(&sc->tab->h);
-        }
-        const uint64_t resident = (uint64_t) sre_hip_cu_count() * (uint64_t) sc->blocks_per_cu * SRE_SCAN_BLOCK;
+        const uint64_t resident = scan_resident(sc);
         /* (measured, one box, 4 GiB: the COUNT kernel at two workgroups per CU takes 1.33 ms
          * with 16 640-byte segments = two rounds of resident workgroups, 1.25 ms with 33 280 =
          * one round, and 1.67 ms with 21 760 = one and a half: a whole number of rounds
          * matters, and one long round beats two short ones; profiles/r02_experiments.txt) */
         const uint64_t seg_cap = sc->seg_cap_env ? sc->seg_cap_env : 40960;
-        uint64_t       rounds = (total + resident * seg_cap - 1) / (resident * seg_cap);
-        if (rounds < 1) rounds = 1;
-        /* ... and a few workgroup slots are left spare: a grid that needs EVERY slot of its
-         * last round waits a whole extra round for the stragglers when anything else (the
-         * tail kernels of the previous call) holds a slot at launch — 509 workgroups on 512
-         * slots ran 30 % slower than 505 */
-        const uint64_t lanes = resident * rounds - (resident * rounds >> 6);
-        seg = (total / lanes + SRE_SCAN_SEG_ALIGN) / SRE_SCAN_SEG_ALIGN * SRE_SCAN_SEG_ALIGN;
-        /* a small batch does not fill the chip whatever the segment size, and a lane's walk
-         * is a serial chain (~1.5 us per 64-byte round): short segments, although half of
-         * what such a lane reads is then warm-up (a 1 MiB chunk: 35 us at 1 KiB, 13 us at 256 B) */
-        if (seg < 256) seg = 256;
-        /* rows that are a multiple of 4 KiB apart land on the same HBM channels */
-        if (seg % 4096 == 0) seg += SRE_SCAN_SEG_ALIGN;
+        /* (sre_scan_auto_segment:) ... and a few workgroup slots are left spare: a grid that
+         * needs EVERY slot of its last round waits a whole extra round for the stragglers when
+         * anything else (the tail kernels of the previous call) holds a slot at launch — 509
+         * workgroups on 512 slots ran 30 % slower than 505.  A small batch does not fill the
+         * chip whatever the segment size, and a lane's walk is a serial chain (~1.5 us per
+         * 64-byte round): short segments, although half of what such a lane reads is then
+         * warm-up (a 1 MiB chunk: 35 us at 1 KiB, 13 us at 256 B).  Rows that are a multiple
+         * of 4 KiB apart land on the same HBM channels. */
+        seg = sre_scan_auto_segment(total, resident, seg_cap);
     }
     uint64_t nsegs = 0;
     for (size_t i = 0; i < nstreams; i++) {
@@ -666,6 +695,16 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
         }
         return 0;
     }
+    return scan_buffers(sc, nstreams, seg, nsegs);
+hip_failed:
+    return -1;
+}
+
+/* the table-driven scanner's per-call buffers: summaries, the chain check's digest (small
+ * batches, not COUNT: sets geom.digest), the capture walker's scratch */
+static int
+scan_buffers(sre_hip_scanner_t *sc, size_t nstreams, uint64_t seg, uint64_t nsegs)
+{
     if (nsegs > sc->sum_cap) {
         if (sc->d_sum) (void) hipFree(sc->d_sum);
         sc->d_sum = NULL;
@@ -970,6 +1009,7 @@ sre_hip_scan_enqueue(sre_hip_scanner_t *sc, const void *const *d_streams, const 
     size_t nstreams, void *hip_stream)
 {
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    sc->last_lines = false;
     sc->fixup_rounds = 0;
     sc->exact_passes = 0;
     sc->lineage_passes = 0;
@@ -1075,11 +1115,28 @@ hip_failed:
     return -1;
 }
 
+/* line mode: the batch's status words reduced on the device to h_linfo->pending (streams not
+ * done) and h_linfo->maps (streams with need_maps); the host reads 16 bytes */
+static int
+lines_status_counters(sre_hip_scanner_t *sc, size_t n, hipStream_t stream)
+{
+    SRE_HIP_TRY(sre_launch_lines_settle(sc->d_status, (uint32_t) n, sc->d_linfo, stream));
+    SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, 2 * sizeof(uint64_t),
+                               hipMemcpyDeviceToHost, stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    return 0;
+hip_failed:
+    return -1;
+}
+
 /* Segments behind a broken state chain are re-run from the exact carried state until
  * every stream's verified prefix reaches its end (h_status holds the latest status on
- * return).  with_captures: the capture kernel runs behind every round. */
+ * return).  with_captures: the capture kernel runs behind every round.  counters (line
+ * mode): the status stays on the device, h_linfo->pending / maps hold its counts (on entry:
+ * of the pass before; on return: of the last round) */
 static int
-scan_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool with_captures, bool *psettled)
+scan_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool with_captures, bool *psettled,
+            bool counters = false)
 {
     bool settled = true;
     int  batch = sc->mode == SRE_HIP_PIKE_COUNT ? 2 : SRE_SPECULATIVE_FIXUPS + 1;
@@ -1090,7 +1147,8 @@ scan_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool with_captu
      * queued at once); COUNT: 2, 4, 8, ... speculative rounds. */
     for (;;) {
         size_t pending = 0;
-        for (size_t i = 0; i < n; i++) pending += sc->h_status[i].done ? 0 : 1;
+        if (counters) pending = (size_t) sc->h_linfo->pending;
+        else for (size_t i = 0; i < n; i++) pending += sc->h_status[i].done ? 0 : 1;
         if (pending == 0) break;
         settled = false;
         for (int r = 0; r < batch; r++) {
@@ -1129,9 +1187,13 @@ scan_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool with_captu
                                                 sc->ovec_slots, NULL, NULL, 0, 0, stream));
             }
         }
-        SRE_HIP_TRY(hipMemcpyAsync(sc->h_status, sc->d_status, n * sizeof(sre_stream_status_t),
-                                   hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        if (counters) {
+            if (lines_status_counters(sc, n, stream) != 0) return -1;
+        } else {
+            SRE_HIP_TRY(hipMemcpyAsync(sc->h_status, sc->d_status, n * sizeof(sre_stream_status_t),
+                                       hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
         batch = sc->mode == SRE_HIP_PIKE_COUNT ? (batch < 16 ? 2 * batch : 16) : 1;
     }
     if (psettled) *psettled = settled;
@@ -1140,9 +1202,38 @@ hip_failed:
     return -1;
 }
 
+/* a match whose lineage outran the plain backward walk: build the per-segment ancestor maps
+ * of the flagged streams in parallel and walk again, jumping */
+static int
+scan_lineage_pass(sre_hip_scanner_t *sc, hipStream_t stream)
+{
+    if (sc->geom.nsegs > sc->maps_cap) {
+        if (sc->d_maps) (void) hipFree(sc->d_maps);
+        if (sc->d_blocks) (void) hipFree(sc->d_blocks);
+        sc->d_maps = sc->d_blocks = NULL;
+        sc->maps_cap = 0;
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_maps),
+                              sc->geom.nsegs * sizeof(sre_seg_lineage_t)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_blocks),
+                              (sc->geom.nsegs / SRE_LINEAGE_BLOCK + 1) * sizeof(sre_seg_lineage_t)));
+        sc->maps_cap = sc->geom.nsegs;
+    }
+    sc->lineage_passes++;
+    SRE_HIP_TRY(sre_launch_lineage(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum,
+                                   sc->d_status, sc->d_maps, sc->d_blocks, stream));
+    SRE_HIP_TRY(sre_launch_captures(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum,
+                                    sc->d_status, sc->d_scratch, sc->d_records,
+                                    sc->ovec_slots, sc->d_maps, sc->d_blocks,
+                                    1, 0, stream));
+    return 0;
+hip_failed:
+    return -1;
+}
+
 extern "C" SRE_API int
 sre_hip_scan_results(sre_hip_scanner_t *sc, sre_int_t *results)
 {
+    if (sc->last_lines) return -1;      /* the last call was a line-mode call: nothing to collect */
     if (sc->last_n == 0) return 0;
     const size_t n = sc->last_n;
     hipStream_t  stream = sc->last_stream;
@@ -1162,25 +1253,8 @@ sre_hip_scan_results(sre_hip_scanner_t *sc, sre_int_t *results)
             size_t want = 0;
             for (size_t i = 0; i < n; i++) want += sc->h_status[i].need_maps != 0;
             if (want) {
-                if (sc->geom.nsegs > sc->maps_cap) {
-                    if (sc->d_maps) (void) hipFree(sc->d_maps);
-                    if (sc->d_blocks) (void) hipFree(sc->d_blocks);
-                    sc->d_maps = sc->d_blocks = NULL;
-                    sc->maps_cap = 0;
-                    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_maps),
-                                          sc->geom.nsegs * sizeof(sre_seg_lineage_t)));
-                    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_blocks),
-                                          (sc->geom.nsegs / SRE_LINEAGE_BLOCK + 1) * sizeof(sre_seg_lineage_t)));
-                    sc->maps_cap = sc->geom.nsegs;
-                }
-                sc->lineage_passes++;
                 settled = false;
-                SRE_HIP_TRY(sre_launch_lineage(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum,
-                                               sc->d_status, sc->d_maps, sc->d_blocks, stream));
-                SRE_HIP_TRY(sre_launch_captures(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum,
-                                                sc->d_status, sc->d_scratch, sc->d_records,
-                                                sc->ovec_slots, sc->d_maps, sc->d_blocks,
-                                                1, 0, stream));
+                if (scan_lineage_pass(sc, stream) != 0) return -1;
             }
         }
     }
@@ -1229,6 +1303,240 @@ sre_hip_scan_batch(sre_hip_scanner_t *sc, const void *const *d_streams, const si
     return sre_hip_scan_results(sc, results);
 }
 
+/* ---- line mode (sre_hip_scan_lines) ---- */
+
+/* grow-only device buffer */
+template <typename T>
+static int
+lines_grow(T **p, size_t *cap, size_t bytes)
+{
+    if (bytes <= *cap) return 0;
+    if (*p) (void) hipFree(*p);
+    *p = NULL;
+    *cap = 0;
+    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(p), bytes));
+    *cap = bytes;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* lines per batch: SRE_HIP_LINES_BATCH (experiment knob, read on every call; at most 2^24) or SRE_LINES_BATCH */
+static uint64_t
+lines_batch_limit(void)
+{
+    const char     *e = getenv("SRE_HIP_LINES_BATCH");
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (v < (1ll << 24) ? (uint64_t) v : (uint64_t) 1 << 24) : SRE_LINES_BATCH;
+}
+
+/* the split: the line table of the buffer in sc->d_ends, *pn lines.  The host reads one word. */
+static int
+lines_split(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, hipStream_t stream, uint64_t *pn)
+{
+    *pn = 0;
+    if (len == 0) return 0;
+    const uint64_t head = reinterpret_cast<uintptr_t>(d_buf) & 15u;
+    const uint64_t ntiles = (head + len + SRE_LINES_TILE_BYTES - 1) / SRE_LINES_TILE_BYTES;
+    /* (the same words later hold the geometry's and the compaction's per-workgroup sums) */
+    const uint64_t nblk = (lines_batch_limit() + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS + 1;
+    if (lines_grow(&sc->d_lblk, &sc->lblk_cap, (ntiles > nblk ? ntiles : nblk) * sizeof(uint64_t)) != 0) return -1;
+    SRE_HIP_TRY(sre_launch_lines_count(d_buf, len, (uint32_t) delim, sc->d_lblk, sc->d_linfo, stream));
+    SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->nlines, &sc->d_linfo->nlines, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    if (lines_grow(&sc->d_ends, &sc->ends_cap, sc->h_linfo->nlines * sizeof(uint64_t)) != 0) return -1;
+    SRE_HIP_TRY(sre_launch_lines_write(d_buf, len, (uint32_t) delim, sc->d_lblk, sc->d_ends, stream));
+    *pn = sc->h_linfo->nlines;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* table-driven scanner: every batch on the device; the host reads a few words per batch */
+static int
+lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
+                  uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms)
+{
+    const size_t   slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
+    const uint64_t bmax = lines_batch_limit();
+    const uint64_t rcap = cap < n ? cap : n;
+    const uint64_t seg_fixed = scan_seg_knobs(sc);
+    const uint64_t resident = scan_resident(sc);
+    const uint64_t seg_cap = sc->seg_cap_env ? sc->seg_cap_env : 40960;
+    if (rcap && lines_grow(&sc->d_rows, &sc->rows_cap, rcap * width * sizeof(int64_t)) != 0) return -1;
+    SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->reported, 0, sizeof(uint64_t), stream));
+    if (sc->ev0 == NULL) {
+        SRE_HIP_TRY(hipEventCreate(&sc->ev0));
+        SRE_HIP_TRY(hipEventCreate(&sc->ev1));
+    }
+    for (uint64_t i0 = 0; i0 < n;) {
+        const uint64_t nmax = bmax < n - i0 ? bmax : n - i0;
+        if (scanner_reserve(sc, nmax) != 0) return -1;
+        /* how many lines the batch takes, its segment size and the stream arrays, on the device */
+        SRE_HIP_TRY(sre_launch_lines_geometry(d_buf, sc->d_ends, n, i0, nmax, SRE_LINES_WALK_MAX, seg_fixed, resident,
+                                              seg_cap, reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens,
+                                              sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
+        if (scan_buffers(sc, nb, seg, nsegs) != 0) return -1;
+        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
+        sc->geom.lens = sc->d_lens;
+        sc->geom.seg_first = sc->d_seg_first;
+        sc->geom.nstreams = (uint32_t) nb;
+        sc->geom.seg_bytes = (uint32_t) seg;
+        sc->geom.nsegs = nsegs;
+        sc->geom.init_variant = 0;
+        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
+        sc->geom.entry_state = 0;
+        sc->geom.one_ptr = NULL;
+        sc->geom.one_len = 0;
+        sc->geom_one = 0;
+        sc->fixup_rounds = 0;
+        sc->exact_passes = 0;
+        sc->lineage_passes = 0;
+        /* as sre_hip_scan_enqueue queues them */
+        SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
+        SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));
+        SRE_HIP_TRY(hipEventRecord(sc->ev1, stream));
+        SRE_HIP_TRY(sre_launch_verify(sc->tab->h, sc->geom, sc->d_sum, sc->d_acc, sc->d_status, stream));
+        SRE_HIP_TRY(sre_launch_captures(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status,
+                                        sc->d_scratch, sc->d_records, sc->ovec_slots, NULL, NULL, 0, 0, stream));
+        /* ... and settle as sre_hip_scan_results does, from two device counters */
+        if (lines_status_counters(sc, nb, stream) != 0) return -1;
+        if (scan_settle(sc, nb, stream, true, NULL, true) != 0) return -1;
+        if (sc->mode != SRE_HIP_THOMPSON && sc->h_linfo->maps != 0 && scan_lineage_pass(sc, stream) != 0) return -1;
+        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
+                                             sc->d_linfo, sc->d_rows, rcap, stream));
+        {
+            float ms = 0.0f;
+            SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
+            *kms += ms;
+        }
+        *fixups += sc->fixup_rounds;
+        *exact += sc->exact_passes;
+        *lineage += sc->lineage_passes;
+        sc->line_batches++;
+        i0 = i1;
+    }
+    SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->reported, &sc->d_linfo->reported, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                               stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    *pnrep = n ? sc->h_linfo->reported : 0;
+    {
+        const uint64_t take = *pnrep < rcap ? *pnrep : rcap;
+        if (take) {
+            SRE_HIP_TRY(hipMemcpyAsync(out, sc->d_rows, take * width * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* NFA tier and exact VM: each batch's slice of the line table comes to the host and goes through
+ * sre_hip_scan_enqueue / sre_hip_scan_results; the rows are compacted on the host */
+static int
+lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
+                uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms)
+{
+    const size_t              slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
+    const uint64_t            bmax = lines_batch_limit();
+    const uint8_t            *buf = static_cast<const uint8_t *>(d_buf);
+    std::vector<uint64_t>     ends;
+    std::vector<const void *> ptrs;
+    std::vector<size_t>       lens;
+    std::vector<sre_int_t>    recs;
+    uint64_t                  nrep = 0;
+    for (uint64_t i0 = 0; i0 < n;) {
+        const uint64_t nb = bmax < n - i0 ? bmax : n - i0;
+        /* ends[0]: the end of the line in front of the batch (its first line starts behind it) */
+        ends.resize(nb + 1);
+        if (i0) {
+            SRE_HIP_TRY(hipMemcpyAsync(ends.data(), sc->d_ends + i0 - 1, (nb + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        } else {
+            SRE_HIP_TRY(hipMemcpyAsync(ends.data() + 1, sc->d_ends, nb * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        ptrs.resize(nb);
+        lens.resize(nb);
+        for (uint64_t j = 0; j < nb; j++) {
+            const uint64_t st = (i0 + j == 0) ? 0 : ends[j] + 1;
+            ptrs[j] = buf + st;
+            lens[j] = ends[j + 1] - st;
+        }
+        recs.resize(nb * slots);
+        if (sre_hip_scan_batch(sc, ptrs.data(), lens.data(), nb, recs.data(), stream) != 0) return -1;
+        *fixups += sc->fixup_rounds;
+        *exact += sc->exact_passes;
+        *lineage += sc->lineage_passes;
+        const double ms = sre_hip_scanner_last_kernel_ms(sc);
+        *kms = (ms < 0 || *kms < 0) ? -1.0 : *kms + ms;
+        for (uint64_t j = 0; j < nb; j++) {
+            const sre_int_t *rec = recs.data() + j * slots;
+            if (!all && rec[0] == SRE_DECLINED) continue;
+            if (nrep < cap) {
+                sre_int_t *row = out + nrep * width;
+                row[0] = (sre_int_t) (i0 + j);
+                row[1] = (sre_int_t) (static_cast<const uint8_t *>(ptrs[j]) - buf);
+                row[2] = (sre_int_t) lens[j];
+                memcpy(row + 3, rec, slots * sizeof(sre_int_t));
+            }
+            nrep++;
+        }
+        sc->line_batches++;
+        i0 += nb;
+    }
+    *pnrep = nrep;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+extern "C" SRE_API int
+sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags,
+    sre_int_t *out, size_t cap, size_t *nlines, size_t *nreported, void *hip_stream)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || (cap != 0 && out == NULL)
+        || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const int   all = (flags & SRE_HIP_LINES_ALL) != 0;
+    uint64_t    n = 0, nrep = 0;
+    int         fixups = 0, exact = 0, lineage = 0, rc = -1;
+    double      kms = sc->engine == SRE_HIP_ENGINE_VM ? -1.0 : 0.0;
+    sc->line_batches = 0;
+    if (sc->d_linfo == NULL) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_linfo), sizeof(sre_lines_info_t)));
+    if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
+    if (lines_split(sc, d_buf, len, delim, stream, &n) == 0) {
+        rc = sc->engine == SRE_HIP_ENGINE_SCAN
+                 ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms)
+                 : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms);
+    }
+hip_failed:
+    /* this call replaces the scanner's last one; its diagnostics describe the whole call */
+    sc->last_lines = true;
+    sc->last_n = 0;
+    sc->ev_valid = 0;
+    sc->fixup_rounds = fixups;
+    sc->exact_passes = exact;
+    sc->lineage_passes = lineage;
+    sc->lines_kernel_ms = rc == 0 ? kms : -1.0;
+    if (rc != 0) return -1;
+    if (nlines) *nlines = (size_t) n;
+    if (nreported) *nreported = (size_t) nrep;
+    return 0;
+}
+
+extern "C" SRE_API int
+sre_hip_scanner_last_line_batches(sre_hip_scanner_t *sc)
+{
+    return sc->line_batches;
+}
+
 /* One device-resident buffer through the scanner, for sre_vm_*_exec on large
  * whole-buffer calls.  `init_variant` is the SRE_DFA_INIT_* of a search on a
  * re-armed context; *poisoned reports the "threads still listed at eof" state
@@ -1273,6 +1581,7 @@ sre_hip_scan_stream_chunk(sre_hip_scanner_t *sc, const void *d_buf, size_t len, 
         ~Midway() { run(); }
     } mid{midway, midway_arg};
     if (sc->engine != SRE_HIP_ENGINE_SCAN || sc->mode == SRE_HIP_PIKE_COUNT) return -1;
+    sc->last_lines = false;
     sc->fixup_rounds = 0;
     sc->exact_passes = 0;
     sc->lineage_passes = 0;

@@ -1,0 +1,67 @@
+/*
+ * sre_hip_lines.h — line mode (sre_hip_scan_lines): the delimiter split of one device
+ * buffer, the per-batch geometry the scan kernels read, the settle counters and the
+ * compaction of the reported rows (sre_hip_lines.hip).  DESIGN.md §4.11.
+ */
+#ifndef SRE_HIP_LINES_H
+#define SRE_HIP_LINES_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "sre_hip_scan.h"
+
+/* split: a workgroup of SRE_LINES_THREADS lanes owns one tile of 16-byte aligned chunks, each lane
+ * loads SRE_LINES_CHUNKS chunks of it (lane x, step k: chunk k * SRE_LINES_THREADS + x of the tile).
+ * Tiles are counted from the 16-byte aligned address at or below the buffer: tile t starts at
+ * buffer offset t * SRE_LINES_TILE_BYTES - (d_buf % 16). */
+#define SRE_LINES_THREADS     256u
+#define SRE_LINES_CHUNKS      16u
+#define SRE_LINES_TILE_BYTES  (SRE_LINES_THREADS * SRE_LINES_CHUNKS * 16u)     /* 64 KiB */
+/* geometry and compaction passes: items (lines) per workgroup, 4 per lane */
+#define SRE_LINES_ITEMS       1024u
+/* lines per batch (SRE_HIP_LINES_BATCH overrides), and the most capture-walker scratch a batch may
+ * take: lines x (segment + 16) x 2 B — 1 Mi lines of 96 B take 570 MB at 256-byte segments */
+#define SRE_LINES_BATCH       (1u << 20)
+#define SRE_LINES_WALK_MAX (1ull << 30)
+
+/* device words of one line-mode call; the host reads them in small copies */
+typedef struct {
+    uint64_t nlines;        /* split: lines in the buffer */
+    uint64_t i1;            /* batch: first line behind it */
+    uint64_t bytes;         /* batch: bytes of its lines */
+    uint64_t seg;           /* batch: segment size */
+    uint64_t nsegs;         /* batch: segments */
+    uint64_t reported;      /* running count of reported lines, all batches so far */
+    uint64_t pending;       /* settle: streams of the batch whose status is not done */
+    uint64_t maps;          /* settle: streams that asked for lineage maps (need_maps) */
+} sre_lines_info_t;
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* split pass 1 + tile scan: info->nlines.  ends / tiles sized by the caller: ntiles =
+ * ceil((d_buf % 16 + len) / SRE_LINES_TILE_BYTES) entries of tiles */
+hipError_t sre_launch_lines_count(const void *d_buf, uint64_t len, uint32_t delim, uint64_t *d_tiles,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* split pass 2: ends[i] = offset of line i's delimiter (len for a final line without one) */
+hipError_t sre_launch_lines_write(const void *d_buf, uint64_t len, uint32_t delim, const uint64_t *d_tiles,
+    uint64_t *d_ends, hipStream_t stream);
+/* the batch from line i0: at most bmax lines whose capture-walker buffer (see SRE_LINES_WALK_MAX) fits, its
+ * segment size (seg_fixed, else sre_scan_auto_segment(bytes, resident, seg_cap)) and the arrays
+ * sre_scan_geom_t reads (ptrs / lens / seg_first, nmax + 1 entries); info->i1, bytes, seg, nsegs */
+hipError_t sre_launch_lines_geometry(const void *d_buf, const uint64_t *d_ends, uint64_t nlines, uint64_t i0,
+    uint64_t nmax, uint64_t scratch_max, uint64_t seg_fixed, uint64_t resident, uint64_t seg_cap,
+    const uint8_t **d_ptrs, uint64_t *d_lens, uint64_t *d_seg_first, uint64_t *d_blk,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* info->pending / info->maps of the batch's n status words (zeroed first) */
+hipError_t sre_launch_lines_settle(const sre_stream_status_t *d_status, uint32_t n, sre_lines_info_t *d_info,
+    hipStream_t stream);
+/* ordered compaction of the batch (lines i0 .. i0 + info->i1 - i0) behind info->reported: rows
+ * [line, start, len, record] with index < cap go to d_rows */
+hipError_t sre_launch_lines_compact(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0,
+    int all, const uint64_t *d_ends, uint64_t *d_blk, sre_lines_info_t *d_info, int64_t *d_rows, uint64_t cap,
+    hipStream_t stream);
+#ifdef __cplusplus
+}
+#endif
+#endif

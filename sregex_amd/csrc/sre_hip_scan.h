@@ -258,6 +258,22 @@ typedef struct {
 #define SRE_GEOM_ONE       4u       /* nstreams == 1, described by one_ptr / one_len / nsegs */
 
 #ifdef __HIPCC__
+/* automatic segment size of a batch of `total` bytes: as few rounds of `resident` lanes as keep a
+ * segment <= seg_cap bytes, a few workgroup slots of the last round spare, a multiple of
+ * SRE_SCAN_SEG_ALIGN, at least 256 B, never a multiple of 4 KiB (rationale: scan_geometry,
+ * sre_hip_batch.cpp).  Host and device: line mode sizes its batches on the device. */
+static __host__ __device__ inline uint64_t
+sre_scan_auto_segment(uint64_t total, uint64_t resident, uint64_t seg_cap)
+{
+    uint64_t rounds = (total + resident * seg_cap - 1) / (resident * seg_cap);
+    if (rounds < 1) rounds = 1;
+    const uint64_t lanes = resident * rounds - (resident * rounds >> 6);
+    uint64_t       seg = (total / lanes + SRE_SCAN_SEG_ALIGN) / SRE_SCAN_SEG_ALIGN * SRE_SCAN_SEG_ALIGN;
+    if (seg < 256) seg = 256;
+    if (seg % 4096 == 0) seg += SRE_SCAN_SEG_ALIGN;
+    return seg;
+}
+
 static __device__ inline const uint8_t *
 geom_ptr(const sre_scan_geom_t &G, uint32_t s)
 {
