@@ -38,8 +38,8 @@ enum {
     SRE_HIP_ENGINE_AUTO = 0, /* table-driven scanner when the program admits one  */
     SRE_HIP_ENGINE_VM   = 1, /* exact bytecode VM kernel, one lane per stream     */
     SRE_HIP_ENGINE_SCAN = 2, /* table-driven segment-parallel scanner, or fail    */
-    SRE_HIP_ENGINE_NFA  = 3  /* bit-parallel NFA scanner (<= 64 list-able threads held as
-                                a 64-bit mask per lane), or fail: the tier for programs
+    SRE_HIP_ENGINE_NFA  = 3  /* bit-parallel NFA scanner (<= 256 list-able threads as 1, 2
+                                or 4 64-bit words per lane), or fail: the tier for programs
                                 whose ordered-list automaton is too large */
 };
 
@@ -105,6 +105,10 @@ SRE_API int sre_hip_scanner_last_lineage_passes(sre_hip_scanner_t *sc);
  * lookup advances 8 / bits bytes); 0 for the VM engine.  Names the kernel
  * variant (sre_k_scan<mode, bits>) in profiles. */
 SRE_API int sre_hip_scanner_class_bits(sre_hip_scanner_t *sc);
+
+/* bits of the thread set a lane of the NFA tier holds: 64, 128 or 256 (counted after equivalent
+ * threads are merged); 0 unless the scanner runs on the NFA tier */
+SRE_API int sre_hip_scanner_nfa_bits(sre_hip_scanner_t *sc);
 
 /* name of the dominant kernel of a scan with this scanner, as rocprofv3 prints it
  * (e.g. "sre_k_scan<1, 2>"); owned by the scanner */

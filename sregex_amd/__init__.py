@@ -67,6 +67,7 @@ API = {
     "sre_hip_compat_trim": (ctypes.c_int, []),
     "sre_hip_scanner_set_tail_stream": (ctypes.c_int, [_vp, _vp]),
     "sre_hip_scanner_class_bits": (ctypes.c_int, [_vp]),
+    "sre_hip_scanner_nfa_bits": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_kernel_name": (ctypes.c_char_p, [_vp]),
     "sre_hip_scanner_last_kernel_ms": (ctypes.c_double, [_vp]),
     "sre_hip_scanner_last_segment_bytes": (_sz, [_vp]),
@@ -326,6 +327,11 @@ class Scanner:
     @property
     def class_bits(self):
         return self.lib.sre_hip_scanner_class_bits(self.h)
+
+    @property
+    def nfa_bits(self):
+        """bits of a lane's thread set on the NFA tier (64, 128 or 256), 0 on the other engines"""
+        return self.lib.sre_hip_scanner_nfa_bits(self.h)
 
     @property
     def last_kernel_ms(self):

@@ -16,6 +16,8 @@
 #include "sre_dfa.h"
 #include "sre_nfa.h"
 #include "sre_hip_nfa.h"
+#include "sre_nfa_wide.h"
+#include "sre_hip_nfa_wide.h"
 #include "sre_pwave.h"
 #include "sre_hip_lines.h"
 #include <stdio.h>
@@ -89,6 +91,12 @@ struct sre_hip_scanner_s {
     sre_nfa_tables_t          ntab;             /* device pointers inside */
     sre_nfa_sa_tables_t       satab;            /* the shift-and form (sre_nfa.h), when the program has one */
     bool                      use_sa;
+    /* the wide form (sre_nfa_wide.h), when the 64-bit form declines for width alone */
+    sre_nfa_wide_t           *wnfa;
+    sre_nfa_wide_tables_t     wtab;             /* device pointers inside */
+    uint64_t                 *d_wsets;          /* [nsegs][2][W] entry and exit sets of the wide kernel */
+    bool                      wide_kernel;      /* the wide form runs on sre_k_nfa_wide (else, as a 64-bit shift-and
+                                                   form, on sre_k_nfa_sa: nfa_wide_as_sa) */
     /* find-all counting on the NFA tier (nfa_count_rounds) */
     struct NfaCount          *cnt;
     uint8_t                  *d_sflags, *h_sflags;      /* per stream of a round: SRE_SFLAG_* */
@@ -181,6 +189,12 @@ scanner_release(void *data)
     if (sc->satab.accept) (void) hipFree(const_cast<uint64_t *>(sc->satab.accept));
     if (sc->satab.lut) (void) hipFree(const_cast<uint64_t *>(sc->satab.lut));
     if (sc->satab.expand) (void) hipFree(const_cast<uint64_t *>(sc->satab.expand));
+    if (sc->d_wsets) (void) hipFree(sc->d_wsets);
+    if (sc->wtab.accept) (void) hipFree(const_cast<uint64_t *>(sc->wtab.accept));
+    if (sc->wtab.lut) (void) hipFree(const_cast<uint64_t *>(sc->wtab.lut));
+    if (sc->wtab.expand) (void) hipFree(const_cast<uint64_t *>(sc->wtab.expand));
+    if (sc->wtab.kind) (void) hipFree(const_cast<uint8_t *>(sc->wtab.kind));
+    sre_nfa_wide_free(sc->wnfa);
     sre_nfa_free(sc->nfa);
     sre_scan_tables_release(sc->tab);
     sre_dfa_free(sc->dfa);
@@ -268,11 +282,114 @@ hip_failed:
     return -1;
 }
 
+/* device copies of the wide form's tables */
+static int
+nfa_wide_upload(sre_hip_scanner_t *sc)
+{
+    const sre_nfa_wide_t  *w = sc->wnfa;
+    sre_nfa_wide_tables_t &t = sc->wtab;
+    const uint32_t         W = w->W;
+    std::vector<uint64_t>  acc((size_t) 256 * W);
+    for (unsigned c = 0; c < 256; c++) {
+        for (uint32_t i = 0; i < W; i++) acc[(size_t) c * W + i] = w->accept[c][i];
+    }
+    uint64_t *d_acc = NULL, *d_lut = NULL, *d_exp = NULL;
+    uint8_t  *d_kind = NULL;
+    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_acc), acc.size() * sizeof(uint64_t)));
+    t.accept = d_acc;
+    SRE_HIP_TRY(hipMemcpy(d_acc, acc.data(), acc.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_kind), 256));
+    t.kind = d_kind;
+    SRE_HIP_TRY(hipMemcpy(d_kind, w->kind, 256, hipMemcpyHostToDevice));
+    if (w->nlut) {
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_lut), w->lut.size() * sizeof(uint64_t)));
+        t.lut = d_lut;
+        SRE_HIP_TRY(hipMemcpy(d_lut, w->lut.data(), w->lut.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    if (w->nassert) {
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_exp), w->expand.size() * sizeof(uint64_t)));
+        t.expand = d_exp;
+        SRE_HIP_TRY(hipMemcpy(d_exp, w->expand.data(), w->expand.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    t.W = W;
+    t.nlut = w->nlut;
+    t.nassert = w->nassert;
+    for (uint32_t k = 0; k < 16; k++) t.hot[k] = w->hot[k];
+    memcpy(t.init, w->init, sizeof(t.init));
+    memcpy(t.seed, w->seed, sizeof(t.seed));
+    memcpy(t.any_bits, w->any_bits, sizeof(t.any_bits));
+    memcpy(t.match_bits, w->match_bits, sizeof(t.match_bits));
+    memcpy(t.msrc, w->msrc, sizeof(t.msrc));
+    memcpy(t.valid, w->valid, sizeof(t.valid));
+    memcpy(t.self, w->self, sizeof(t.self));
+    memcpy(t.shift_src, w->shift_src, sizeof(t.shift_src));
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* A wide form of ONE word without look-ahead assertions and with at most three lookups is a 64-bit shift-and
+ * form (sre_nfa.h): masked, carried across the two halves, MATCH as event sources — it runs on the compiled
+ * sre_k_nfa_sa<W64, W64, true, true, NLUT, false> instead of the wide kernel (the 64-bit builder declined the
+ * program only because it counts threads before merging) */
+static bool
+nfa_wide_fits_sa(const sre_nfa_wide_t *w)
+{
+    return w->W == 1 && w->nassert == 0 && w->nlut <= SRE_NFA_SA_MAX_LUT;
+}
+
+static int
+nfa_wide_as_sa(sre_hip_scanner_t *sc)
+{
+    const sre_nfa_wide_t *w = sc->wnfa;
+    sre_nfa_sa_tables_t  &t = sc->satab;
+    uint64_t              acc[256];
+    for (unsigned c = 0; c < 256; c++) acc[c] = w->accept[c][0];
+    uint64_t *d_sacc = NULL, *d_lut = NULL;
+    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_sacc), sizeof(acc)));
+    t.accept = d_sacc;
+    SRE_HIP_TRY(hipMemcpy(d_sacc, acc, sizeof(acc), hipMemcpyHostToDevice));
+    if (w->nlut) {
+        /* [nlut][256][1]: the layout of the 64-bit form's lookups */
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_lut), w->lut.size() * sizeof(uint64_t)));
+        t.lut = d_lut;
+        SRE_HIP_TRY(hipMemcpy(d_lut, w->lut.data(), w->lut.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    t.w64 = w->nbits > 32;
+    t.carry = t.w64;
+    t.masked = 1;
+    t.evacc = 1;
+    t.nlut = w->nlut;
+    t.perm = 0;
+    for (uint32_t k = 0; k < w->nlut; k++) t.perm |= w->hot[k] << (8 * k);     /* hot bytes < 4 unless w64 */
+    for (int v = 0; v < 3; v++) t.init[v] = w->init[v][0];
+    t.seed = w->seed[0];
+    t.any_bits = w->any_bits[0];
+    t.match_bits = 0;
+    t.msrc = w->msrc[0];
+    t.valid = w->valid[0];
+    t.self = w->self[0];
+    t.shift_src = w->shift_src[0];
+    t.nassert = 0;
+    sc->use_sa = true;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* 64-bit words per set of the NFA tier's kernel */
+static uint32_t
+nfa_words(const sre_hip_scanner_t *sc)
+{
+    return sc->wide_kernel ? sc->wtab.W : 1u;
+}
+
 /* one pass of the set kernel the scanner's program runs on */
 static hipError_t
 nfa_launch_scan(sre_hip_scanner_t *sc, const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid,
                 hipStream_t stream)
 {
+    if (sc->wide_kernel) return sre_launch_nfa_wide_scan(sc->wtab, sc->geom, sc->d_nsum, sc->d_wsets, d_lo, d_belief, d_bvalid, stream);
     if (sc->use_sa) return sre_launch_nfa_sa_scan(sc->satab, sc->geom, sc->d_nsum, d_lo, d_belief, d_bvalid, stream);
     return sre_launch_nfa_scan(sc->mode == SRE_HIP_THOMPSON ? SRE_HIP_THOMPSON : SRE_HIP_PIKE_FIRST, sc->ntab, sc->geom,
                                sc->d_nsum, d_lo, d_belief, d_bvalid, stream);
@@ -362,6 +479,19 @@ scanner_create(sre_pool_t *pool, sre_program_t *prog, int mode, int engine, int 
          * bit-parallel form, if the program has one */
         const char *why = NULL;
         sc->nfa = sre_nfa_build(prog, &why);
+        if (sc->nfa == NULL && why != NULL && strncmp(why, "more than 64", 12) == 0) {
+            /* declined for width alone: the wide form counts its bits after merging (sre_nfa_wide.h) */
+            const char *e = getenv("SRE_HIP_NFA_WIDE");     /* build options (tests) */
+            sc->wnfa = sre_nfa_wide_build(prog, e ? (unsigned) strtoul(e, NULL, 0) : 0u, &why);
+            if (sc->wnfa && mode == SRE_HIP_PIKE_COUNT
+                && (sc->wnfa->nassert || memcmp(sc->wnfa->init[1], sc->wnfa->init[2], sizeof(sc->wnfa->init[1])) != 0)) {
+                /* the 64-bit tier's find-all restrictions (below) */
+                why = sc->wnfa->nassert ? "find-all counting of a look-ahead program the step automaton declines"
+                                        : "find-all counting of a program whose initial closure depends on ^ (re-armed searches skip newlines)";
+                sre_nfa_wide_free(sc->wnfa);
+                sc->wnfa = NULL;
+            }
+        }
         if (sc->nfa && mode == SRE_HIP_PIKE_COUNT && (sc->nfa->nassert || sc->nfa->init[1] != sc->nfa->init[2])) {
             /* Find-all on this tier restarts searches in the middle of the stream.  A re-armed search
              * that does not start behind a newline holds the bare ".*?" list as its initial-state
@@ -376,7 +506,9 @@ scanner_create(sre_pool_t *pool, sre_program_t *prog, int mode, int engine, int 
             sre_nfa_free(sc->nfa);
             sc->nfa = NULL;
         }
-        if (sc->nfa && nfa_upload(sc) == 0) {
+        if (sc->wnfa) sc->wide_kernel = !nfa_wide_fits_sa(sc->wnfa);
+        if ((sc->nfa && nfa_upload(sc) == 0)
+            || (sc->wnfa && (sc->wide_kernel ? nfa_wide_upload(sc) : nfa_wide_as_sa(sc)) == 0)) {
             sc->engine = SRE_HIP_ENGINE_NFA;
             if (mode == SRE_HIP_PIKE_COUNT) sc->cnt = new NfaCount();
             if (mode != SRE_HIP_THOMPSON && getenv("SRE_HIP_NO_PWAVE") == NULL) {
@@ -462,6 +594,13 @@ sre_hip_scanner_last_exact_passes(sre_hip_scanner_t *sc)
 }
 
 extern "C" SRE_API int
+sre_hip_scanner_nfa_bits(sre_hip_scanner_t *sc)
+{
+    if (sc->engine != SRE_HIP_ENGINE_NFA) return 0;
+    return 64 * (int) nfa_words(sc);
+}
+
+extern "C" SRE_API int
 sre_hip_scanner_class_bits(sre_hip_scanner_t *sc)
 {
     return sc->engine == SRE_HIP_ENGINE_SCAN ? (int) sc->tab->h.class_bits : 0;
@@ -477,7 +616,8 @@ sre_hip_scanner_kernel_name(sre_hip_scanner_t *sc)
                      sc->tab->h.wide ? "true" : "false",
                      sc->mode == SRE_HIP_PIKE_COUNT && sc->tab->h.any_fresh ? "true" : "false");
         } else if (sc->engine == SRE_HIP_ENGINE_NFA) {
-            if (sc->use_sa) sre_nfa_sa_kernel_name(&sc->satab, sc->kernel_name, sizeof(sc->kernel_name));
+            if (sc->wide_kernel) sre_nfa_wide_kernel_name(&sc->wtab, sc->kernel_name, sizeof(sc->kernel_name));
+            else if (sc->use_sa) sre_nfa_sa_kernel_name(&sc->satab, sc->kernel_name, sizeof(sc->kernel_name));
             else sre_nfa_kernel_name(sc->mode == SRE_HIP_THOMPSON ? 0 : 1, sc->ntab.nslices, sc->ntab.nassert != 0,
                                      sc->kernel_name, sizeof(sc->kernel_name));
         } else {
@@ -618,7 +758,8 @@ scan_resident(sre_hip_scanner_t *sc)
 {
     if (sc->blocks_per_cu == 0) {
         sc->blocks_per_cu = sc->engine == SRE_HIP_ENGINE_NFA
-                                ? (sc->use_sa ? sre_nfa_sa_blocks_per_cu(&sc->satab)
+                                ? (sc->wide_kernel ? sre_nfa_wide_blocks_per_cu(&sc->wtab)
+                                   : sc->use_sa ? sre_nfa_sa_blocks_per_cu(&sc->satab)
                                               : sre_nfa_blocks_per_cu(sc->mode == SRE_HIP_THOMPSON ? 0 : 1, sc->ntab.nslices,
                                                                       sc->ntab.nassert != 0))
                                                              : sre_scan_blocks_per_cu(&sc->tab->h);
@@ -684,12 +825,15 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
             if (sc->d_nsum) (void) hipFree(sc->d_nsum);
             if (sc->d_belief) (void) hipFree(sc->d_belief);
             if (sc->d_bvalid) (void) hipFree(sc->d_bvalid);
+            if (sc->d_wsets) (void) hipFree(sc->d_wsets);
             sc->d_nsum = NULL;
             sc->d_belief = NULL;
             sc->d_bvalid = NULL;
+            sc->d_wsets = NULL;
             sc->nsum_cap = 0;
             SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nsum), nsegs * sizeof(sre_nfa_summary_t)));
-            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_belief), nsegs * sizeof(uint64_t)));
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_belief), nsegs * nfa_words(sc) * sizeof(uint64_t)));
+            if (sc->wide_kernel) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_wsets), nsegs * 2 * nfa_words(sc) * sizeof(uint64_t)));
             SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_bvalid), nsegs));
             sc->nsum_cap = nsegs;
         }
@@ -745,8 +889,13 @@ nfa_finish(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
     const uint32_t n = sc->geom.nstreams;
     /* (the kernels know two modes: find-all counting is a loop of first-match searches) */
     const int kmode = sc->mode == SRE_HIP_THOMPSON ? SRE_HIP_THOMPSON : SRE_HIP_PIKE_FIRST;
-    SRE_HIP_TRY(sre_launch_nfa_verify(kmode, sc->geom, sc->d_nsum, sc->d_nacc, sc->d_nstatus,
-                                      sc->d_belief, sc->d_bvalid, sc->d_records, sc->ovec_slots, d_lo, stream));
+    if (sc->wide_kernel) {
+        SRE_HIP_TRY(sre_launch_nfa_wide_verify(kmode, sc->wtab.W, sc->geom, sc->d_nsum, sc->d_wsets, sc->d_nacc, sc->d_nstatus,
+                                               sc->d_belief, sc->d_bvalid, sc->d_records, sc->ovec_slots, d_lo, stream));
+    } else {
+        SRE_HIP_TRY(sre_launch_nfa_verify(kmode, sc->geom, sc->d_nsum, sc->d_nacc, sc->d_nstatus,
+                                          sc->d_belief, sc->d_bvalid, sc->d_records, sc->ovec_slots, d_lo, stream));
+    }
     if (sc->mode != SRE_HIP_THOMPSON) {
         if (sc->d_pwave) {
             SRE_HIP_TRY(sre_launch_pike_window_wave(sc->d_pwave, sc->h_pwave, sc->d_ptrs, sc->d_lens, n, sc->d_records,
@@ -838,16 +987,40 @@ nfa_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool *psettled)
             && getenv("SRE_HIP_NO_NFA_EXACT") == NULL) {
             /* speculation does not settle this batch (a program that never forgets): every remaining lane's
              * exact entry set from the segments' singleton exit sets — the pass below is then exact */
-            if (sc->geom.nsegs > sc->nmat_cap) {
-                if (sc->d_nmat) (void) hipFree(sc->d_nmat);
-                sc->d_nmat = NULL;
-                sc->nmat_cap = 0;
-                SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), sc->geom.nsegs * 64 * sizeof(uint64_t)));
-                sc->nmat_cap = sc->geom.nsegs;
+            if (sc->wide_kernel) {
+                /* the wide matrix: 64W x W words a segment (8 KiB at 256 bits).  It takes at most half of the
+                 * device memory that is free; when it cannot be had, speculation goes on (slower, never wrong) */
+                const size_t need = sre_nfa_wide_matrix_bytes(sc->wtab.W, sc->geom.nsegs);
+                if (need > sc->nmat_cap * 64 * sizeof(uint64_t)) {
+                    if (sc->d_nmat) (void) hipFree(sc->d_nmat);
+                    sc->d_nmat = NULL;
+                    sc->nmat_cap = 0;
+                    size_t free_b = 0, total_b = 0;
+                    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2
+                        && hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), need) == hipSuccess) {
+                        sc->nmat_cap = need / (64 * sizeof(uint64_t));
+                    } else {
+                        (void) hipGetLastError();
+                        sc->d_nmat = NULL;
+                    }
+                }
+                if (sc->d_nmat) {
+                    SRE_HIP_TRY(sre_launch_nfa_wide_exact_entries(sc->wtab, sc->geom, sc->d_nsum, sc->d_wsets, sc->d_lo, sc->d_nmat,
+                                                                  sc->d_belief, sc->d_bvalid, stream));
+                    sc->exact_passes++;
+                }
+            } else {
+                if (sc->geom.nsegs > sc->nmat_cap) {
+                    if (sc->d_nmat) (void) hipFree(sc->d_nmat);
+                    sc->d_nmat = NULL;
+                    sc->nmat_cap = 0;
+                    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), sc->geom.nsegs * 64 * sizeof(uint64_t)));
+                    sc->nmat_cap = sc->geom.nsegs;
+                }
+                SRE_HIP_TRY(sre_launch_nfa_exact_entries(sc->use_sa ? 1 : 0, sc->ntab, sc->satab, sc->geom, sc->d_nsum, sc->d_lo,
+                                                         sc->d_nmat, sc->d_belief, sc->d_bvalid, stream));
+                sc->exact_passes++;
             }
-            SRE_HIP_TRY(sre_launch_nfa_exact_entries(sc->use_sa ? 1 : 0, sc->ntab, sc->satab, sc->geom, sc->d_nsum, sc->d_lo,
-                                                     sc->d_nmat, sc->d_belief, sc->d_bvalid, stream));
-            sc->exact_passes++;
         }
         SRE_HIP_TRY(nfa_launch_scan(sc, sc->d_lo, sc->d_belief, sc->d_bvalid, stream));
         if (nfa_finish(sc, sc->d_lo, stream) != 0) return -1;

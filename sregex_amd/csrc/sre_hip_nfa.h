@@ -88,6 +88,12 @@ hipError_t sre_nfa_verify_acc_init(void *d_acc, uint32_t nstreams, hipStream_t s
 hipError_t sre_launch_nfa_verify(int mode, sre_scan_geom_t geom, const sre_nfa_summary_t *d_sum,
     void *d_acc, sre_nfa_status_t *d_status, uint64_t *d_belief, uint8_t *d_bvalid,
     int64_t *d_records, uint32_t ovec_slots, const int64_t *d_lo, hipStream_t stream);
+/* the same without its first kernel (the per-segment set comparison): the wide tier's chain check
+ * (sre_hip_nfa_wide.h) compares its own sets into the same accumulators, then runs this */
+hipError_t sre_launch_nfa_verify_tail(int mode, sre_scan_geom_t geom, const sre_nfa_summary_t *d_sum, void *d_acc,
+    sre_nfa_status_t *d_status, int64_t *d_records, uint32_t ovec_slots, const int64_t *d_lo, hipStream_t stream);
+/* the per-stream accumulator of the chain check: {bad, end, clean} (sre_hip_nfa.hip) */
+typedef struct { unsigned long long bad, end, clean; } sre_nfa_acc_t;
 #ifdef __cplusplus
 }
 #endif

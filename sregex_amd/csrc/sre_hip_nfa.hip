@@ -1142,6 +1142,18 @@ sre_launch_nfa_verify(int mode, sre_scan_geom_t geom, const sre_nfa_summary_t *d
     NfaAcc        *acc = static_cast<NfaAcc *>(d_acc);
     const uint32_t gseg = (uint32_t) ((geom.nsegs + 255) / 256);
     hipLaunchKernelGGL(sre_k_nfa_verify_a, dim3(gseg), dim3(256), 0, stream, geom, d_sum, acc, d_belief, d_bvalid);
+    return sre_launch_nfa_verify_tail(mode, geom, d_sum, d_acc, d_status, d_records, ovec_slots, d_lo, stream);
+}
+
+/* the chain check behind its first kernel (the wide tier, sre_hip_nfa_wide.hip, compares W-word sets in
+ * its own first kernel, into the same accumulators): clean positions, status words, records */
+extern "C" hipError_t
+sre_launch_nfa_verify_tail(int mode, sre_scan_geom_t geom, const sre_nfa_summary_t *d_sum, void *d_acc,
+                           sre_nfa_status_t *d_status, int64_t *d_records, uint32_t ovec_slots, const int64_t *d_lo,
+                           hipStream_t stream)
+{
+    if (geom.nstreams == 0) return hipSuccess;
+    NfaAcc *acc = static_cast<NfaAcc *>(d_acc);
     hipLaunchKernelGGL(sre_k_nfa_verify_b, dim3((uint32_t) ((geom.nsegs + 1023) / 1024)), dim3(256), 0, stream,
                        geom, d_sum, acc);
     hipLaunchKernelGGL(sre_k_nfa_verify_c, dim3((geom.nstreams + 63) / 64), dim3(64), 0, stream, mode, geom,
