@@ -227,6 +227,76 @@ SRE_API int sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t 
  * first call) */
 SRE_API int sre_hip_scanner_last_line_batches(sre_hip_scanner_t *sc);
 
+/* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
+
+typedef struct sre_hip_streams_s sre_hip_streams_t;
+
+/*
+ * A stream set: nstreams independent streams of one compiled program, each the equivalent of
+ * one reference context (sre_vm_pike_create_ctx, sre_vm_pike.c:94-145, resp.
+ * sre_vm_thompson_create_ctx) whose state — the ordered thread list as an automaton state, one
+ * capture vector per listed thread, the pending match, processed_bytes, seen_newline /
+ * seen_word — lives on the device between calls.  mode: SRE_HIP_PIKE_FIRST or SRE_HIP_THOMPSON.
+ * Owned by `pool`.
+ *
+ * Returns NULL (with a diagnostic on stderr) when the program's chunks cannot run on the
+ * table-driven scanner: a program the step automaton declines (the NFA tier's and the exact
+ * VM's programs), one with more than 64 listed threads or 64 capture slots, or a Thompson
+ * program with look-ahead assertions (that VM's \A ^ \b are local to a call's buffer).  Pike
+ * programs with look-ahead assertions are admitted.
+ *
+ * Scope: ONE search per stream.  A stream is closed by its first final answer (a match,
+ * SRE_DECLINED, SRE_ERROR) and stays closed until sre_hip_streams_reset gives its slot a fresh
+ * context.  Re-arming a context inside the chunk that held the match (the find-all iteration
+ * of sre_vm_pike.c:179-196, 624-628) and SRE_HIP_PIKE_COUNT over chunks are not offered.
+ */
+SRE_API sre_hip_streams_t *sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog,
+    int mode, size_t nstreams);
+
+SRE_API size_t sre_hip_streams_count(sre_hip_streams_t *ss);
+
+/* sre_int_t per record: 5 + 2 * (max_ncaps + 1) */
+SRE_API size_t sre_hip_streams_result_slots(sre_hip_streams_t *ss);
+
+/* HBM the set holds for its contexts: nstreams rows of 8 * (4 + nslots * (1 + 2 * max_threads))
+ * bytes, nslots and max_threads being the program's capture slots and longest thread list
+ * (Thompson: 32 bytes a stream) */
+SRE_API size_t sre_hip_streams_device_bytes(sre_hip_streams_t *ss);
+
+/*
+ * One exec() per stream.  d_chunks, lens and eof are HOST arrays of nstreams entries:
+ * d_chunks[i] is a DEVICE pointer to lens[i] bytes at any alignment, eof[i] != 0 marks stream
+ * i's last chunk.  d_chunks[i] == NULL: stream i is not fed in this call.  lens[i] == 0 with a
+ * non-NULL pointer IS a call (the reference answers SRE_AGAIN, or takes its EOF step with eof).
+ * Synchronous; all work on hip_stream.  The number of kernel launches, copies and waits of a
+ * call does not depend on nstreams (fix-up rounds aside).  0 on success, -1 on failure.
+ *
+ * results: nstreams records of sre_hip_streams_result_slots() sre_int_t each:
+ *   [0] rc      what sre_vm_pike_exec(ctx_i, chunk, len, eof, &pending) (resp.
+ *               sre_vm_thompson_exec) returns for this call after the same earlier calls:
+ *               regex id (SRE_OK for Thompson), SRE_AGAIN, SRE_DECLINED, SRE_ERROR
+ *   [1] state   0 open (more chunks welcome); 1 closed by this call (rc is final); 2 was
+ *               closed before this call (the chunk was ignored and not read; [0] and [2..]
+ *               repeat the closing record); 3 not fed in this call (rest of the record
+ *               undefined)
+ *   [2..4]      has_pending, pending[0], pending[1]: the reference's *pending_matched after
+ *               SRE_AGAIN (sre_vm_pike.c:640-688); 0, -1, -1 otherwise
+ *   [5..]       ovector, 2 * (max_ncaps + 1) slots, ABSOLUTE stream offsets, -1 unset.  On a
+ *               match: the captures (:945-989).  On SRE_AGAIN: [5] and [6] are the temporary
+ *               match range of prepare_temp_captures (:692-735), the others -1.
+ */
+SRE_API int sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks,
+    const size_t *lens, const unsigned char *eof, sre_int_t *results, void *hip_stream);
+
+/* give streams idx[0..n) fresh contexts (a new flow takes over the slot).  Synchronous. */
+SRE_API int sre_hip_streams_reset(sre_hip_streams_t *ss, const size_t *idx, size_t n);
+
+/* diagnostics: fix-up rounds of the last feed (as sre_hip_scanner_last_fixups) */
+SRE_API int sre_hip_streams_last_fixups(sre_hip_streams_t *ss);
+
+/* diagnostics: kernels and copies the last feed queued (fix-up rounds: the batches of rounds) */
+SRE_API int sre_hip_streams_last_launches(sre_hip_streams_t *ss);
+
 /* ---- helpers for drivers that have no HIP runtime binding of their own ---- */
 
 /* device buffer management (hipMalloc / hipFree / hipMemcpy) */

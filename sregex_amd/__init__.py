@@ -78,6 +78,15 @@ API = {
     "sre_hip_scan_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _pssz, _sz,
                                           ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
+    "sre_hip_streams_create": (_vp, [_vp, _vp, ctypes.c_int, _sz]),
+    "sre_hip_streams_count": (_sz, [_vp]),
+    "sre_hip_streams_result_slots": (_sz, [_vp]),
+    "sre_hip_streams_device_bytes": (_sz, [_vp]),
+    "sre_hip_streams_feed": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+                                            ctypes.POINTER(ctypes.c_ubyte), _pssz, _vp]),
+    "sre_hip_streams_reset": (ctypes.c_int, [_vp, ctypes.POINTER(_sz), _sz]),
+    "sre_hip_streams_last_fixups": (ctypes.c_int, [_vp]),
+    "sre_hip_streams_last_launches": (ctypes.c_int, [_vp]),
     "sre_hip_alloc": (_vp, [_sz]),
     "sre_hip_free": (None, [_vp]),
     "sre_hip_upload": (ctypes.c_int, [_vp, _vp, _sz]),
@@ -391,6 +400,57 @@ class Scanner:
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
+
+
+class StreamSet:
+    """sre_hip_streams_* (include/sregex_hip.h): n streams of one program whose contexts live on
+    the device and are fed chunk by chunk, all together in one call."""
+
+    OPEN, CLOSED, WAS_CLOSED, NOT_FED = 0, 1, 2, 3
+
+    def __init__(self, pool, prog, mode, nstreams):
+        self.lib = pool.lib
+        self.h = self.lib.sre_hip_streams_create(pool.p, prog.h, mode, nstreams)
+        if not self.h:
+            raise RuntimeError("sre_hip_streams_create failed (no HIP device, or the program's chunks "
+                               "do not run on the table-driven scanner)")
+        self.n = self.lib.sre_hip_streams_count(self.h)
+        self.slots = self.lib.sre_hip_streams_result_slots(self.h)
+        self._out = (ctypes.c_ssize_t * (self.n * self.slots))()
+
+    def feed_raw(self, ptrs, lens, eof, hip_stream=None):
+        """one call with ctypes arrays of n entries; returns the flat ctypes array of records"""
+        if self.lib.sre_hip_streams_feed(self.h, ptrs, lens, eof, self._out, hip_stream) != 0:
+            raise RuntimeError("sre_hip_streams_feed failed")
+        return self._out
+
+    def feed(self, ptrs, lens, eof, hip_stream=None):
+        """ptrs[i]: device pointer of stream i's chunk, or None (not fed in this call); returns one
+        record [rc, state, has_pending, pending0, pending1, ovector...] per stream"""
+        n = self.n
+        if not (len(ptrs) == len(lens) == len(eof) == n):
+            raise ValueError("a stream set of %d streams takes %d pointers, lengths and eof flags" % (n, n))
+        out = self.feed_raw((_vp * n)(*ptrs), (_sz * n)(*lens), (ctypes.c_ubyte * n)(*[1 if e else 0 for e in eof]),
+                            hip_stream)
+        s = self.slots
+        return [list(out[i * s:(i + 1) * s]) for i in range(n)]
+
+    def reset(self, idx):
+        idx = list(idx)
+        if self.lib.sre_hip_streams_reset(self.h, (_sz * max(len(idx), 1))(*idx), len(idx)) != 0:
+            raise RuntimeError("sre_hip_streams_reset failed")
+
+    @property
+    def device_bytes(self):
+        return self.lib.sre_hip_streams_device_bytes(self.h)
+
+    @property
+    def last_fixups(self):
+        return self.lib.sre_hip_streams_last_fixups(self.h)
+
+    @property
+    def last_launches(self):
+        return self.lib.sre_hip_streams_last_launches(self.h)
 
 
 class DeviceBuffer:

@@ -20,6 +20,7 @@
 #include "sre_hip_nfa_wide.h"
 #include "sre_pwave.h"
 #include "sre_hip_lines.h"
+#include "sre_hip_streams.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1819,6 +1820,247 @@ sre_hip_scanner_streams(sre_hip_scanner_t *sc)
     if (sc->mode == SRE_HIP_THOMPSON) return 1;         /* the state alone */
     return sc->mode == SRE_HIP_PIKE_FIRST && sc->tab->h.max_threads <= SRE_STREAM_MAX_THREADS
            && sc->tab->h.nslots <= SRE_STREAM_MAX_SLOTS;
+}
+
+/* ---- stream sets (sre_hip_streams_*) ---- */
+
+struct sre_hip_streams_s {
+    sre_hip_scanner_t    *sc;           /* the set's own scanner: tables, per-call buffers, fix-up rounds */
+    size_t                n;
+    sre_streams_layout_t  L;
+    int64_t              *d_rows;       /* n context rows */
+    size_t                rows_bytes;
+    uint8_t              *d_rekind;     /* [nstates][4], NULL: a chunk boundary leaves every state as it is */
+    sre_streams_feed_t   *d_feed, *h_feed;      /* what a call hands in: three words a stream (h_: pinned) */
+    uint32_t             *d_sentry;
+    unsigned char        *d_out, *h_out;        /* [sre_streams_info_t][n records] */
+    sre_stream_result_t  *d_tailres;    /* one per workgroup of the tail kernel */
+    uint64_t             *d_idx;        /* sre_hip_streams_reset */
+    size_t                idx_cap;
+    int                   fixups, launches;
+};
+
+static void
+streams_release(void *data)
+{
+    sre_hip_streams_t *ss = static_cast<sre_hip_streams_t *>(data);
+    if (ss->d_rows) (void) hipFree(ss->d_rows);
+    if (ss->d_rekind) (void) hipFree(ss->d_rekind);
+    if (ss->d_feed) (void) hipFree(ss->d_feed);
+    if (ss->h_feed) (void) hipHostFree(ss->h_feed);
+    if (ss->d_sentry) (void) hipFree(ss->d_sentry);
+    if (ss->d_out) (void) hipFree(ss->d_out);
+    if (ss->h_out) (void) hipHostFree(ss->h_out);
+    if (ss->d_tailres) (void) hipFree(ss->d_tailres);
+    if (ss->d_idx) (void) hipFree(ss->d_idx);
+    free(ss);
+}
+
+extern "C" SRE_API sre_hip_streams_t *
+sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog, int mode, size_t nstreams)
+{
+    if (pool == NULL || prog == NULL || nstreams == 0 || nstreams > (size_t) 1 << 30) return NULL;
+    if (mode != SRE_HIP_THOMPSON && mode != SRE_HIP_PIKE_FIRST) {
+        fprintf(stderr, "[sregex-hip] stream set: mode must be SRE_HIP_THOMPSON or SRE_HIP_PIKE_FIRST\n");
+        return NULL;
+    }
+    if (sre_hip_ready() != 0) return NULL;
+    if (mode == SRE_HIP_THOMPSON && prog->lookahead_asserts) {
+        /* (sre_vm_api.cpp thompson_stream_route: \A, ^ and \b are local to a call's buffer in that VM) */
+        fprintf(stderr, "[sregex-hip] stream set: a Thompson program with look-ahead assertions has no chunked scanner\n");
+        return NULL;
+    }
+    /* as the compat path's chunk route: look-ahead programs on the automaton with chunk-boundary twins */
+    sre_hip_scanner_t *sc = scanner_create(pool, prog, mode, SRE_HIP_ENGINE_SCAN, prog->lookahead_asserts ? 1 : 0);
+    if (sc == NULL) return NULL;
+    if (!sre_hip_scanner_streams(sc)) {
+        fprintf(stderr, "[sregex-hip] stream set: more than %u listed threads or capture slots\n", SRE_STREAM_MAX_THREADS);
+        return NULL;
+    }
+    sre_hip_streams_t *ss = static_cast<sre_hip_streams_t *>(calloc(1, sizeof(*ss)));
+    if (ss == NULL) return NULL;
+    ss->sc = sc;
+    ss->n = nstreams;
+    ss->L.nslots = mode == SRE_HIP_THOMPSON ? 0 : sc->tab->h.nslots;
+    ss->L.max_threads = mode == SRE_HIP_THOMPSON ? 0 : sc->tab->h.max_threads;
+    ss->L.row_words = SRE_SROW_HDR + ss->L.nslots * (1 + 2 * ss->L.max_threads);
+    ss->L.ovec_slots = sc->ovec_slots;
+    ss->L.rec_slots = SRE_SREC_HDR + sc->ovec_slots;
+    ss->rows_bytes = nstreams * ss->L.row_words * sizeof(int64_t);
+    {
+        const size_t out_bytes = sizeof(sre_streams_info_t) + nstreams * ss->L.rec_slots * sizeof(int64_t);
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_rows), ss->rows_bytes));
+        SRE_HIP_TRY(hipMemset(ss->d_rows, 0, ss->rows_bytes));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_feed), nstreams * sizeof(sre_streams_feed_t)));
+        SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ss->h_feed), nstreams * sizeof(sre_streams_feed_t), 0));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_sentry), nstreams * sizeof(uint32_t)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_out), out_bytes));
+        SRE_HIP_TRY(hipMemset(ss->d_out, 0, out_bytes));
+        SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ss->h_out), out_bytes, 0));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_tailres), SRE_STREAMS_TAIL_GRID * sizeof(sre_stream_result_t)));
+        if (sc->d_linfo == NULL) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_linfo), sizeof(sre_lines_info_t)));
+        if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
+        if (!sc->dfa->rekind.empty()) {
+            std::vector<uint8_t> rk(sc->dfa->rekind.size());
+            for (size_t i = 0; i < rk.size(); i++) rk[i] = (uint8_t) sc->dfa->rekind[i];
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_rekind), rk.size()));
+            SRE_HIP_TRY(hipMemcpy(ss->d_rekind, rk.data(), rk.size(), hipMemcpyHostToDevice));
+        }
+    }
+    if (sre_pool_add_cleanup(pool, streams_release, ss) != SRE_OK) goto hip_failed;
+    return ss;
+hip_failed:
+    streams_release(ss);
+    return NULL;
+}
+
+extern "C" SRE_API size_t
+sre_hip_streams_count(sre_hip_streams_t *ss)
+{
+    return ss->n;
+}
+
+extern "C" SRE_API size_t
+sre_hip_streams_result_slots(sre_hip_streams_t *ss)
+{
+    return ss->L.rec_slots;
+}
+
+extern "C" SRE_API size_t
+sre_hip_streams_device_bytes(sre_hip_streams_t *ss)
+{
+    return ss->rows_bytes;
+}
+
+extern "C" SRE_API int
+sre_hip_streams_last_fixups(sre_hip_streams_t *ss)
+{
+    return ss->fixups;
+}
+
+extern "C" SRE_API int
+sre_hip_streams_last_launches(sre_hip_streams_t *ss)
+{
+    return ss->launches;
+}
+
+extern "C" SRE_API int
+sre_hip_streams_reset(sre_hip_streams_t *ss, const size_t *idx, size_t n)
+{
+    if (ss == NULL || (n != 0 && idx == NULL)) return -1;
+    if (n == 0) return 0;
+    for (size_t i = 0; i < n; i++) {
+        if (idx[i] >= ss->n) return -1;
+    }
+    if (lines_grow(&ss->d_idx, &ss->idx_cap, n * sizeof(uint64_t)) != 0) return -1;
+    {
+        std::vector<uint64_t> h(idx, idx + n);
+        SRE_HIP_TRY(hipMemcpy(ss->d_idx, h.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
+    SRE_HIP_TRY(sre_launch_streams_reset(ss->d_rows, ss->L.row_words, ss->d_idx, n, NULL));
+    SRE_HIP_TRY(hipStreamSynchronize(NULL));
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* One exec() per fed stream.  The host fills three words a stream; everything else of the call —
+ * which streams take part, the geometry, the entry states, the tails, the records — happens on
+ * the device in a number of launches and copies that does not depend on the size of the set. */
+extern "C" SRE_API int
+sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const size_t *lens,
+    const unsigned char *eof, sre_int_t *results, void *hip_stream)
+{
+    if (ss == NULL || d_chunks == NULL || lens == NULL || eof == NULL || results == NULL) return -1;
+    hipStream_t         stream = static_cast<hipStream_t>(hip_stream);
+    sre_hip_scanner_t  *sc = ss->sc;
+    const size_t        n = ss->n;
+    sre_streams_info_t *d_info = reinterpret_cast<sre_streams_info_t *>(ss->d_out);
+    const volatile sre_streams_info_t *h_info = reinterpret_cast<sre_streams_info_t *>(ss->h_out);
+    int64_t            *d_recs = reinterpret_cast<int64_t *>(ss->d_out + sizeof(sre_streams_info_t));
+    const size_t        out_bytes = sizeof(sre_streams_info_t) + n * ss->L.rec_slots * sizeof(int64_t);
+    ss->fixups = 0;
+    ss->launches = 0;
+    sc->last_lines = false;
+    sc->last_n = 0;
+    sc->fixup_rounds = 0;
+    sc->exact_passes = 0;
+    sc->lineage_passes = 0;
+    sc->ev_valid = 0;
+    for (size_t i = 0; i < n; i++) {
+        ss->h_feed[i].ptr = (uint64_t) reinterpret_cast<uintptr_t>(d_chunks[i]);
+        ss->h_feed[i].len = d_chunks[i] ? lens[i] : 0;
+        ss->h_feed[i].flags = d_chunks[i] ? (SRE_SFEED_FED | (eof[i] ? SRE_SFEED_EOF : 0u)) : 0u;
+    }
+    if (scanner_reserve(sc, n) != 0) return -1;
+    {
+        const uint64_t seg_fixed = scan_seg_knobs(sc);
+        const uint64_t resident = scan_resident(sc);
+        SRE_HIP_TRY(sre_launch_upload_words(reinterpret_cast<const uint64_t *>(ss->h_feed),
+                                            reinterpret_cast<uint64_t *>(ss->d_feed), (uint32_t) (3 * n), stream));
+        SRE_HIP_TRY(sre_launch_streams_prologue(ss->d_feed, (uint32_t) n, ss->d_rows, ss->L, ss->d_rekind, sc->tab->h.init[0],
+                                                seg_fixed, resident, sc->seg_cap_env ? sc->seg_cap_env : 40960,
+                                                reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens, sc->d_seg_first,
+                                                ss->d_sentry, d_recs, d_info, stream));
+        /* the host sizes the call's buffers and grids from two of its words */
+        SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, sizeof(sre_streams_info_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        ss->launches += 3;
+    }
+    if (h_info->nsegs != 0) {
+        const uint64_t seg = h_info->seg, nsegs = h_info->nsegs, nact = h_info->nactive;
+        const uint32_t grid = (uint32_t) (nact < SRE_STREAMS_TAIL_GRID ? nact : SRE_STREAMS_TAIL_GRID);
+        /* (the walker's scratch: one block per workgroup of the tail kernel, not per stream) */
+        if (scan_buffers(sc, grid, seg, nsegs) != 0) return -1;
+        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
+        sc->geom.lens = sc->d_lens;
+        sc->geom.seg_first = sc->d_seg_first;
+        sc->geom.nstreams = (uint32_t) n;
+        sc->geom.seg_bytes = (uint32_t) seg;
+        sc->geom.nsegs = nsegs;
+        sc->geom.init_variant = 0;
+        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
+        sc->geom.entry_state = 0;
+        sc->geom.one_ptr = NULL;
+        sc->geom.one_len = 0;
+        sc->geom.digest = NULL;
+        sc->geom.sentry = ss->d_sentry;
+        sc->geom_one = 0;
+        SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));
+        SRE_HIP_TRY(sre_launch_verify(sc->tab->h, sc->geom, sc->d_sum, sc->d_acc, sc->d_status, stream));
+        SRE_HIP_TRY(sre_launch_streams_tail(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status, sc->d_scratch,
+                                            ss->d_rows, ss->L, ss->d_tailres, d_recs, d_info, grid, 0, stream));
+        ss->launches += 1 + (sc->mode == SRE_HIP_PIKE_FIRST && sc->tab->h.nshadow ? 4 : 3) + 1;
+    }
+    SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    ss->launches += 1;
+    if (h_info->unsettled != 0) {
+        /* speculative entry states of some stream's lanes were wrong: the fix-up rounds over the
+         * streams that are not done, driven from device counters, then their tails */
+        const uint64_t nact = h_info->nactive;
+        const uint32_t grid = (uint32_t) (nact < SRE_STREAMS_TAIL_GRID ? nact : SRE_STREAMS_TAIL_GRID);
+        sc->h_linfo->pending = h_info->unsettled;
+        sc->h_linfo->maps = 0;
+        if (scan_settle(sc, n, stream, false, NULL, true) != 0) goto hip_failed;
+        SRE_HIP_TRY(hipMemsetAsync(&d_info->unsettled, 0, sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_streams_tail(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status, sc->d_scratch,
+                                            ss->d_rows, ss->L, ss->d_tailres, d_recs, d_info, grid, 1, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        ss->fixups = sc->fixup_rounds;
+        ss->launches += 3;
+        if (h_info->unsettled != 0) {
+            fprintf(stderr, "[sregex-hip] stream set: %llu streams did not settle\n", (unsigned long long) h_info->unsettled);
+            goto hip_failed;
+        }
+    }
+    sc->geom.sentry = NULL;
+    memcpy(results, ss->h_out + sizeof(sre_streams_info_t), n * ss->L.rec_slots * sizeof(int64_t));
+    return 0;
+hip_failed:
+    sc->geom.sentry = NULL;
+    return -1;
 }
 
 /* ------------------------------------------------------------------ helpers */

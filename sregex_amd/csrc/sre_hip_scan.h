@@ -247,7 +247,16 @@ typedef struct {
      * (sre_seg_digest_t; NULL: none is written).  One workgroup checks up to 8192 segments: out of the
      * 144-byte summaries that was 14 us for the 4096 segments of a 1 MiB chunk. */
     struct sre_seg_digest_s *digest;
+    /* stream sets (sre_hip_streams.hip): per stream, instead of entry_state / init_variant and the
+     * SRE_GEOM_CONTINUES / SRE_GEOM_NO_EOF bits — SRE_SENTRY_*: the automaton state in front of the
+     * stream's offset 0, whether its search began in an earlier call, whether more chunks follow.
+     * Read where a lane enters a stream's first segment and at its last.  NULL: the fields above
+     * hold for every stream. */
+    const uint32_t *sentry;
 } sre_scan_geom_t;
+#define SRE_SENTRY_STATE(e)   ((e) & 0xffffu)
+#define SRE_SENTRY_CONTINUES  0x40000000u
+#define SRE_SENTRY_NO_EOF     0x80000000u
 #define SRE_SFLAG_INIT(f)    ((f) & 3u)
 #define SRE_SFLAG_SNAP(f)    (((f) >> 2) & 3u)
 #define SRE_SFLAG_MODE(f)    (((f) >> 4) & 1u)

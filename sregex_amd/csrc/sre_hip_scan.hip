@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include "sre_hip_scan.h"
+#include "sre_hip_streams.h"
 #include "sre_hip_tile.h"
 
 #define SRE_HIP_PIKE_COUNT 2
@@ -216,6 +217,7 @@ enum : uint32_t {
     F_SHADOW = 256u,    /* FIRST: the lane is inside a stable stretch (in a shadow row of the fast table) */
     F_PEND_LAZY = 512u, /* COUNT: the last fast span ended in a FRESH state: a match is pending whose event was not
                            recorded — it ends with that span's last byte (settle() replays the span) */
+    F_NO_EOF = 2048u,   /* the stream's own "more chunks follow" (sre_scan_geom_t.sentry) */
     F_LZ_GROUP = 1024u  /* ... and that span was a 16-byte group, not a 64-byte round */
 };
 
@@ -736,11 +738,13 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
         const uint64_t nseg = geom_first(G, sidx + 1) - geom_first(G, sidx);
         last_seg = (k + 1 == nseg);
         if (seg_b > w.n) seg_b = w.n;
+        if (last_seg && G.sentry != nullptr && (G.sentry[sidx] & SRE_SENTRY_NO_EOF)) w.fl |= F_NO_EOF;
 
         if (k == 0) {
             /* a chunk of a stream whose search is already under way enters with the
              * state the previous chunk ended in (sre_k_stream_tail) */
-            w.st = (G.flags & SRE_GEOM_CONTINUES) ? G.entry_state : T.init[G.init_variant];
+            w.st = G.sentry != nullptr ? SRE_SENTRY_STATE(G.sentry[sidx])
+                   : (G.flags & SRE_GEOM_CONTINUES) ? G.entry_state : T.init[G.init_variant];
             w.cur_sp = 0;
         } else if (lo_s >= 0 && (int64_t) k == lo_s) {
             /* exact carry from the verified predecessor */
@@ -1117,7 +1121,7 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
 
     /* the lane that owns the end of the stream performs the EOF step(s) — unless more
      * chunks of the stream follow */
-    if (last_seg && !w.f(F_FINISHED) && !(G.flags & SRE_GEOM_NO_EOF)) {
+    if (last_seg && !w.f(F_FINISHED) && !(G.flags & SRE_GEOM_NO_EOF) && !w.f(F_NO_EOF)) {
         settle();
         w.anchor_pos = -1;
         slow_run<MODE>(w, w.n, w.n + 1, false, 0);
@@ -2226,7 +2230,8 @@ struct LineageWalk {
     uint64_t                 first;
     const sre_seg_lineage_t *maps, *blocks;
     bool                     use_maps;
-    const int64_t           *carried;   /* [SRE_STREAM_MAX_THREADS][SRE_STREAM_MAX_SLOTS], or null */
+    const int64_t           *carried;   /* [threads][carried_stride], or null */
+    uint32_t                 carried_stride;    /* SRE_STREAM_MAX_SLOTS (sre_stream_ctx_t) or nslots (a stream set's row) */
     int64_t                  base;
     int64_t                  walk_budget;   /* positions of plain walk before the maps are asked for */
 
@@ -2360,7 +2365,7 @@ struct LineageWalk {
             /* the search came in from the previous chunk: the rest is what the context
              * carries for this thread */
             for (uint32_t q = 0; q < nslots; q++) {
-                if ((unresolved >> q) & 1) vec[q] = carried[(size_t) j * SRE_STREAM_MAX_SLOTS + q];
+                if ((unresolved >> q) & 1) vec[q] = carried[(size_t) j * carried_stride + q];
             }
             unresolved = 0;
             break;
@@ -2566,6 +2571,7 @@ sre_k_captures(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
         lw.blocks = blocks;
         lw.use_maps = use_maps != 0;
         lw.carried = nullptr;
+        lw.carried_stride = 0;
         lw.base = 0;
         lw.walk_budget = SRE_WALK_BUDGET;
 #ifdef SRE_DEBUG_WALK
@@ -2619,6 +2625,247 @@ sre_k_captures(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
  */
 #define SRE_TAIL_THREADS 1024
 
+/* The carried context of one stream as the tail sees it, behind one pointer each: the compat path's
+ * sre_stream_ctx_t (rows SRE_STREAM_MAX_SLOTS wide) ... */
+struct TailCtxCompat {
+    sre_stream_ctx_t *c;
+    __device__ __forceinline__ uint32_t &state() const { return c->state; }
+    __device__ __forceinline__ uint32_t &has_pending() const { return c->has_pending; }
+    __device__ __forceinline__ int64_t  &pending_regex() const { return c->pending_regex; }
+    __device__ __forceinline__ int64_t  *pending_vec() const { return c->pending_vec; }
+    __device__ __forceinline__ int64_t  *caps() const { return &c->caps[0][0]; }
+    __device__ __forceinline__ int64_t  *caps_next() const { return &c->caps_next[0][0]; }
+    __device__ __forceinline__ uint32_t  stride() const { return SRE_STREAM_MAX_SLOTS; }
+};
+/* ... or a row of a stream set (rows nslots wide, sre_hip_streams.h) */
+struct TailCtxRow {
+    int64_t *row;
+    uint32_t nslots, max_threads;
+    __device__ __forceinline__ uint32_t &state() const { return reinterpret_cast<uint32_t *>(row + SRE_SROW_STATE)[0]; }
+    __device__ __forceinline__ uint32_t &has_pending() const { return reinterpret_cast<uint32_t *>(row + SRE_SROW_STATE)[1]; }
+    __device__ __forceinline__ int64_t  &pending_regex() const { return row[SRE_SROW_REGEX]; }
+    __device__ __forceinline__ int64_t  *pending_vec() const { return row + SRE_SROW_HDR; }
+    __device__ __forceinline__ int64_t  *caps() const { return row + SRE_SROW_HDR + nslots; }
+    __device__ __forceinline__ int64_t  *caps_next() const { return row + SRE_SROW_HDR + nslots + (size_t) max_threads * nslots; }
+    __device__ __forceinline__ uint32_t  stride() const { return nslots; }
+};
+/* one chunk of one stream: its bytes, its summaries, how it is entered and left */
+struct TailChunk {
+    const uint8_t           *data;
+    int64_t                  n, base;
+    const sre_seg_summary_t *sum;
+    uint64_t                 nseg;
+    uint32_t                 seg_bytes, variant, entry_state, ovec_slots;
+    bool                     continues, eof;
+    uint16_t                *scratch;
+    __attribute__((address_space(3))) uint16_t *sh_trace;   /* the walker's current 64-byte block (Tracer): 72 entries each */
+    __attribute__((address_space(3))) uint8_t  *sh_syms;
+};
+
+/* The tail of one chunk by ONE lane (sre_k_stream_tail, sre_k_streams_tail): updates the context,
+ * fills *res except rc and returns rc — SRE_STREAM_UNSETTLED when the chunk's lanes are not all
+ * verified (nothing was changed then that the call behind the fix-up rounds does not set again). */
+template <class Ctx>
+__device__ __forceinline__ int64_t
+stream_tail_body(const sre_scan_tables_t &T, const sre_scan_tables_t *__restrict__ tabp, const sre_stream_status_t &st,
+                 const TailChunk &K, const Ctx &ctx, sre_stream_result_t *__restrict__ res)
+{
+    int64_t                  rc_out = RC_ERROR;
+    const sre_seg_summary_t *sum = K.sum;
+    const uint64_t           nseg = K.nseg;
+    const int64_t            base = K.base;
+    const bool               eof = K.eof;
+    const uint32_t           ovec_slots = K.ovec_slots;
+    const uint32_t           nsym = T.ncls + 1;
+    const bool               continues = K.continues;
+    const int64_t            n = K.n;
+
+    res->has_pending = 0;
+    res->ev_in_chunk = 0;
+    res->ev_slot1 = -1;
+    res->poisoned = 0;
+    res->next_state = 0;
+    if (!continues) ctx.has_pending() = 0;       /* a search starts with this chunk: nothing is carried in */
+    if (!st.done) {
+        rc_out = SRE_STREAM_UNSETTLED;
+        return rc_out;
+    }
+    if (T.mode == 0) {
+        /* Thompson (sre_vm_thompson.c:63-270): SRE_OK at the first MATCH thread met, else
+         * SRE_DECLINED at eof / SRE_AGAIN with the list (= the state) carried on */
+        /* A MATCH thread is met when the position it is listed at is RUN: one listed by the
+         * closure behind the chunk's last byte waits for the next call that runs a position
+         * (a byte, or the extra iteration at eof; :88, :265-269) */
+        const bool carried_match = continues && ctx.has_pending() != 0;
+        bool       match_now = false, match_waits = false;
+        if (carried_match) {
+            match_now = n > 0 || eof;
+            match_waits = !match_now;
+        } else if (st.ev_pos >= 0) {
+            const uint32_t kind = T.trans[(size_t) st.ev_state * (T.ncls + 1) + st.ev_sym].kind;
+            const bool     listed_behind = (kind == EV_DONE || kind == SRE_DEV_EV_DONE_EMPTY);
+            match_waits = listed_behind && st.ev_pos == n - 1 && !eof;
+            match_now = !match_waits;
+        }
+        if (match_now) {
+            rc_out = 0;
+            ctx.state() = 0;
+            ctx.has_pending() = 0;
+        } else if (match_waits) {
+            ctx.has_pending() = 1;
+            ctx.state() = 1;                 /* (any live state: the next call does not get to use it) */
+            res->next_state = 1;
+            rc_out = -2;                    /* SRE_AGAIN */
+        } else if (eof) {
+            rc_out = RC_DECLINED;
+            ctx.state() = 0;
+            ctx.has_pending() = 0;
+        } else {
+            const uint32_t sF = sum[nseg - 1].s_out & ~SRE_STATE_SKIP;
+            ctx.state() = tabp->unskip[sF];
+            ctx.has_pending() = 0;
+            res->next_state = ctx.state();
+            rc_out = -2;                   /* SRE_AGAIN */
+        }
+        return rc_out;
+    }
+
+    Tracer tr;
+    tr.T = &T;
+    tr.sum = sum;
+    tr.data = K.data;
+    tr.n = n;
+    tr.sp = 0;
+    tr.seg_bytes = K.seg_bytes;
+    const uint32_t variant = K.variant;
+    tr.init_state = continues ? K.entry_state : T.init[variant];
+    tr.apos = st.ev_apos >= 0 ? st.ev_apos : -1;
+    tr.astate = st.ev_astate;
+    tr.ck = K.scratch;
+    tr.trace = K.sh_trace;
+    tr.syms = K.sh_syms;
+    tr.bind();
+    tr.seg_lo = tr.seg_hi = -1;
+    tr.blk_lo = 1;
+    tr.blk_hi = 0;
+    tr.seg_entry = 0;
+    tr.valid_from = 1;                  /* one search per chunk: every recorded entry state is its own */
+    tr.use_stable = (T.nshadow != 0);
+
+    LineageWalk lw;
+    lw.T = &T;
+    lw.tabp = tabp;
+    lw.tr = &tr;
+    lw.variant = variant;
+    lw.ev_seg = st.ev_seg >= 0 ? st.ev_seg : (int64_t) nseg;
+    lw.unst_seg = st.ev_seg >= 0 ? st.unst_seg : (int64_t) nseg;
+    lw.unst_end = T.nshadow ? st.unst_end : (int64_t) 1 << 62;
+    lw.first = 0;
+    lw.maps = lw.blocks = nullptr;
+    lw.use_maps = false;
+    lw.carried = continues ? ctx.caps() : nullptr;
+    lw.carried_stride = ctx.stride();
+    lw.base = base;
+    lw.walk_budget = (int64_t) 1 << 62;
+
+    const uint64_t all = T.nslots >= 64 ? ~0ull : ((1ull << T.nslots) - 1);
+    int64_t        vec[SRE_STREAM_MAX_SLOTS];
+
+    /* ---- a match event inside this chunk replaces the pending match */
+    if (st.ev_pos >= 0) {
+        uint64_t unresolved = all;
+        for (uint32_t q = 0; q < T.nslots; q++) vec[q] = -1;
+        const sre_dev_trans_t &te = T.trans[(size_t) st.ev_state * nsym + st.ev_sym];
+        if (te.kind == EV_DONE || te.kind == SRE_DEV_EV_DONE_EMPTY) {
+            const uint64_t m = te.saves & unresolved;
+            for (uint32_t q = 0; q < T.nslots; q++) {
+                if ((m >> q) & 1) vec[q] = st.ev_pos + 1 + base;
+            }
+            unresolved &= ~m;
+        }
+        if (te.early & unresolved) {
+            const uint64_t m = te.early & unresolved;
+            for (uint32_t q = 0; q < T.nslots; q++) {
+                if ((m >> q) & 1) vec[q] = st.ev_pos + base;
+            }
+            unresolved &= ~m;
+        }
+            lw.run(st.ev_pos, te.src, st.ev_state, unresolved, vec);
+        ctx.has_pending() = 1;
+        ctx.pending_regex() = st.rc;
+        for (uint32_t q = 0; q < T.nslots; q++) ctx.pending_vec()[q] = vec[q];
+        res->ev_in_chunk = 1;
+        res->ev_slot1 = vec[1];
+    }
+
+    /* ---- is the search over? */
+    const uint64_t last = (uint64_t) st.limit >= 1 ? (uint64_t) st.limit - 1 : 0;
+    const bool     died = (sum[last].flags & SRE_SUM_TERM) != 0;
+    if (died || eof) {
+        if (ctx.has_pending()) {
+            const int64_t id = ctx.pending_regex();
+            uint64_t      ofs = 0;
+            for (int64_t i = 0; i < id; i++) ofs += T.multi_ncaps[i] + 1;
+            ofs *= 2;
+            const uint64_t ncopy = 2ull * (T.multi_ncaps[id] + 1);
+            for (uint64_t q = 0; q < ovec_slots && q < SRE_STREAM_MAX_SLOTS; q++) {
+                res->ov[q] = q < ncopy ? ctx.pending_vec()[ofs + q] : -1;
+            }
+            rc_out = id;
+            res->poisoned = st.error ? 1 : 0;
+        } else {
+            rc_out = RC_DECLINED;
+        }
+        ctx.state() = 0;
+        ctx.has_pending() = 0;
+        return rc_out;
+    }
+
+    /* ---- SRE_AGAIN: carry the list (state + every thread's captures) to the next chunk */
+    const uint32_t sF = sum[nseg - 1].s_out & ~SRE_STATE_SKIP;
+    const uint32_t nth = T.list_off[sF + 1] - T.list_off[sF];
+    /* what the next chunk starts from: a leading-byte skip that is still travelling ends
+     * with the chunk (sre_dfa.h `unskip`); the list, and so the vectors, are the same */
+    const uint32_t sNext = tabp->unskip[sF];
+    int64_t        a0 = -1, a1 = -1;
+    /* the new vectors go to a second set of rows first: the walk of thread j may still
+     * read the carried vector of any thread */
+    int64_t *fresh = ctx.caps_next();
+    for (uint32_t j = 0; j < nth && j < SRE_STREAM_MAX_THREADS; j++) {
+        uint64_t unresolved = all;
+        for (uint32_t q = 0; q < T.nslots; q++) vec[q] = -1;
+        lw.run(n, j, sF, unresolved, vec);
+        for (uint32_t q = 0; q < T.nslots; q++) fresh[(size_t) j * ctx.stride() + q] = vec[q];
+        /* prepare_temp_captures (:692-735) */
+        uint64_t ofs = 0;
+        for (uint32_t r = 0; r < T.nregexes; r++) {
+            int64_t b = vec[ofs];
+            if (b != -1 && (a0 == -1 || b < a0)) a0 = b;
+            b = vec[1];
+            if (b != -1 && (a1 == -1 || b > a1)) a1 = b;
+            ofs += 2ull * (T.multi_ncaps[r] + 1);
+        }
+    }
+    for (uint32_t j = 0; j < nth && j < SRE_STREAM_MAX_THREADS; j++) {
+        for (uint32_t q = 0; q < T.nslots; q++) ctx.caps()[(size_t) j * ctx.stride() + q] = fresh[(size_t) j * ctx.stride() + q];
+    }
+    ctx.state() = sNext;
+    res->next_state = sNext;
+    res->ov[0] = a0;
+    res->ov[1] = a1;
+    rc_out = -2;                       /* SRE_AGAIN */
+    if (ctx.has_pending()) {
+        const int64_t id = ctx.pending_regex();
+        uint64_t      ofs = 0;
+        for (int64_t i = 0; i < id; i++) ofs += T.multi_ncaps[i] + 1;
+        ofs *= 2;
+        res->has_pending = 1;
+        res->pending[0] = ctx.pending_vec()[ofs];
+        res->pending[1] = ctx.pending_vec()[ofs + 1];
+    }
+    return rc_out;
+}
+
 /* verify != 0: the chain check of the chunk runs here too (verify_one_stream), in front of
  * the tail, and leaves the status word in status[0] */
 __global__ __launch_bounds__(SRE_TAIL_THREADS) void
@@ -2649,199 +2896,24 @@ sre_k_stream_tail(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     if (threadIdx.x != 0) return;
     /* the host may be spinning on res->rc (host-visible memory): it is written last, behind
      * a system-scope fence, once everything else of the result is in place */
-    int64_t rc_out = RC_ERROR;
-    auto body = [&]() {
-    const sre_scan_tables_t   &T = Ts;
-    const sre_stream_status_t  st = verify ? sh_st : status[0];
-    const uint32_t             nsym = T.ncls + 1;
-    const bool                 continues = (G.flags & SRE_GEOM_CONTINUES) != 0;
-    const int64_t              n = (int64_t) geom_len(G, 0);
-
-    res->has_pending = 0;
-    res->ev_in_chunk = 0;
-    res->ev_slot1 = -1;
-    res->poisoned = 0;
-    res->next_state = 0;
-    if (!continues) ctx->has_pending = 0;       /* a search starts with this chunk: nothing is carried in */
-    if (!st.done) {
-        rc_out = SRE_STREAM_UNSETTLED;
-        return;
-    }
-    if (T.mode == 0) {
-        /* Thompson (sre_vm_thompson.c:63-270): SRE_OK at the first MATCH thread met, else
-         * SRE_DECLINED at eof / SRE_AGAIN with the list (= the state) carried on */
-        /* A MATCH thread is met when the position it is listed at is RUN: one listed by the
-         * closure behind the chunk's last byte waits for the next call that runs a position
-         * (a byte, or the extra iteration at eof; :88, :265-269) */
-        const bool carried_match = continues && ctx->has_pending != 0;
-        bool       match_now = false, match_waits = false;
-        if (carried_match) {
-            match_now = n > 0 || eof;
-            match_waits = !match_now;
-        } else if (st.ev_pos >= 0) {
-            const uint32_t kind = T.trans[(size_t) st.ev_state * (T.ncls + 1) + st.ev_sym].kind;
-            const bool     listed_behind = (kind == EV_DONE || kind == SRE_DEV_EV_DONE_EMPTY);
-            match_waits = listed_behind && st.ev_pos == n - 1 && !eof;
-            match_now = !match_waits;
-        }
-        if (match_now) {
-            rc_out = 0;
-            ctx->state = 0;
-            ctx->has_pending = 0;
-        } else if (match_waits) {
-            ctx->has_pending = 1;
-            ctx->state = 1;                 /* (any live state: the next call does not get to use it) */
-            res->next_state = 1;
-            rc_out = -2;                    /* SRE_AGAIN */
-        } else if (eof) {
-            rc_out = RC_DECLINED;
-            ctx->state = 0;
-            ctx->has_pending = 0;
-        } else {
-            const uint32_t sF = sum[nseg - 1].s_out & ~SRE_STATE_SKIP;
-            ctx->state = tabp->unskip[sF];
-            ctx->has_pending = 0;
-            res->next_state = ctx->state;
-            rc_out = -2;                   /* SRE_AGAIN */
-        }
-        return;
-    }
-
-    Tracer tr;
-    tr.T = &T;
-    tr.sum = sum;
-    tr.data = geom_ptr(G, 0);
-    tr.n = n;
-    tr.sp = 0;
-    tr.seg_bytes = G.seg_bytes;
-    const uint32_t variant = G.init_variant;
-    tr.init_state = continues ? G.entry_state : T.init[variant];
-    tr.apos = st.ev_apos >= 0 ? st.ev_apos : -1;
-    tr.astate = st.ev_astate;
-    tr.ck = scratch;
-    tr.trace = (__attribute__((address_space(3))) uint16_t *) sh_trace;
-    tr.syms = (__attribute__((address_space(3))) uint8_t *) sh_syms;
-    tr.bind();
-    tr.seg_lo = tr.seg_hi = -1;
-    tr.blk_lo = 1;
-    tr.blk_hi = 0;
-    tr.seg_entry = 0;
-    tr.valid_from = 1;                  /* one search per chunk: every recorded entry state is its own */
-    tr.use_stable = (T.nshadow != 0);
-
-    LineageWalk lw;
-    lw.T = &T;
-    lw.tabp = tabp;
-    lw.tr = &tr;
-    lw.variant = variant;
-    lw.ev_seg = st.ev_seg >= 0 ? st.ev_seg : (int64_t) nseg;
-    lw.unst_seg = st.ev_seg >= 0 ? st.unst_seg : (int64_t) nseg;
-    lw.unst_end = T.nshadow ? st.unst_end : (int64_t) 1 << 62;
-    lw.first = 0;
-    lw.maps = lw.blocks = nullptr;
-    lw.use_maps = false;
-    lw.carried = continues ? &ctx->caps[0][0] : nullptr;
-    lw.base = base;
-    lw.walk_budget = (int64_t) 1 << 62;
-
-    const uint64_t all = T.nslots >= 64 ? ~0ull : ((1ull << T.nslots) - 1);
-    int64_t        vec[SRE_STREAM_MAX_SLOTS];
-
-    /* ---- a match event inside this chunk replaces the pending match */
-    if (st.ev_pos >= 0) {
-        uint64_t unresolved = all;
-        for (uint32_t q = 0; q < T.nslots; q++) vec[q] = -1;
-        const sre_dev_trans_t &te = T.trans[(size_t) st.ev_state * nsym + st.ev_sym];
-        if (te.kind == EV_DONE || te.kind == SRE_DEV_EV_DONE_EMPTY) {
-            const uint64_t m = te.saves & unresolved;
-            for (uint32_t q = 0; q < T.nslots; q++) {
-                if ((m >> q) & 1) vec[q] = st.ev_pos + 1 + base;
-            }
-            unresolved &= ~m;
-        }
-        if (te.early & unresolved) {
-            const uint64_t m = te.early & unresolved;
-            for (uint32_t q = 0; q < T.nslots; q++) {
-                if ((m >> q) & 1) vec[q] = st.ev_pos + base;
-            }
-            unresolved &= ~m;
-        }
-        /* carried stride: the context's rows are SRE_STREAM_MAX_SLOTS wide */
-        lw.run(st.ev_pos, te.src, st.ev_state, unresolved, vec);
-        ctx->has_pending = 1;
-        ctx->pending_regex = st.rc;
-        for (uint32_t q = 0; q < T.nslots; q++) ctx->pending_vec[q] = vec[q];
-        res->ev_in_chunk = 1;
-        res->ev_slot1 = vec[1];
-    }
-
-    /* ---- is the search over? */
-    const uint64_t last = (uint64_t) st.limit >= 1 ? (uint64_t) st.limit - 1 : 0;
-    const bool     died = (sum[last].flags & SRE_SUM_TERM) != 0;
-    if (died || eof) {
-        if (ctx->has_pending) {
-            const int64_t id = ctx->pending_regex;
-            uint64_t      ofs = 0;
-            for (int64_t i = 0; i < id; i++) ofs += T.multi_ncaps[i] + 1;
-            ofs *= 2;
-            const uint64_t ncopy = 2ull * (T.multi_ncaps[id] + 1);
-            for (uint64_t q = 0; q < ovec_slots && q < SRE_STREAM_MAX_SLOTS; q++) {
-                res->ov[q] = q < ncopy ? ctx->pending_vec[ofs + q] : -1;
-            }
-            rc_out = id;
-            res->poisoned = st.error ? 1 : 0;
-        } else {
-            rc_out = RC_DECLINED;
-        }
-        ctx->state = 0;
-        ctx->has_pending = 0;
-        return;
-    }
-
-    /* ---- SRE_AGAIN: carry the list (state + every thread's captures) to the next chunk */
-    const uint32_t sF = sum[nseg - 1].s_out & ~SRE_STATE_SKIP;
-    const uint32_t nth = T.list_off[sF + 1] - T.list_off[sF];
-    /* what the next chunk starts from: a leading-byte skip that is still travelling ends
-     * with the chunk (sre_dfa.h `unskip`); the list, and so the vectors, are the same */
-    const uint32_t sNext = tabp->unskip[sF];
-    int64_t        a0 = -1, a1 = -1;
-    /* the new vectors go to a second set of rows first: the walk of thread j may still
-     * read the carried vector of any thread */
-    int64_t *fresh = &ctx->caps_next[0][0];
-    for (uint32_t j = 0; j < nth && j < SRE_STREAM_MAX_THREADS; j++) {
-        uint64_t unresolved = all;
-        for (uint32_t q = 0; q < T.nslots; q++) vec[q] = -1;
-        lw.run(n, j, sF, unresolved, vec);
-        for (uint32_t q = 0; q < T.nslots; q++) fresh[(size_t) j * SRE_STREAM_MAX_SLOTS + q] = vec[q];
-        /* prepare_temp_captures (:692-735) */
-        uint64_t ofs = 0;
-        for (uint32_t r = 0; r < T.nregexes; r++) {
-            int64_t b = vec[ofs];
-            if (b != -1 && (a0 == -1 || b < a0)) a0 = b;
-            b = vec[1];
-            if (b != -1 && (a1 == -1 || b > a1)) a1 = b;
-            ofs += 2ull * (T.multi_ncaps[r] + 1);
-        }
-    }
-    for (uint32_t j = 0; j < nth && j < SRE_STREAM_MAX_THREADS; j++) {
-        for (uint32_t q = 0; q < T.nslots; q++) ctx->caps[j][q] = fresh[(size_t) j * SRE_STREAM_MAX_SLOTS + q];
-    }
-    ctx->state = sNext;
-    res->next_state = sNext;
-    res->ov[0] = a0;
-    res->ov[1] = a1;
-    rc_out = -2;                       /* SRE_AGAIN */
-    if (ctx->has_pending) {
-        const int64_t id = ctx->pending_regex;
-        uint64_t      ofs = 0;
-        for (int64_t i = 0; i < id; i++) ofs += T.multi_ncaps[i] + 1;
-        ofs *= 2;
-        res->has_pending = 1;
-        res->pending[0] = ctx->pending_vec[ofs];
-        res->pending[1] = ctx->pending_vec[ofs + 1];
-    }
-    };
-    body();
+    const sre_stream_status_t st = verify ? sh_st : status[0];
+    TailChunk K;
+    K.data = geom_ptr(G, 0);
+    K.n = (int64_t) geom_len(G, 0);
+    K.base = base;
+    K.sum = sum;
+    K.nseg = nseg;
+    K.seg_bytes = G.seg_bytes;
+    K.variant = G.init_variant;
+    K.entry_state = G.entry_state;
+    K.ovec_slots = ovec_slots;
+    K.continues = (G.flags & SRE_GEOM_CONTINUES) != 0;
+    K.eof = eof != 0;
+    K.scratch = scratch;
+    K.sh_trace = (__attribute__((address_space(3))) uint16_t *) sh_trace;
+    K.sh_syms = (__attribute__((address_space(3))) uint8_t *) sh_syms;
+    const TailCtxCompat C = {ctx};
+    const int64_t rc_out = stream_tail_body(Ts, tabp, st, K, C, res);
 #ifdef SRE_DEBUG_TAIL
     /* (10 ns ticks) table staging, chain check, the lane's work */
     res->ov[SRE_STREAM_MAX_SLOTS - 3] = (int64_t) (dbg_t1 - dbg_t0);
@@ -2850,6 +2922,100 @@ sre_k_stream_tail(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
 #endif
     __threadfence_system();
     *reinterpret_cast<volatile int64_t *>(&res->rc) = rc_out;
+}
+
+/*
+ * Stream sets (sre_hip_streams.h): the tail of every stream of the set that was fed in this call,
+ * behind the scan and sre_launch_verify.  A workgroup stages the walker's tables once and takes
+ * its streams in turn (blockIdx.x, + gridDim.x, ...); lane 0 runs stream_tail_body against the
+ * stream's context row with base = the row's processed_bytes, then does what the compat path
+ * does on the host behind the result (sre_vm_api.cpp pike_stream_route): seen_newline / seen_word
+ * from the byte in front of a match end reached in this call (sre_vm_pike.c:586-601),
+ * processed_bytes += len on SRE_AGAIN, closing the stream on a final answer — and writes the
+ * stream's record.  A stream whose lanes are not all verified gets rc SRE_STREAM_UNSETTLED and is
+ * counted in info->unsettled; only_unsettled != 0: the call behind the fix-up rounds, for those.
+ */
+__global__ __launch_bounds__(SRE_STREAMS_TAIL_THREADS) void
+sre_k_streams_tail(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
+                   const sre_seg_summary_t *__restrict__ sum, const sre_stream_status_t *__restrict__ status,
+                   uint16_t *__restrict__ scratch, int64_t *__restrict__ rows, sre_streams_layout_t L,
+                   sre_stream_result_t *__restrict__ tailres, int64_t *__restrict__ recs,
+                   sre_streams_info_t *__restrict__ info, int only_unsettled)
+{
+    SRE_TAIL_PRIO();
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ sre_scan_tables_t Ts;
+    __shared__ uint16_t sh_trace[72];
+    __shared__ uint8_t  sh_syms[72];
+    stage_walk_tables(tabp, lds, &Ts);
+    if (threadIdx.x != 0) return;
+    sre_stream_result_t *res = tailres + blockIdx.x;
+    for (uint32_t s = blockIdx.x; s < G.nstreams; s += gridDim.x) {
+        const uint64_t first = G.seg_first[s], nseg = G.seg_first[s + 1] - first;
+        if (nseg == 0) continue;                /* not fed in this call, or closed before it */
+        int64_t *rec = recs + (size_t) s * L.rec_slots;
+        if (only_unsettled && rec[0] != SRE_STREAM_UNSETTLED) continue;
+        int64_t       *row = rows + (size_t) s * L.row_words;
+        const uint32_t e = G.sentry[s];
+        uint64_t       fl = (uint64_t) row[SRE_SROW_FLAGS];
+        const int64_t  processed = row[SRE_SROW_PROCESSED];
+        TailChunk K;
+        K.data = G.streams[s];
+        K.n = (int64_t) G.lens[s];
+        K.base = processed;
+        K.sum = sum + first;
+        K.nseg = nseg;
+        K.seg_bytes = G.seg_bytes;
+        K.variant = 0;                          /* one search per stream: it starts at offset 0 of the stream */
+        K.entry_state = SRE_SENTRY_STATE(e);
+        K.ovec_slots = L.ovec_slots;
+        K.continues = (e & SRE_SENTRY_CONTINUES) != 0;
+        K.eof = (e & SRE_SENTRY_NO_EOF) == 0;
+        K.scratch = scratch + (size_t) blockIdx.x * (G.seg_bytes + 16);
+        K.sh_trace = (__attribute__((address_space(3))) uint16_t *) sh_trace;
+        K.sh_syms = (__attribute__((address_space(3))) uint8_t *) sh_syms;
+        const TailCtxRow C = {row, L.nslots, L.max_threads};
+        const int64_t rc = stream_tail_body(Ts, tabp, status[s], K, C, res);
+        if (rc == SRE_STREAM_UNSETTLED) {
+            rec[0] = rc;
+            atomicAdd(reinterpret_cast<unsigned long long *>(&info->unsettled), 1ull);
+            continue;
+        }
+        if (res->ev_in_chunk && res->ev_slot1 >= 0) {
+            const int64_t p = res->ev_slot1 - processed;            /* chunk-relative end */
+            if (p > 0 && p <= K.n) {
+                const uint8_t c = K.data[p - 1];
+                const bool    word = (c >= '0' && c <= '9') || (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || c == '_';
+                fl = (fl & ~(uint64_t) (SRE_SFL_NEWLINE | SRE_SFL_WORD)) | (c == '\n' ? SRE_SFL_NEWLINE : 0u)
+                     | (word ? SRE_SFL_WORD : 0u);
+            }
+        }
+        rec[0] = rc;
+        rec[2] = 0;
+        rec[3] = rec[4] = -1;
+        for (uint32_t q = 0; q < L.ovec_slots; q++) rec[5 + q] = -1;
+        if (rc == -2) {                         /* SRE_AGAIN */
+            rec[1] = 0;
+            if (L.ovec_slots >= 2 && Ts.mode != 0) {
+                rec[5] = res->ov[0];
+                rec[6] = res->ov[1];
+            }
+            if (res->has_pending) {
+                rec[2] = 1;
+                rec[3] = res->pending[0];
+                rec[4] = res->pending[1];
+            }
+            row[SRE_SROW_PROCESSED] = processed + K.n;              /* sre_vm_pike.c:673 */
+            fl |= SRE_SFL_STARTED;
+        } else {
+            rec[1] = 1;
+            if (rc >= 0 && Ts.mode != 0) {
+                for (uint32_t q = 0; q < L.ovec_slots; q++) rec[5 + q] = res->ov[q];
+            }
+            fl = (fl & ~(uint64_t) SRE_SFL_STARTED) | SRE_SFL_CLOSED;
+        }
+        row[SRE_SROW_FLAGS] = (int64_t) fl;
+    }
 }
 
 }  // namespace
@@ -3115,5 +3281,29 @@ sre_launch_stream_tail(const sre_scan_tables_t *d_tab, sre_scan_tables_t h_tab, 
     }
     hipLaunchKernelGGL(sre_k_stream_tail, dim3(1), dim3(SRE_TAIL_THREADS), shmem, stream, d_tab, geom, d_sum, d_status,
                        d_scratch, d_ctx, result, base, eof, ovec_slots, verify);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_streams_tail(const sre_scan_tables_t *d_tab, sre_scan_tables_t h_tab, sre_scan_geom_t geom,
+                        const sre_seg_summary_t *d_sum, const sre_stream_status_t *d_status, uint16_t *d_scratch,
+                        int64_t *d_rows, sre_streams_layout_t layout, sre_stream_result_t *d_tailres, int64_t *d_recs,
+                        sre_streams_info_t *d_info, uint32_t grid, int only_unsettled, hipStream_t stream)
+{
+    if (geom.nstreams == 0 || grid == 0) return hipSuccess;
+    const size_t shmem = (size_t) h_tab.fast_bytes + 256
+                         + ((size_t) h_tab.nstates * (h_tab.ncls + 1) + SRE_SCAN_NINIT) * sizeof(sre_dev_trans_t)
+                         + (size_t) h_tab.lin_total * 9 + ((size_t) h_tab.nstates + 1 + h_tab.list_total) * 4 + 16;
+    if (shmem > 48 * 1024) {
+        static bool raised = false;
+        if (!raised) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sre_k_streams_tail),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, SRE_CAPTURE_LDS_LIMIT);
+            if (e != hipSuccess) return e;
+            raised = true;
+        }
+    }
+    hipLaunchKernelGGL(sre_k_streams_tail, dim3(grid), dim3(SRE_STREAMS_TAIL_THREADS), shmem, stream, d_tab, geom, d_sum,
+                       d_status, d_scratch, d_rows, layout, d_tailres, d_recs, d_info, only_unsettled);
     return hipGetLastError();
 }
