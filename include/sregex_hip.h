@@ -253,6 +253,21 @@ typedef struct sre_hip_streams_s sre_hip_streams_t;
 SRE_API sre_hip_streams_t *sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog,
     int mode, size_t nstreams);
 
+/* as sre_hip_streams_create, with the engine chosen like sre_hip_scanner_create's:
+ * SRE_HIP_ENGINE_SCAN = exactly sre_hip_streams_create; SRE_HIP_ENGINE_NFA = the bit-parallel NFA tier
+ * (64, 128 or 256 bits) or NULL; SRE_HIP_ENGINE_AUTO = the table-driven scanner when it admits the program's
+ * chunks, else the NFA tier, else NULL.  SRE_HIP_ENGINE_VM: NULL.
+ *
+ * The NFA tier takes SRE_HIP_THOMPSON streams of programs without look-ahead assertions (counted
+ * repeats, `(a|b)*a(a|b){k}`-shaped rules): there a stream's context is its thread set, so feeding in
+ * chunks equals feeding the whole buffer.  Every other combination is NULL with a diagnostic on stderr;
+ * a Pike first match is not offered (its exact window starts at a position that may lie in a chunk that
+ * is gone).  feed, reset, the record and the diagnostics are those of the table-driven set. */
+SRE_API sre_hip_streams_t *sre_hip_streams_create_engine(sre_pool_t *pool, sre_program_t *prog,
+    int mode, int engine, size_t nstreams);
+SRE_API int sre_hip_streams_engine(sre_hip_streams_t *ss);     /* SRE_HIP_ENGINE_SCAN or _NFA */
+SRE_API int sre_hip_streams_nfa_bits(sre_hip_streams_t *ss);   /* 64 / 128 / 256, 0 on the scanner */
+
 SRE_API size_t sre_hip_streams_count(sre_hip_streams_t *ss);
 
 /* sre_int_t per record: 5 + 2 * (max_ncaps + 1) */
@@ -260,7 +275,8 @@ SRE_API size_t sre_hip_streams_result_slots(sre_hip_streams_t *ss);
 
 /* HBM the set holds for its contexts: nstreams rows of 8 * (4 + nslots * (1 + 2 * max_threads))
  * bytes, nslots and max_threads being the program's capture slots and longest thread list
- * (Thompson: 32 bytes a stream) */
+ * (Thompson: 32 bytes a stream).  On the NFA tier: nstreams * 8 * (1 + W) bytes, W = nfa_bits / 64 —
+ * one flag word (started, match pending, closed, the closing rc) and the thread set */
 SRE_API size_t sre_hip_streams_device_bytes(sre_hip_streams_t *ss);
 
 /*
@@ -296,6 +312,9 @@ SRE_API int sre_hip_streams_last_fixups(sre_hip_streams_t *ss);
 
 /* diagnostics: kernels and copies the last feed queued (fix-up rounds: the batches of rounds) */
 SRE_API int sre_hip_streams_last_launches(sre_hip_streams_t *ss);
+
+/* diagnostics: exact-entry passes of the last feed's fix-up rounds (as sre_hip_scanner_last_exact_passes) */
+SRE_API int sre_hip_streams_last_exact_passes(sre_hip_streams_t *ss);
 
 /* ---- helpers for drivers that have no HIP runtime binding of their own ---- */
 

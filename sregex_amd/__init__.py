@@ -79,6 +79,10 @@ API = {
                                           ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_streams_create": (_vp, [_vp, _vp, ctypes.c_int, _sz]),
+    "sre_hip_streams_create_engine": (_vp, [_vp, _vp, ctypes.c_int, ctypes.c_int, _sz]),
+    "sre_hip_streams_engine": (ctypes.c_int, [_vp]),
+    "sre_hip_streams_nfa_bits": (ctypes.c_int, [_vp]),
+    "sre_hip_streams_last_exact_passes": (ctypes.c_int, [_vp]),
     "sre_hip_streams_count": (_sz, [_vp]),
     "sre_hip_streams_result_slots": (_sz, [_vp]),
     "sre_hip_streams_device_bytes": (_sz, [_vp]),
@@ -408,12 +412,17 @@ class StreamSet:
 
     OPEN, CLOSED, WAS_CLOSED, NOT_FED = 0, 1, 2, 3
 
-    def __init__(self, pool, prog, mode, nstreams):
+    def __init__(self, pool, prog, mode, nstreams, engine=None):
+        """engine: None = sre_hip_streams_create (the table-driven scanner); ENGINE_AUTO / ENGINE_SCAN /
+        ENGINE_NFA = sre_hip_streams_create_engine (the NFA tier: HIP_THOMPSON, no look-ahead assertions)"""
         self.lib = pool.lib
-        self.h = self.lib.sre_hip_streams_create(pool.p, prog.h, mode, nstreams)
+        if engine is None:
+            self.h = self.lib.sre_hip_streams_create(pool.p, prog.h, mode, nstreams)
+        else:
+            self.h = self.lib.sre_hip_streams_create_engine(pool.p, prog.h, mode, engine, nstreams)
         if not self.h:
-            raise RuntimeError("sre_hip_streams_create failed (no HIP device, or the program's chunks "
-                               "do not run on the table-driven scanner)")
+            raise RuntimeError("sre_hip_streams_create%s failed (no HIP device, or the program's chunks "
+                               "do not run on the engine asked for)" % ("" if engine is None else "_engine"))
         self.n = self.lib.sre_hip_streams_count(self.h)
         self.slots = self.lib.sre_hip_streams_result_slots(self.h)
         self._out = (ctypes.c_ssize_t * (self.n * self.slots))()
@@ -451,6 +460,18 @@ class StreamSet:
     @property
     def last_launches(self):
         return self.lib.sre_hip_streams_last_launches(self.h)
+
+    @property
+    def engine(self):
+        return self.lib.sre_hip_streams_engine(self.h)
+
+    @property
+    def nfa_bits(self):
+        return self.lib.sre_hip_streams_nfa_bits(self.h)
+
+    @property
+    def last_exact_passes(self):
+        return self.lib.sre_hip_streams_last_exact_passes(self.h)
 
 
 class DeviceBuffer:

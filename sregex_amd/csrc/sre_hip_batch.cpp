@@ -21,6 +21,7 @@
 #include "sre_pwave.h"
 #include "sre_hip_lines.h"
 #include "sre_hip_streams.h"
+#include "sre_streams_nfa.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -115,6 +116,7 @@ struct sre_hip_scanner_s {
     size_t                    nmat_cap;
     void                     *d_nacc;
     sre_nfa_status_t         *d_nstatus, *h_nstatus;
+    const uint64_t           *d_eset;           /* stream sets: [nstreams][W] per-stream entry sets of the call in flight, else NULL */
     /* line mode (sre_hip_scan_lines), grown on demand */
     uint64_t                 *d_ends;           /* line table: one end offset per line */
     size_t                    ends_cap;
@@ -390,10 +392,10 @@ static hipError_t
 nfa_launch_scan(sre_hip_scanner_t *sc, const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid,
                 hipStream_t stream)
 {
-    if (sc->wide_kernel) return sre_launch_nfa_wide_scan(sc->wtab, sc->geom, sc->d_nsum, sc->d_wsets, d_lo, d_belief, d_bvalid, stream);
-    if (sc->use_sa) return sre_launch_nfa_sa_scan(sc->satab, sc->geom, sc->d_nsum, d_lo, d_belief, d_bvalid, stream);
+    if (sc->wide_kernel) return sre_launch_nfa_wide_scan(sc->wtab, sc->geom, sc->d_nsum, sc->d_wsets, d_lo, d_belief, d_bvalid, sc->d_eset, stream);
+    if (sc->use_sa) return sre_launch_nfa_sa_scan(sc->satab, sc->geom, sc->d_nsum, d_lo, d_belief, d_bvalid, sc->d_eset, stream);
     return sre_launch_nfa_scan(sc->mode == SRE_HIP_THOMPSON ? SRE_HIP_THOMPSON : SRE_HIP_PIKE_FIRST, sc->ntab, sc->geom,
-                               sc->d_nsum, d_lo, d_belief, d_bvalid, stream);
+                               sc->d_nsum, d_lo, d_belief, d_bvalid, sc->d_eset, stream);
 }
 
 extern "C" SRE_API int
@@ -770,6 +772,31 @@ scan_resident(sre_hip_scanner_t *sc)
 
 static int scan_buffers(sre_hip_scanner_t *sc, size_t nstreams, uint64_t seg, uint64_t nsegs);
 
+/* the NFA tier's per-call buffers: summaries, beliefs, the wide kernel's sets */
+static int
+nfa_buffers(sre_hip_scanner_t *sc, uint64_t nsegs)
+{
+    if (nsegs > sc->nsum_cap) {
+        if (sc->d_nsum) (void) hipFree(sc->d_nsum);
+        if (sc->d_belief) (void) hipFree(sc->d_belief);
+        if (sc->d_bvalid) (void) hipFree(sc->d_bvalid);
+        if (sc->d_wsets) (void) hipFree(sc->d_wsets);
+        sc->d_nsum = NULL;
+        sc->d_belief = NULL;
+        sc->d_bvalid = NULL;
+        sc->d_wsets = NULL;
+        sc->nsum_cap = 0;
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nsum), nsegs * sizeof(sre_nfa_summary_t)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_belief), nsegs * nfa_words(sc) * sizeof(uint64_t)));
+        if (sc->wide_kernel) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_wsets), nsegs * 2 * nfa_words(sc) * sizeof(uint64_t)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_bvalid), nsegs));
+        sc->nsum_cap = nsegs;
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
 /* segment geometry: one lane per segment, 256 lanes per workgroup.  The number
  * of workgroups is steered towards a whole multiple of what the chip holds at
  * once (LDS-limited: 160 KiB per CU), so the last round of workgroups is not
@@ -821,28 +848,8 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
     sc->geom_one = (nstreams == 1 && sc->engine == SRE_HIP_ENGINE_SCAN) ? SRE_GEOM_ONE : 0u;
     sc->geom.flags = (sc->geom.flags & ~SRE_GEOM_ONE) | sc->geom_one;
 
-    if (sc->engine == SRE_HIP_ENGINE_NFA) {
-        if (nsegs > sc->nsum_cap) {
-            if (sc->d_nsum) (void) hipFree(sc->d_nsum);
-            if (sc->d_belief) (void) hipFree(sc->d_belief);
-            if (sc->d_bvalid) (void) hipFree(sc->d_bvalid);
-            if (sc->d_wsets) (void) hipFree(sc->d_wsets);
-            sc->d_nsum = NULL;
-            sc->d_belief = NULL;
-            sc->d_bvalid = NULL;
-            sc->d_wsets = NULL;
-            sc->nsum_cap = 0;
-            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nsum), nsegs * sizeof(sre_nfa_summary_t)));
-            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_belief), nsegs * nfa_words(sc) * sizeof(uint64_t)));
-            if (sc->wide_kernel) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_wsets), nsegs * 2 * nfa_words(sc) * sizeof(uint64_t)));
-            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_bvalid), nsegs));
-            sc->nsum_cap = nsegs;
-        }
-        return 0;
-    }
+    if (sc->engine == SRE_HIP_ENGINE_NFA) return nfa_buffers(sc, nsegs);
     return scan_buffers(sc, nstreams, seg, nsegs);
-hip_failed:
-    return -1;
 }
 
 /* the table-driven scanner's per-call buffers: summaries, the chain check's digest (small
@@ -955,6 +962,60 @@ hip_failed:
     return -1;
 }
 
+/* NFA tier: one fix-up round over the streams listed in d_lo (already on the device): past the
+ * speculative rounds every remaining lane's exact entry set first, then the set pass and the chain check */
+static int
+nfa_fixup_round(sre_hip_scanner_t *sc, hipStream_t stream)
+{
+    if (++sc->fixup_rounds > 1000000) {
+        fprintf(stderr, "[sregex-hip] NFA scanner fix-up did not converge\n");
+        return -1;
+    }
+    if (sc->fixup_rounds > SRE_SPECULATIVE_FIXUPS && sc->geom.nsegs <= ((size_t) 1 << 23)       /* (512 bytes a segment) */
+        && getenv("SRE_HIP_NO_NFA_EXACT") == NULL) {
+        /* speculation does not settle this batch (a program that never forgets): every remaining lane's
+         * exact entry set from the segments' singleton exit sets — the pass below is then exact */
+        if (sc->wide_kernel) {
+            /* the wide matrix: 64W x W words a segment (8 KiB at 256 bits).  It takes at most half of the
+             * device memory that is free; when it cannot be had, speculation goes on (slower, never wrong) */
+            const size_t need = sre_nfa_wide_matrix_bytes(sc->wtab.W, sc->geom.nsegs);
+            if (need > sc->nmat_cap * 64 * sizeof(uint64_t)) {
+                if (sc->d_nmat) (void) hipFree(sc->d_nmat);
+                sc->d_nmat = NULL;
+                sc->nmat_cap = 0;
+                size_t free_b = 0, total_b = 0;
+                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2
+                    && hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), need) == hipSuccess) {
+                    sc->nmat_cap = need / (64 * sizeof(uint64_t));
+                } else {
+                    (void) hipGetLastError();
+                    sc->d_nmat = NULL;
+                }
+            }
+            if (sc->d_nmat) {
+                SRE_HIP_TRY(sre_launch_nfa_wide_exact_entries(sc->wtab, sc->geom, sc->d_nsum, sc->d_wsets, sc->d_lo, sc->d_nmat,
+                                                              sc->d_belief, sc->d_bvalid, stream));
+                sc->exact_passes++;
+            }
+        } else {
+            if (sc->geom.nsegs > sc->nmat_cap) {
+                if (sc->d_nmat) (void) hipFree(sc->d_nmat);
+                sc->d_nmat = NULL;
+                sc->nmat_cap = 0;
+                SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), sc->geom.nsegs * 64 * sizeof(uint64_t)));
+                sc->nmat_cap = sc->geom.nsegs;
+            }
+            SRE_HIP_TRY(sre_launch_nfa_exact_entries(sc->use_sa ? 1 : 0, sc->ntab, sc->satab, sc->geom, sc->d_nsum, sc->d_lo,
+                                                     sc->d_nmat, sc->d_belief, sc->d_bvalid, stream));
+            sc->exact_passes++;
+        }
+    }
+    SRE_HIP_TRY(nfa_launch_scan(sc, sc->d_lo, sc->d_belief, sc->d_bvalid, stream));
+    return nfa_finish(sc, sc->d_lo, stream);
+hip_failed:
+    return -1;
+}
+
 /* NFA tier: segments behind a wrong entry set are re-run — the first one from the exact carried
  * set, the ones behind it from what their predecessor's lane ended in last round (sets only grow
  * towards the truth, so corrections travel many segments per round) — until every stream's
@@ -979,52 +1040,8 @@ nfa_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool *psettled)
         }
         if (pending == 0) break;
         *psettled = false;
-        if (++sc->fixup_rounds > 1000000) {
-            fprintf(stderr, "[sregex-hip] NFA scanner fix-up did not converge\n");
-            return -1;
-        }
         SRE_HIP_TRY(hipMemcpyAsync(sc->d_lo, sc->h_lo, n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-        if (sc->fixup_rounds > SRE_SPECULATIVE_FIXUPS && sc->geom.nsegs <= ((size_t) 1 << 23)       /* (512 bytes a segment) */
-            && getenv("SRE_HIP_NO_NFA_EXACT") == NULL) {
-            /* speculation does not settle this batch (a program that never forgets): every remaining lane's
-             * exact entry set from the segments' singleton exit sets — the pass below is then exact */
-            if (sc->wide_kernel) {
-                /* the wide matrix: 64W x W words a segment (8 KiB at 256 bits).  It takes at most half of the
-                 * device memory that is free; when it cannot be had, speculation goes on (slower, never wrong) */
-                const size_t need = sre_nfa_wide_matrix_bytes(sc->wtab.W, sc->geom.nsegs);
-                if (need > sc->nmat_cap * 64 * sizeof(uint64_t)) {
-                    if (sc->d_nmat) (void) hipFree(sc->d_nmat);
-                    sc->d_nmat = NULL;
-                    sc->nmat_cap = 0;
-                    size_t free_b = 0, total_b = 0;
-                    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= free_b / 2
-                        && hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), need) == hipSuccess) {
-                        sc->nmat_cap = need / (64 * sizeof(uint64_t));
-                    } else {
-                        (void) hipGetLastError();
-                        sc->d_nmat = NULL;
-                    }
-                }
-                if (sc->d_nmat) {
-                    SRE_HIP_TRY(sre_launch_nfa_wide_exact_entries(sc->wtab, sc->geom, sc->d_nsum, sc->d_wsets, sc->d_lo, sc->d_nmat,
-                                                                  sc->d_belief, sc->d_bvalid, stream));
-                    sc->exact_passes++;
-                }
-            } else {
-                if (sc->geom.nsegs > sc->nmat_cap) {
-                    if (sc->d_nmat) (void) hipFree(sc->d_nmat);
-                    sc->d_nmat = NULL;
-                    sc->nmat_cap = 0;
-                    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_nmat), sc->geom.nsegs * 64 * sizeof(uint64_t)));
-                    sc->nmat_cap = sc->geom.nsegs;
-                }
-                SRE_HIP_TRY(sre_launch_nfa_exact_entries(sc->use_sa ? 1 : 0, sc->ntab, sc->satab, sc->geom, sc->d_nsum, sc->d_lo,
-                                                         sc->d_nmat, sc->d_belief, sc->d_bvalid, stream));
-                sc->exact_passes++;
-            }
-        }
-        SRE_HIP_TRY(nfa_launch_scan(sc, sc->d_lo, sc->d_belief, sc->d_bvalid, stream));
-        if (nfa_finish(sc, sc->d_lo, stream) != 0) return -1;
+        if (nfa_fixup_round(sc, stream) != 0) return -1;
     }
     return 0;
 hip_failed:
@@ -1838,7 +1855,16 @@ struct sre_hip_streams_s {
     uint64_t             *d_idx;        /* sre_hip_streams_reset */
     size_t                idx_cap;
     int                   fixups, launches;
+    /* the bit-parallel NFA tier (sre_hip_streams_create_engine): rows of 1 + W words, sre_streams_nfa.h */
+    int                   engine;       /* SRE_HIP_ENGINE_SCAN or SRE_HIP_ENGINE_NFA */
+    uint32_t              W;            /* 64-bit words of a thread set */
+    sre_streams_nfa_init_t init0;       /* the set of a fresh stream */
+    uint64_t             *d_eset;       /* [n][W] the sets the streams of a call enter with */
+    uint8_t              *d_sflags;     /* [n] SRE_SFLAG_* */
+    int                   exact_passes;
 };
+
+static sre_hip_streams_t *streams_create_on(sre_pool_t *pool, sre_hip_scanner_t *sc, int mode, size_t nstreams);
 
 static void
 streams_release(void *data)
@@ -1853,6 +1879,8 @@ streams_release(void *data)
     if (ss->h_out) (void) hipHostFree(ss->h_out);
     if (ss->d_tailres) (void) hipFree(ss->d_tailres);
     if (ss->d_idx) (void) hipFree(ss->d_idx);
+    if (ss->d_eset) (void) hipFree(ss->d_eset);
+    if (ss->d_sflags) (void) hipFree(ss->d_sflags);
     free(ss);
 }
 
@@ -1873,7 +1901,14 @@ sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog, int mode, size_t n
     /* as the compat path's chunk route: look-ahead programs on the automaton with chunk-boundary twins */
     sre_hip_scanner_t *sc = scanner_create(pool, prog, mode, SRE_HIP_ENGINE_SCAN, prog->lookahead_asserts ? 1 : 0);
     if (sc == NULL) return NULL;
-    if (!sre_hip_scanner_streams(sc)) {
+    return streams_create_on(pool, sc, mode, nstreams);
+}
+
+/* the set around its scanner (table-driven or NFA tier): rows, feed words, records */
+static sre_hip_streams_t *
+streams_create_on(sre_pool_t *pool, sre_hip_scanner_t *sc, int mode, size_t nstreams)
+{
+    if (sc->engine == SRE_HIP_ENGINE_SCAN && !sre_hip_scanner_streams(sc)) {
         fprintf(stderr, "[sregex-hip] stream set: more than %u listed threads or capture slots\n", SRE_STREAM_MAX_THREADS);
         return NULL;
     }
@@ -1881,9 +1916,19 @@ sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog, int mode, size_t n
     if (ss == NULL) return NULL;
     ss->sc = sc;
     ss->n = nstreams;
-    ss->L.nslots = mode == SRE_HIP_THOMPSON ? 0 : sc->tab->h.nslots;
-    ss->L.max_threads = mode == SRE_HIP_THOMPSON ? 0 : sc->tab->h.max_threads;
-    ss->L.row_words = SRE_SROW_HDR + ss->L.nslots * (1 + 2 * ss->L.max_threads);
+    ss->engine = sc->engine;
+    if (sc->engine == SRE_HIP_ENGINE_NFA) {
+        /* the context is the thread set: one flag word and W set words (sre_streams_nfa.h) */
+        ss->W = nfa_words(sc);
+        for (uint32_t w = 0; w < ss->W; w++) {
+            ss->init0.w[w] = sc->wide_kernel ? sc->wtab.init[0][w] : sc->use_sa ? sc->satab.init[0] : sc->ntab.init[0];
+        }
+        ss->L.row_words = 1 + ss->W;
+    } else {
+        ss->L.nslots = mode == SRE_HIP_THOMPSON ? 0 : sc->tab->h.nslots;
+        ss->L.max_threads = mode == SRE_HIP_THOMPSON ? 0 : sc->tab->h.max_threads;
+        ss->L.row_words = SRE_SROW_HDR + ss->L.nslots * (1 + 2 * ss->L.max_threads);
+    }
     ss->L.ovec_slots = sc->ovec_slots;
     ss->L.rec_slots = SRE_SREC_HDR + sc->ovec_slots;
     ss->rows_bytes = nstreams * ss->L.row_words * sizeof(int64_t);
@@ -1893,14 +1938,19 @@ sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog, int mode, size_t n
         SRE_HIP_TRY(hipMemset(ss->d_rows, 0, ss->rows_bytes));
         SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_feed), nstreams * sizeof(sre_streams_feed_t)));
         SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ss->h_feed), nstreams * sizeof(sre_streams_feed_t), 0));
-        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_sentry), nstreams * sizeof(uint32_t)));
+        if (ss->engine == SRE_HIP_ENGINE_NFA) {
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_eset), nstreams * ss->W * sizeof(uint64_t)));
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_sflags), nstreams));
+        } else {
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_sentry), nstreams * sizeof(uint32_t)));
+        }
         SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_out), out_bytes));
         SRE_HIP_TRY(hipMemset(ss->d_out, 0, out_bytes));
         SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ss->h_out), out_bytes, 0));
-        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_tailres), SRE_STREAMS_TAIL_GRID * sizeof(sre_stream_result_t)));
+        if (ss->engine == SRE_HIP_ENGINE_SCAN) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_tailres), SRE_STREAMS_TAIL_GRID * sizeof(sre_stream_result_t)));
         if (sc->d_linfo == NULL) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_linfo), sizeof(sre_lines_info_t)));
         if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
-        if (!sc->dfa->rekind.empty()) {
+        if (ss->engine == SRE_HIP_ENGINE_SCAN && !sc->dfa->rekind.empty()) {
             std::vector<uint8_t> rk(sc->dfa->rekind.size());
             for (size_t i = 0; i < rk.size(); i++) rk[i] = (uint8_t) sc->dfa->rekind[i];
             SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ss->d_rekind), rk.size()));
@@ -1912,6 +1962,53 @@ sre_hip_streams_create(sre_pool_t *pool, sre_program_t *prog, int mode, size_t n
 hip_failed:
     streams_release(ss);
     return NULL;
+}
+
+extern "C" SRE_API sre_hip_streams_t *
+sre_hip_streams_create_engine(sre_pool_t *pool, sre_program_t *prog, int mode, int engine, size_t nstreams)
+{
+    if (engine == SRE_HIP_ENGINE_SCAN) return sre_hip_streams_create(pool, prog, mode, nstreams);
+    if (pool == NULL || prog == NULL || nstreams == 0 || nstreams > (size_t) 1 << 30) return NULL;
+    if (engine != SRE_HIP_ENGINE_AUTO && engine != SRE_HIP_ENGINE_NFA) {
+        fprintf(stderr, "[sregex-hip] stream set: engine must be SRE_HIP_ENGINE_AUTO, _SCAN or _NFA\n");
+        return NULL;
+    }
+    /* The NFA tier feeds Thompson streams of programs without look-ahead assertions: there the context
+     * is the thread set.  A first match needs the clean position in front of the event for its exact
+     * window, and that position may lie in a chunk that is gone. */
+    const bool nfa_ok = mode == SRE_HIP_THOMPSON && !prog->lookahead_asserts;
+    if (!nfa_ok) {
+        if (engine == SRE_HIP_ENGINE_AUTO) return sre_hip_streams_create(pool, prog, mode, nstreams);
+        fprintf(stderr, "[sregex-hip] stream set: the NFA tier feeds chunks in mode SRE_HIP_THOMPSON to programs without look-ahead assertions only\n");
+        return NULL;
+    }
+    if (sre_hip_ready() != 0) return NULL;
+    /* (AUTO: the table-driven scanner when it admits the program, else the NFA tier; no look-ahead, so no chunk twins) */
+    sre_hip_scanner_t *sc = scanner_create(pool, prog, mode, engine, 0);
+    if (sc == NULL) return NULL;
+    if (sc->engine != SRE_HIP_ENGINE_SCAN && sc->engine != SRE_HIP_ENGINE_NFA) {
+        fprintf(stderr, "[sregex-hip] stream set: neither the table-driven scanner nor the NFA tier admits the program\n");
+        return NULL;
+    }
+    return streams_create_on(pool, sc, mode, nstreams);
+}
+
+extern "C" SRE_API int
+sre_hip_streams_engine(sre_hip_streams_t *ss)
+{
+    return ss->engine;
+}
+
+extern "C" SRE_API int
+sre_hip_streams_nfa_bits(sre_hip_streams_t *ss)
+{
+    return ss->engine == SRE_HIP_ENGINE_NFA ? sre_hip_scanner_nfa_bits(ss->sc) : 0;
+}
+
+extern "C" SRE_API int
+sre_hip_streams_last_exact_passes(sre_hip_streams_t *ss)
+{
+    return ss->exact_passes;
 }
 
 extern "C" SRE_API size_t
@@ -1964,6 +2061,98 @@ hip_failed:
     return -1;
 }
 
+/* The call on the NFA tier: prologue (geometry, entry sets, the records of streams that need no byte),
+ * set pass + chain check, tail; fix-up rounds — the exact-entry fallback among them — run from device
+ * counters: per round the host reads one word, never the streams' status blocks. */
+static int
+streams_feed_nfa(sre_hip_streams_t *ss, sre_int_t *results, hipStream_t stream)
+{
+    sre_hip_scanner_t  *sc = ss->sc;
+    const size_t        n = ss->n;
+    sre_streams_info_t *d_info = reinterpret_cast<sre_streams_info_t *>(ss->d_out);
+    const volatile sre_streams_info_t *h_info = reinterpret_cast<sre_streams_info_t *>(ss->h_out);
+    int64_t            *d_recs = reinterpret_cast<int64_t *>(ss->d_out + sizeof(sre_streams_info_t));
+    const size_t        out_bytes = sizeof(sre_streams_info_t) + n * ss->L.rec_slots * sizeof(int64_t);
+    {
+        uint64_t seg_fixed = scan_seg_knobs(sc);
+        if (seg_fixed == 0) {
+            /* (the set kernels take any multiple of the 64-byte round: tests cut streams into segments
+             * that are shorter than the warm-up) */
+            const char *e = getenv("SRE_HIP_SEG_BYTES");
+            if (e && atoi(e) > 0 && atoi(e) % 64 == 0) seg_fixed = (uint64_t) atoi(e);
+        }
+        const uint64_t resident = scan_resident(sc);
+        SRE_HIP_TRY(sre_launch_upload_words(reinterpret_cast<const uint64_t *>(ss->h_feed),
+                                            reinterpret_cast<uint64_t *>(ss->d_feed), (uint32_t) (3 * n), stream));
+        SRE_HIP_TRY(sre_launch_streams_nfa_prologue(ss->d_feed, (uint32_t) n, ss->d_rows, ss->W, ss->init0, ss->L.rec_slots, seg_fixed,
+                                                    resident, sc->seg_cap_env ? sc->seg_cap_env : 40960,
+                                                    reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens, sc->d_seg_first,
+                                                    ss->d_sflags, ss->d_eset, d_recs, d_info, stream));
+        /* the host sizes the call's buffers and grids from two of its words */
+        SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, sizeof(sre_streams_info_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        ss->launches += 3;
+    }
+    if (h_info->nsegs != 0) {
+        if (nfa_buffers(sc, h_info->nsegs) != 0) return -1;
+        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
+        sc->geom.lens = sc->d_lens;
+        sc->geom.seg_first = sc->d_seg_first;
+        sc->geom.nstreams = (uint32_t) n;
+        sc->geom.seg_bytes = (uint32_t) h_info->seg;
+        sc->geom.nsegs = h_info->nsegs;
+        sc->geom.init_variant = 0;
+        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
+        sc->geom.entry_state = 0;
+        sc->geom.one_ptr = NULL;
+        sc->geom.one_len = 0;
+        sc->geom.digest = NULL;
+        sc->geom.sentry = NULL;
+        sc->geom.sflags = ss->d_sflags;
+        sc->geom_one = 0;
+        sc->d_eset = ss->d_eset;
+        SRE_HIP_TRY(nfa_launch_scan(sc, NULL, NULL, NULL, stream));
+        if (nfa_finish(sc, NULL, stream) != 0) goto hip_failed;
+        SRE_HIP_TRY(sre_launch_streams_nfa_tail(ss->d_feed, (uint32_t) n, ss->d_rows, ss->W, sc->d_seg_first, sc->d_nstatus, sc->d_nsum,
+                                                sc->wide_kernel ? sc->d_wsets : NULL, ss->L.rec_slots, d_recs, d_info, 0, stream));
+        ss->launches += 1 + 3 + 1;
+    }
+    SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    ss->launches += 1;
+    if (h_info->unsettled != 0) {
+        /* speculative entry sets of some stream's lanes were wrong: fix-up rounds over the streams that
+         * are not verified, their work list and its length made on the device */
+        for (;;) {
+            SRE_HIP_TRY(sre_launch_streams_nfa_lo(sc->d_nstatus, (uint32_t) n, sc->d_lo, &sc->d_linfo->pending, stream));
+            SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            if (sc->h_linfo->pending == 0) break;
+            if (nfa_fixup_round(sc, stream) != 0) goto hip_failed;
+        }
+        SRE_HIP_TRY(hipMemsetAsync(&d_info->unsettled, 0, sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_streams_nfa_tail(ss->d_feed, (uint32_t) n, ss->d_rows, ss->W, sc->d_seg_first, sc->d_nstatus, sc->d_nsum,
+                                                sc->wide_kernel ? sc->d_wsets : NULL, ss->L.rec_slots, d_recs, d_info, 1, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        ss->fixups = sc->fixup_rounds;
+        ss->exact_passes = sc->exact_passes;
+        ss->launches += 3;
+        if (h_info->unsettled != 0) {
+            fprintf(stderr, "[sregex-hip] stream set: %llu streams did not settle\n", (unsigned long long) h_info->unsettled);
+            goto hip_failed;
+        }
+    }
+    sc->geom.sflags = NULL;
+    sc->d_eset = NULL;
+    memcpy(results, ss->h_out + sizeof(sre_streams_info_t), n * ss->L.rec_slots * sizeof(int64_t));
+    return 0;
+hip_failed:
+    sc->geom.sflags = NULL;
+    sc->d_eset = NULL;
+    return -1;
+}
+
 /* One exec() per fed stream.  The host fills three words a stream; everything else of the call —
  * which streams take part, the geometry, the entry states, the tails, the records — happens on
  * the device in a number of launches and copies that does not depend on the size of the set. */
@@ -1981,6 +2170,7 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
     const size_t        out_bytes = sizeof(sre_streams_info_t) + n * ss->L.rec_slots * sizeof(int64_t);
     ss->fixups = 0;
     ss->launches = 0;
+    ss->exact_passes = 0;
     sc->last_lines = false;
     sc->last_n = 0;
     sc->fixup_rounds = 0;
@@ -1993,6 +2183,7 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
         ss->h_feed[i].flags = d_chunks[i] ? (SRE_SFEED_FED | (eof[i] ? SRE_SFEED_EOF : 0u)) : 0u;
     }
     if (scanner_reserve(sc, n) != 0) return -1;
+    if (ss->engine == SRE_HIP_ENGINE_NFA) return streams_feed_nfa(ss, results, stream);
     {
         const uint64_t seg_fixed = scan_seg_knobs(sc);
         const uint64_t resident = scan_resident(sc);
@@ -2049,6 +2240,7 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
         SRE_HIP_TRY(hipMemcpyAsync(ss->h_out, ss->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
         ss->fixups = sc->fixup_rounds;
+        ss->exact_passes = sc->exact_passes;
         ss->launches += 3;
         if (h_info->unsettled != 0) {
             fprintf(stderr, "[sregex-hip] stream set: %llu streams did not settle\n", (unsigned long long) h_info->unsettled);

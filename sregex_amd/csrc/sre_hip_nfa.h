@@ -64,15 +64,17 @@ const char *sre_nfa_kernel_name(int mode, uint32_t nslices, int la, char *buf, s
 /* pass over segments [lo[s], nseg_s) of every stream (lo == NULL: all, speculative
  * entry sets from a 128-byte warm-up).  With lo: segment lo[s] enters with
  * belief[g] (its verified predecessor's exit set), later ones with belief[g] where
- * bvalid[g], i.e. with what the previous round's lane in front of them ended in. */
+ * bvalid[g], i.e. with what the previous round's lane in front of them ended in.
+ * d_entry: one entry set per stream (stream sets: the set a stream's earlier chunks left; segment 0
+ * and a warm-up that starts at offset 0 enter with it), NULL: the tables' initial sets. */
 hipError_t sre_launch_nfa_scan(int mode, sre_nfa_tables_t tab, sre_scan_geom_t geom,
     sre_nfa_summary_t *d_sum, const int64_t *d_lo, const uint64_t *d_belief,
-    const uint8_t *d_bvalid, hipStream_t stream);
+    const uint8_t *d_bvalid, const uint64_t *d_entry, hipStream_t stream);
 /* the same pass by the shift-and kernel (sre_k_nfa_sa): summaries, beliefs and the chain check are
  * shared, the masks are in the numbering of the shift-and form */
 hipError_t sre_launch_nfa_sa_scan(sre_nfa_sa_tables_t tab, sre_scan_geom_t geom,
     sre_nfa_summary_t *d_sum, const int64_t *d_lo, const uint64_t *d_belief,
-    const uint8_t *d_bvalid, hipStream_t stream);
+    const uint8_t *d_bvalid, const uint64_t *d_entry, hipStream_t stream);
 /* exact entry sets for the segments [lo[s], ...) of every unsettled stream (a program that never forgets):
  * the segments' singleton exit sets (d_mat: 64 x uint64 per segment of the batch), then the recurrence that
  * leaves every lane's exact entry set in d_belief / d_bvalid — the next pass is exact (sre_hip_nfa.hip) */

@@ -101,7 +101,7 @@ template <int MODE, int NSLICE, bool LA>
 __global__ __launch_bounds__(SRE_SCAN_BLOCK) void
 sre_k_nfa(sre_nfa_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__restrict__ sum,
           const int64_t *__restrict__ lo, const uint64_t *__restrict__ belief,
-          const uint8_t *__restrict__ bvalid)
+          const uint8_t *__restrict__ bvalid, const uint64_t *__restrict__ eset)
 {
     typedef typename std::conditional<(NSLICE <= 4), uint32_t, uint64_t>::type M;
     typedef AccEntry<M, LA> Acc;
@@ -177,7 +177,8 @@ sre_k_nfa(sre_nfa_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__restrict__
         last_seg = (k + 1 == geom_first(G, sidx + 1) - geom_first(G, sidx));
         if (seg_b > n) seg_b = n;
         if (k == 0) {
-            S = (M) T.init[v_init];
+            /* eset: the stream's own entry set (a stream set's carried context), else the batch's */
+            S = eset != nullptr ? (M) eset[sidx] : (M) T.init[v_init];
             last_clean = 0;                     /* the search starts here */
             clean_mode = (int32_t) SRE_SFLAG_MODE(sfl);
         } else if (lo != nullptr && ((int64_t) k == lo[sidx] || bvalid[g])) {
@@ -186,8 +187,9 @@ sre_k_nfa(sre_nfa_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__restrict__
             S = (M) belief[g];
         } else {
             warm = true;
-            /* a search that is (re)started in the middle of a stream: ^ false */
-            S = (M) T.init[seg_a <= WARM ? v_init : 2];
+            /* a search that is (re)started in the middle of a stream: ^ false (a warm-up from offset 0
+             * starts as segment 0 does: with a carried entry set it is exact) */
+            S = seg_a <= WARM && eset != nullptr ? (M) eset[sidx] : (M) T.init[seg_a <= WARM ? v_init : 2];
         }
         s_in = S;
         mine.addr = (uint64_t) reinterpret_cast<uintptr_t>(data) + (uint64_t) (seg_a - WARM);
@@ -390,7 +392,7 @@ template <bool W64, bool CARRY, bool MASKED, bool EVACC, int NLUT, bool LA>
 __global__ __launch_bounds__(SRE_SCAN_BLOCK, (W64 || LA ? 5 : 6)) void
 sre_k_nfa_sa(sre_nfa_sa_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__restrict__ sum,
              const int64_t *__restrict__ lo, const uint64_t *__restrict__ belief,
-             const uint8_t *__restrict__ bvalid)
+             const uint8_t *__restrict__ bvalid, const uint64_t *__restrict__ eset)
 {
     typedef typename std::conditional<W64, uint64_t, uint32_t>::type E; /* a table entry */
     constexpr int      TILE = SRE_SCAN_ROUND;
@@ -474,14 +476,14 @@ sre_k_nfa_sa(sre_nfa_sa_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__rest
         if (seg_b > n) seg_b = n;
         uint64_t S;
         if (k == 0) {
-            S = T.init[v_init];
+            S = eset != nullptr ? eset[sidx] : T.init[v_init];       /* (eset: see sre_k_nfa) */
             last_clean = 0;                     /* the search starts here */
             clean_mode = (int32_t) SRE_SFLAG_MODE(sfl);
         } else if (lo != nullptr && ((int64_t) k == lo[sidx] || bvalid[g])) {
             S = belief[g];
         } else {
             warm = true;
-            S = T.init[seg_a <= WARM ? v_init : 2];
+            S = seg_a <= WARM && eset != nullptr ? eset[sidx] : T.init[seg_a <= WARM ? v_init : 2];
         }
         s_in = S;
         s_lo = lo32(S);
@@ -1032,7 +1034,7 @@ sre_launch_nfa_exact_entries(int use_sa, sre_nfa_tables_t ptab, sre_nfa_sa_table
 }
 
 typedef void (*nfa_kernel_t)(sre_nfa_tables_t, sre_scan_geom_t, sre_nfa_summary_t *, const int64_t *,
-                             const uint64_t *, const uint8_t *);
+                             const uint64_t *, const uint8_t *, const uint64_t *);
 
 template <int MODE, bool LA>
 nfa_kernel_t
@@ -1101,7 +1103,7 @@ sre_nfa_blocks_per_cu(int mode, uint32_t nslices, int la)
 extern "C" hipError_t
 sre_launch_nfa_scan(int mode, sre_nfa_tables_t tab, sre_scan_geom_t geom, sre_nfa_summary_t *d_sum,
                     const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid,
-                    hipStream_t stream)
+                    const uint64_t *d_entry, hipStream_t stream)
 {
     if (geom.nsegs == 0) return hipSuccess;
     const uint32_t grid = (uint32_t) ((geom.nsegs + SRE_SCAN_BLOCK - 1) / SRE_SCAN_BLOCK);
@@ -1114,7 +1116,7 @@ sre_launch_nfa_scan(int mode, sre_nfa_tables_t tab, sre_scan_geom_t geom, sre_nf
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SRE_SCAN_BLOCK), nfa_dynamic_lds(), stream, tab, geom, d_sum, d_lo,
-                       d_belief, d_bvalid);
+                       d_belief, d_bvalid, d_entry);
     return hipGetLastError();
 }
 
@@ -1231,7 +1233,8 @@ sre_nfa_sa_blocks_per_cu(const sre_nfa_sa_tables_t *t)
 
 extern "C" hipError_t
 sre_launch_nfa_sa_scan(sre_nfa_sa_tables_t tab, sre_scan_geom_t geom, sre_nfa_summary_t *d_sum,
-                       const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid, hipStream_t stream)
+                       const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid, const uint64_t *d_entry,
+                       hipStream_t stream)
 {
     if (geom.nsegs == 0) return hipSuccess;
     const uint32_t grid = (uint32_t) ((geom.nsegs + SRE_SCAN_BLOCK - 1) / SRE_SCAN_BLOCK);
@@ -1241,6 +1244,6 @@ sre_launch_nfa_sa_scan(sre_nfa_sa_tables_t tab, sre_scan_geom_t geom, sre_nfa_su
         hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) nfa_sa_dynamic_lds(tab));
         if (e != hipSuccess) return e;
     }
-    void *args[] = {&tab, &geom, &d_sum, &d_lo, &d_belief, &d_bvalid};
+    void *args[] = {&tab, &geom, &d_sum, &d_lo, &d_belief, &d_bvalid, &d_entry};
     return hipLaunchKernel(kern, dim3(grid), dim3(SRE_SCAN_BLOCK), args, nfa_sa_dynamic_lds(tab), stream);
 }

@@ -29,9 +29,11 @@ size_t sre_nfa_wide_kernel_lds(const sre_nfa_wide_tables_t *t);
 int sre_nfa_wide_blocks_per_cu(const sre_nfa_wide_tables_t *t);
 const char *sre_nfa_wide_kernel_name(const sre_nfa_wide_tables_t *t, char *buf, size_t n);
 /* one pass of sre_k_nfa_wide over segments [lo[s], ...) of every stream (lo == NULL: all, speculative entry
- * sets from a 128-byte warm-up); d_sets: [nsegs][2][W] entry and exit sets, d_belief: [nsegs][W] */
+ * sets from a 128-byte warm-up); d_sets: [nsegs][2][W] entry and exit sets, d_belief: [nsegs][W];
+ * d_entry: [nstreams][W] per-stream entry sets (stream sets), NULL: the tables' initial sets */
 hipError_t sre_launch_nfa_wide_scan(sre_nfa_wide_tables_t tab, sre_scan_geom_t geom, sre_nfa_summary_t *d_sum,
-    uint64_t *d_sets, const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid, hipStream_t stream);
+    uint64_t *d_sets, const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid, const uint64_t *d_entry,
+    hipStream_t stream);
 /* the chain check on W-word sets, then the 64-bit tier's clean-position reduction and status / records */
 hipError_t sre_launch_nfa_wide_verify(int mode, uint32_t W, sre_scan_geom_t geom, const sre_nfa_summary_t *d_sum,
     const uint64_t *d_sets, void *d_acc, sre_nfa_status_t *d_status, uint64_t *d_belief, uint8_t *d_bvalid,

@@ -50,7 +50,7 @@ template <int W, int NL, bool LA>
 __global__ __launch_bounds__(SRE_SCAN_BLOCK) void
 sre_k_nfa_wide(sre_nfa_wide_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__restrict__ sum,
                uint64_t *__restrict__ sets, const int64_t *__restrict__ lo, const uint64_t *__restrict__ belief,
-               const uint8_t *__restrict__ bvalid)
+               const uint8_t *__restrict__ bvalid, const uint64_t *__restrict__ eset)
 {
     constexpr int      TILE = SRE_SCAN_ROUND;
     constexpr int      WARM = SRE_SCAN_LINE;
@@ -131,8 +131,9 @@ sre_k_nfa_wide(sre_nfa_wide_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__
         last_seg = (k + 1 == geom_first(G, sidx + 1) - geom_first(G, sidx));
         if (seg_b > n) seg_b = n;
         if (k == 0) {
+            /* eset: the stream's own entry set [nstreams][W] (a stream set's carried context), else the batch's */
 #pragma unroll
-            for (int i = 0; i < W; i++) S[i] = T.init[v_init][i];
+            for (int i = 0; i < W; i++) S[i] = eset != nullptr ? eset[(size_t) sidx * W + i] : T.init[v_init][i];
             last_clean = 0;
             clean_mode = (int32_t) SRE_SFLAG_MODE(sfl);
         } else if (lo != nullptr && ((int64_t) k == lo[sidx] || bvalid[g])) {
@@ -140,9 +141,10 @@ sre_k_nfa_wide(sre_nfa_wide_tables_t T, sre_scan_geom_t G, sre_nfa_summary_t *__
             for (int i = 0; i < W; i++) S[i] = belief[g * W + i];
         } else {
             warm = true;
+            /* (a warm-up from offset 0 starts as segment 0 does: with a carried entry set it is exact) */
             const uint32_t v = seg_a <= WARM ? v_init : 2u;
 #pragma unroll
-            for (int i = 0; i < W; i++) S[i] = T.init[v][i];
+            for (int i = 0; i < W; i++) S[i] = seg_a <= WARM && eset != nullptr ? eset[(size_t) sidx * W + i] : T.init[v][i];
         }
 #pragma unroll
         for (int i = 0; i < W; i++) s_in[i] = S[i];
@@ -551,7 +553,7 @@ sre_k_nfa_wide_exact_entries(sre_scan_geom_t G, const sre_nfa_summary_t *__restr
 }
 
 typedef void (*nfaw_kernel_t)(sre_nfa_wide_tables_t, sre_scan_geom_t, sre_nfa_summary_t *, uint64_t *, const int64_t *,
-                              const uint64_t *, const uint8_t *);
+                              const uint64_t *, const uint8_t *, const uint64_t *);
 
 template <int W, bool LA>
 nfaw_kernel_t
@@ -610,7 +612,8 @@ sre_nfa_wide_blocks_per_cu(const sre_nfa_wide_tables_t *t)
 
 extern "C" hipError_t
 sre_launch_nfa_wide_scan(sre_nfa_wide_tables_t tab, sre_scan_geom_t geom, sre_nfa_summary_t *d_sum, uint64_t *d_sets,
-                         const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid, hipStream_t stream)
+                         const int64_t *d_lo, const uint64_t *d_belief, const uint8_t *d_bvalid, const uint64_t *d_entry,
+                         hipStream_t stream)
 {
     if (geom.nsegs == 0) return hipSuccess;
     const uint32_t grid = (uint32_t) ((geom.nsegs + SRE_SCAN_BLOCK - 1) / SRE_SCAN_BLOCK);
@@ -621,7 +624,7 @@ sre_launch_nfa_wide_scan(sre_nfa_wide_tables_t tab, sre_scan_geom_t geom, sre_nf
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(SRE_SCAN_BLOCK), lds, stream, tab, geom, d_sum, d_sets, d_lo, d_belief, d_bvalid);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(SRE_SCAN_BLOCK), lds, stream, tab, geom, d_sum, d_sets, d_lo, d_belief, d_bvalid, d_entry);
     return hipGetLastError();
 }
 

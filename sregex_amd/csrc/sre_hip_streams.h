@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sre_hip_scan.h"
+#include "sre_hip_nfa.h"
 
 /*
  * One context row, in 64-bit words — what sre_stream_ctx_t holds for the compat path plus what
@@ -91,6 +92,26 @@ hipError_t sre_launch_streams_tail(const sre_scan_tables_t *d_tab, sre_scan_tabl
     const sre_seg_summary_t *d_sum, const sre_stream_status_t *d_status, uint16_t *d_scratch, int64_t *d_rows,
     sre_streams_layout_t layout, sre_stream_result_t *d_tailres, int64_t *d_recs, sre_streams_info_t *d_info,
     uint32_t grid, int only_unsettled, hipStream_t stream);
+
+/* ---- the bit-parallel NFA tier (sre_hip_streams_create_engine): rows of 1 + W words, sre_streams_nfa.h */
+typedef struct { uint64_t w[4]; } sre_streams_nfa_init_t;      /* the initial set of a fresh stream */
+/* As sre_launch_streams_prologue: ptrs / lens / seg_first of the streams that scan bytes in this call
+ * (sre_streams_nfa_scans), d_sflags (SRE_SFLAG_NO_EOF unless the stream's chunk is its last), d_eset
+ * [n][W]: the set every stream enters with; the records — and rows — of the streams the call
+ * decides without a byte; *d_info */
+hipError_t sre_launch_streams_nfa_prologue(const sre_streams_feed_t *d_feed, uint32_t n, int64_t *d_rows, uint32_t W,
+    sre_streams_nfa_init_t init0, uint32_t rec_slots, uint64_t seg_fixed, uint64_t resident, uint64_t seg_cap,
+    const uint8_t **d_ptrs, uint64_t *d_lens, uint64_t *d_seg_first, uint8_t *d_sflags, uint64_t *d_eset,
+    int64_t *d_recs, sre_streams_info_t *d_info, hipStream_t stream);
+/* d_lo[s] = first wrong segment of stream s or -1 (verified), *d_pending = streams that are not */
+hipError_t sre_launch_streams_nfa_lo(const sre_nfa_status_t *d_status, uint32_t n, int64_t *d_lo, uint64_t *d_pending,
+    hipStream_t stream);
+/* the tail of every stream that scanned (only_unsettled: of those the first tail left for the fix-up
+ * rounds): row, record, d_info->unsettled; d_wsets: the wide kernel's [nsegs][2][W] sets, NULL: W == 1
+ * and the exit sets are d_sum[].s_out */
+hipError_t sre_launch_streams_nfa_tail(const sre_streams_feed_t *d_feed, uint32_t n, int64_t *d_rows, uint32_t W,
+    const uint64_t *d_seg_first, const sre_nfa_status_t *d_status, const sre_nfa_summary_t *d_sum, const uint64_t *d_wsets,
+    uint32_t rec_slots, int64_t *d_recs, sre_streams_info_t *d_info, int only_unsettled, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,10 @@ synchronous calls.  Prints one JSON document (--out also writes it).
     python tools/streams_probe.py [--reps 5] [--max-bytes N] [--out FILE]
     python tools/streams_probe.py --one 1024x1048576      # that cell of the headline program only
                                                           # (the run to put under rocprofv3)
+    python tools/streams_probe.py --engine nfa [--out profiles/streams_nfa_rate.json]
+        the same shapes on the NFA tier (StreamSet(..., engine=ENGINE_NFA), Thompson): three programs the
+        step automaton declines, at 64, 64 and 128 bits; the yardstick is sre_hip_scan_batch with
+        SRE_HIP_ENGINE_NFA on the same chunks (no compat column: chunks of such programs go to the exact VM)
 """
 import argparse
 import ctypes
@@ -34,6 +38,11 @@ import sregex_amd as S
 PROGRAMS = {
     "headline": [rb"[a-z]+@[a-z]+\.[a-z]+"],
     "configs2_12_regexes": [b"a", b"ab", b"c", b"a(bc)", b"e(f)", b"gh", b"A", b"b", b"BLAH", rb"\s+", b"abcd", b"bc"],
+}
+NFA_PROGRAMS = {
+    "nfa_a7": [rb"(?:a|b)*a(?:a|b){7}@"],
+    "nfa_a20c30": [rb"(?:a|b)*a[ab]{20}c[^x]{30}@"],
+    "nfa_wide_a45c45": [rb"[ab]*a[ab]{45}c[^x]{45}@"],
 }
 STREAMS = [1, 64, 1024, 16384]
 CHUNKS = [16 << 10, 256 << 10, 1 << 20, 16 << 20]
@@ -65,12 +74,16 @@ def compat_rate(pool, prog, ncaps, chunk):
     return rate
 
 
-def run_cell(lib, pool, prog, big, n, chunk, reps, yardstick=True):
+def run_cell(lib, pool, prog, big, n, chunk, reps, yardstick=True, nfa=False):
     ptrs = (ctypes.c_void_p * n)(*[big.ptr + i * chunk for i in range(n)])
     lens = (ctypes.c_size_t * n)(*([chunk] * n))
     eofs = (ctypes.c_ubyte * n)(*([0] * n))
-    ss = S.StreamSet(pool, prog, S.HIP_PIKE_FIRST, n)
-    sc = S.Scanner(pool, prog, S.HIP_PIKE_FIRST)
+    if nfa:
+        ss = S.StreamSet(pool, prog, S.HIP_THOMPSON, n, engine=S.ENGINE_NFA)
+        sc = S.Scanner(pool, prog, S.HIP_THOMPSON, S.ENGINE_NFA)
+    else:
+        ss = S.StreamSet(pool, prog, S.HIP_PIKE_FIRST, n)
+        sc = S.Scanner(pool, prog, S.HIP_PIKE_FIRST)
     out_b = (ctypes.c_ssize_t * (n * sc.slots))()
     everyone = list(range(n))
     t_first, t_next, t_batch = [], [], []
@@ -101,6 +114,7 @@ def run_cell(lib, pool, prog, big, n, chunk, reps, yardstick=True):
         row["batch_GBps"] = nbytes / med(t_batch) / 1e9
         row["batch_us"] = med(t_batch) * 1e6
         row["set_first_over_batch"] = med(t_first) / med(t_batch)
+        row["set_next_over_batch"] = med(t_next) / med(t_batch)
     return row
 
 
@@ -110,7 +124,9 @@ def main():
     ap.add_argument("--max-bytes", type=int, default=16 << 30)
     ap.add_argument("--one", default=None, help="STREAMSxCHUNK: that cell of the headline program only, no yardsticks")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--engine", default="scan", choices=["scan", "nfa"], help="nfa: the NFA tier's programs and yardstick")
     args = ap.parse_args()
+    nfa = args.engine == "nfa"
     lib = S.load_library()
     assert lib.sre_hip_device_count() >= 1, "no HIP device"
     try:
@@ -119,7 +135,9 @@ def main():
         commit = None
     doc = {"tool": "tools/streams_probe.py", "commit": commit, "reps": args.reps,
            "timing": "host clock around each synchronous call; median of reps after a warm-up round; set and batched API alternating",
-           "kernels": ["sre_k_streams_prologue", "sre_k_scan<1, BITS>", "sre_k_verify_a/b/b2/c", "sre_k_streams_tail"],
+           "kernels": (["sre_k_streams_nfa_prologue", "sre_k_nfa / sre_k_nfa_sa / sre_k_nfa_wide", "sre_k_nfa_verify_a/b/c",
+                        "sre_k_streams_nfa_tail"] if nfa else
+                       ["sre_k_streams_prologue", "sre_k_scan<1, BITS>", "sre_k_verify_a/b/b2/c", "sre_k_streams_tail"]),
            "results": {}}
     cells = [(n, c) for n in STREAMS for c in CHUNKS if n * c <= args.max_bytes]
     if args.one:
@@ -129,20 +147,22 @@ def main():
     big = S.DeviceBuffer(biggest)
     assert lib.sre_hip_gen_data(big.ptr, biggest, b"", 0, None) == 0
     assert lib.sre_hip_synchronize(None) == 0
-    for name, pats in PROGRAMS.items():
-        if args.one and name != "headline":
+    for name, pats in (NFA_PROGRAMS if nfa else PROGRAMS).items():
+        if args.one and name not in ("headline", "nfa_a7"):
             continue
         with S.Pool() as pool:
             re = S.parse(pool, pats)
             prog = S.compile(pool, re)
-            sc = S.Scanner(pool, prog, S.HIP_PIKE_FIRST)
+            sc = S.Scanner(pool, prog, S.HIP_THOMPSON, S.ENGINE_NFA) if nfa else S.Scanner(pool, prog, S.HIP_PIKE_FIRST)
             res = {"scan_kernel": sc.kernel_name, "cells": [], "compat_GBps": {}}
-            if not args.one:
+            if nfa:
+                res["nfa_bits"] = sc.nfa_bits
+            if not args.one and not nfa:
                 for c in CHUNKS:
                     res["compat_GBps"][str(c)] = compat_rate(pool, prog, re.ncaps, c)
                     print(json.dumps({name: {"compat_chunk": c, "GBps": res["compat_GBps"][str(c)]}}), flush=True)
             for n, c in cells:
-                row = run_cell(lib, pool, prog, big, n, c, args.reps, yardstick=not args.one)
+                row = run_cell(lib, pool, prog, big, n, c, args.reps, yardstick=not args.one, nfa=nfa)
                 if str(c) in res["compat_GBps"]:
                     row["set_first_over_compat_rate"] = row["set_first_GBps"] / res["compat_GBps"][str(c)]
                 res["cells"].append(row)
