@@ -212,8 +212,13 @@ enum { SRE_HIP_LINES_ALL = 1 };   /* report every line, not only the lines with 
  * Returns 0 on success, -1 on bad arguments or failure.
  *
  * The table-driven scanner does the whole call on the device (split, per-line geometry,
- * fix-up rounds, compaction of the rows); the NFA tier and the exact VM take each batch of
- * lines through sre_hip_scan_enqueue / sre_hip_scan_results.  Line mode ignores
+ * fix-up rounds, compaction of the rows), and so do Thompson and first-match scanners of the
+ * bit-parallel NFA tier: there short lines (at most SRE_HIP_LINES_SHORT_MAX bytes, environment,
+ * read on every call, default 512; 0 turns it off; 64-bit forms only) go one to a lane through
+ * a kernel of their own and the longer ones through the tier's set pass.  Find-all counting on
+ * the tier and the exact VM take each batch of lines through sre_hip_scan_enqueue /
+ * sre_hip_scan_results on the host, and SRE_HIP_LINES_NFA_HOST=1 (environment, read on every
+ * call) keeps every scanner of the tier on that route.  Line mode ignores
  * sre_hip_scanner_set_tail_stream.  A call of either kind replaces the scanner's last
  * call: after a line-mode call sre_hip_scan_results returns -1, and the diagnostics
  * (last_fixups, last_exact_passes, last_lineage_passes: sums over the call's batches;
@@ -226,6 +231,12 @@ SRE_API int sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t 
 /* diagnostics: internal batches of lines the last sre_hip_scan_lines call ran (0 before the
  * first call) */
 SRE_API int sre_hip_scanner_last_line_batches(sre_hip_scanner_t *sc);
+/* 1 when every batch of the last sre_hip_scan_lines call ran on the device with no per-line
+ * host work (the table-driven scanner; Thompson and first-match scanners of the NFA tier),
+ * else 0; 0 before the first call */
+SRE_API int sre_hip_scanner_last_lines_device(sre_hip_scanner_t *sc);
+/* lines of the last sre_hip_scan_lines call that the NFA tier's short-line kernel took */
+SRE_API size_t sre_hip_scanner_last_short_lines(sre_hip_scanner_t *sc);
 
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 

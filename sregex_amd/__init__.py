@@ -78,6 +78,8 @@ API = {
     "sre_hip_scan_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _pssz, _sz,
                                           ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
+    "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
+    "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
     "sre_hip_streams_create": (_vp, [_vp, _vp, ctypes.c_int, _sz]),
     "sre_hip_streams_create_engine": (_vp, [_vp, _vp, ctypes.c_int, ctypes.c_int, _sz]),
     "sre_hip_streams_engine": (ctypes.c_int, [_vp]),
@@ -404,6 +406,16 @@ class Scanner:
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
+
+    @property
+    def last_lines_device(self):
+        """1 when every batch of the last scan_lines call ran on the device with no per-line host work"""
+        return self.lib.sre_hip_scanner_last_lines_device(self.h)
+
+    @property
+    def last_short_lines(self):
+        """lines of the last scan_lines call that the NFA tier's short-line kernel took"""
+        return self.lib.sre_hip_scanner_last_short_lines(self.h)
 
 
 class StreamSet:

@@ -128,6 +128,9 @@ struct sre_hip_scanner_s {
     bool                      last_lines;       /* the last call was a line-mode call */
     int                       line_batches;     /* of the last line-mode call */
     double                    lines_kernel_ms;  /* ... the sum of its scan kernels, -1 unknown */
+    bool                      lines_device;     /* ... every batch ran on the device, no per-line host work */
+    size_t                    short_lines;      /* ... lines the short-line kernel took (NFA tier) */
+    hipEvent_t                ev_l0, ev_l1;     /* around a batch's short-line kernel */
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -175,6 +178,8 @@ scanner_release(void *data)
     if (sc->ev0) (void) hipEventDestroy(sc->ev0);
     if (sc->ev1) (void) hipEventDestroy(sc->ev1);
     if (sc->ev_done) (void) hipEventDestroy(sc->ev_done);
+    if (sc->ev_l0) (void) hipEventDestroy(sc->ev_l0);
+    if (sc->ev_l1) (void) hipEventDestroy(sc->ev_l1);
     if (sc->d_nsum) (void) hipFree(sc->d_nsum);
     if (sc->d_belief) (void) hipFree(sc->d_belief);
     if (sc->d_bvalid) (void) hipFree(sc->d_bvalid);
@@ -728,7 +733,8 @@ scanner_reserve(sre_hip_scanner_t *sc, size_t n)
     sc->h_status = reinterpret_cast<sre_stream_status_t *>(sc->h_out + record_bytes(sc, n));
     sc->d_nstatus = reinterpret_cast<sre_nfa_status_t *>(sc->d_status);
     sc->h_nstatus = reinterpret_cast<sre_nfa_status_t *>(sc->h_status);
-    if ((sc->engine == SRE_HIP_ENGINE_VM || (sc->engine == SRE_HIP_ENGINE_NFA && sc->mode != SRE_HIP_THOMPSON))
+    /* (the NFA tier's exact window takes contexts only when the program has no wave form: nfa_windows) */
+    if ((sc->engine == SRE_HIP_ENGINE_VM || (sc->engine == SRE_HIP_ENGINE_NFA && sc->mode != SRE_HIP_THOMPSON && sc->d_pwave == NULL))
         && n * sc->ctx_stride > sc->ctx_cap)
     {
         if (sc->d_ctx) (void) hipFree(sc->d_ctx);
@@ -889,12 +895,33 @@ hip_failed:
     return -1;
 }
 
+/* Pike: the exact VM over the window of every stream that is verified and holds an event (d_lo: only
+ * the streams it lists) */
+static int
+nfa_windows(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
+{
+    const uint32_t n = sc->geom.nstreams;
+    if (sc->d_pwave) {
+        SRE_HIP_TRY(sre_launch_pike_window_wave(sc->d_pwave, sc->h_pwave, sc->d_ptrs, sc->d_lens, n, sc->d_records,
+                                                sc->ovec_slots, reinterpret_cast<sre_nfa_window_t *>(sc->d_nstatus), d_lo,
+                                                sc->geom.sflags ? sc->d_creq : NULL, stream));
+    } else {
+        /* (the window kernel zero-fills the context it uses) */
+        SRE_HIP_TRY(sre_launch_pike_window(sc->dp->d_blob, sc->dp->blob_bytes, sc->d_ptrs, sc->d_lens, n, sc->d_ctx, sc->ctx_stride,
+                                           sc->d_records, sc->ovec_slots,
+                                           reinterpret_cast<sre_nfa_window_t *>(sc->d_nstatus), d_lo,
+                                           sc->geom.sflags ? sc->d_creq : NULL, stream));
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
 /* chain check of the set pass and, for Pike, the exact VM over the window of every
  * stream that is verified and holds an event (d_lo: the streams of this fix-up round) */
 static int
 nfa_finish(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
 {
-    const uint32_t n = sc->geom.nstreams;
     /* (the kernels know two modes: find-all counting is a loop of first-match searches) */
     const int kmode = sc->mode == SRE_HIP_THOMPSON ? SRE_HIP_THOMPSON : SRE_HIP_PIKE_FIRST;
     if (sc->wide_kernel) {
@@ -904,19 +931,7 @@ nfa_finish(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
         SRE_HIP_TRY(sre_launch_nfa_verify(kmode, sc->geom, sc->d_nsum, sc->d_nacc, sc->d_nstatus,
                                           sc->d_belief, sc->d_bvalid, sc->d_records, sc->ovec_slots, d_lo, stream));
     }
-    if (sc->mode != SRE_HIP_THOMPSON) {
-        if (sc->d_pwave) {
-            SRE_HIP_TRY(sre_launch_pike_window_wave(sc->d_pwave, sc->h_pwave, sc->d_ptrs, sc->d_lens, n, sc->d_records,
-                                                    sc->ovec_slots, reinterpret_cast<sre_nfa_window_t *>(sc->d_nstatus), d_lo,
-                                                    sc->geom.sflags ? sc->d_creq : NULL, stream));
-        } else {
-            /* (the window kernel zero-fills the context it uses) */
-            SRE_HIP_TRY(sre_launch_pike_window(sc->dp->d_blob, sc->dp->blob_bytes, sc->d_ptrs, sc->d_lens, n, sc->d_ctx, sc->ctx_stride,
-                                               sc->d_records, sc->ovec_slots,
-                                               reinterpret_cast<sre_nfa_window_t *>(sc->d_nstatus), d_lo,
-                                               sc->geom.sflags ? sc->d_creq : NULL, stream));
-        }
-    }
+    if (sc->mode != SRE_HIP_THOMPSON) return nfa_windows(sc, d_lo, stream);
     return 0;
 hip_failed:
     return -1;
@@ -1626,8 +1641,157 @@ hip_failed:
     return -1;
 }
 
-/* NFA tier and exact VM: each batch's slice of the line table comes to the host and goes through
- * sre_hip_scan_enqueue / sre_hip_scan_results; the rows are compacted on the host */
+/* the longest line the short-line kernel takes: SRE_HIP_LINES_SHORT_MAX (read on every call; 0: the kernel is
+ * off) or SRE_LINES_SHORT_MAX; the wide forms have no such kernel */
+static uint64_t
+lines_short_max(const sre_hip_scanner_t *sc)
+{
+    if (sc->wide_kernel) return 0;
+    const char *e = getenv("SRE_HIP_LINES_SHORT_MAX");
+    if (e == NULL || *e == 0) return SRE_LINES_SHORT_MAX;
+    const long long v = atoll(e);
+    return v <= 0 ? 0 : v < (1ll << 20) ? (uint64_t) v : (uint64_t) 1 << 20;
+}
+
+/* NFA tier, Thompson and first match: every batch on the device.  Lines of at most lines_short_max() bytes take
+ * no segment and go to the short-line kernel (sre_hip_lines_nfa.hip); the others go through the set pass, the
+ * chain check and the fix-up rounds as a batch of streams does, settled from one device counter.  Order of a
+ * batch: set pass and nfa_finish over every stream (a line without segments comes out verified and DECLINED,
+ * and has no window), THEN the short-line kernel writes the short lines' status blocks and records and the work
+ * list d_lo of their windows, then the window kernel runs over that list; the fix-up rounds rebuild d_lo from
+ * the status blocks, in which every short line is done. */
+static int
+lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
+               uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, double *kms, size_t *nshort_all)
+{
+    const size_t   slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
+    const uint64_t rcap = cap < n ? cap : n;
+    const uint64_t lmax = lines_short_max(sc), short_lim = lmax ? lmax + 1 : 0;
+    const uint32_t W = nfa_words(sc);
+    /* what a segment costs: its summary, belief and validity byte, and the wide kernel's entry and exit sets */
+    const uint64_t seg_cost = sizeof(sre_nfa_summary_t) + W * sizeof(uint64_t) + 1 + (sc->wide_kernel ? 2 * W * sizeof(uint64_t) : 0);
+    uint64_t       bmax = lines_batch_limit();
+    uint64_t       seg_fixed = scan_seg_knobs(sc);
+    if (seg_fixed == 0) {
+        /* (the set kernels take any multiple of the 64-byte round, as for stream sets) */
+        const char *e = getenv("SRE_HIP_SEG_BYTES");
+        if (e && atoi(e) > 0 && atoi(e) % 64 == 0) seg_fixed = (uint64_t) atoi(e);
+    }
+    const uint64_t resident = scan_resident(sc);
+    const uint64_t seg_cap = sc->seg_cap_env ? sc->seg_cap_env : 40960;
+    if (sc->mode != SRE_HIP_THOMPSON && sc->d_pwave == NULL && sc->ctx_stride) {
+        /* the exact window's contexts, one per line of the batch */
+        const uint64_t most = SRE_LINES_NFA_WORK_MAX / sc->ctx_stride;
+        if (bmax > most) bmax = most ? most : 1;
+    }
+    sre_lnfa_t ltab;
+    memset(&ltab, 0, sizeof(ltab));
+    if (short_lim) ltab = sc->use_sa ? sre_lines_nfa_tables_sa(&sc->satab) : sre_lines_nfa_tables_plain(&sc->ntab);
+    if (rcap && lines_grow(&sc->d_rows, &sc->rows_cap, rcap * width * sizeof(int64_t)) != 0) return -1;
+    SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->reported, 0, sizeof(uint64_t), stream));
+    if (sc->ev0 == NULL) {
+        SRE_HIP_TRY(hipEventCreate(&sc->ev0));
+        SRE_HIP_TRY(hipEventCreate(&sc->ev1));
+    }
+    if (sc->ev_l0 == NULL) {
+        SRE_HIP_TRY(hipEventCreate(&sc->ev_l0));
+        SRE_HIP_TRY(hipEventCreate(&sc->ev_l1));
+    }
+    for (uint64_t i0 = 0; i0 < n;) {
+        const uint64_t nmax = bmax < n - i0 ? bmax : n - i0;
+        if (scanner_reserve(sc, nmax) != 0) return -1;
+        SRE_HIP_TRY(sre_launch_lines_geometry_nfa(d_buf, sc->d_ends, n, i0, nmax, short_lim, SRE_LINES_NFA_WORK_MAX, seg_cost,
+                                                  seg_fixed, resident, seg_cap, reinterpret_cast<const uint8_t **>(sc->d_ptrs),
+                                                  sc->d_lens, sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->nshort, &sc->d_linfo->nshort, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
+        const uint64_t nshort = sc->h_linfo->nshort;
+        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
+        sc->geom.lens = sc->d_lens;
+        sc->geom.seg_first = sc->d_seg_first;
+        sc->geom.nstreams = (uint32_t) nb;
+        sc->geom.seg_bytes = (uint32_t) seg;
+        sc->geom.nsegs = nsegs;
+        sc->geom.init_variant = 0;
+        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
+        sc->geom.entry_state = 0;
+        sc->geom.one_ptr = NULL;
+        sc->geom.one_len = 0;
+        sc->geom.digest = NULL;
+        sc->geom.sentry = NULL;
+        sc->geom.sflags = NULL;
+        sc->geom_one = 0;
+        sc->d_eset = NULL;
+        sc->fixup_rounds = 0;
+        sc->exact_passes = 0;
+        if (nsegs) {
+            if (nfa_buffers(sc, nsegs) != 0) return -1;
+            SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
+            SRE_HIP_TRY(nfa_launch_scan(sc, NULL, NULL, NULL, stream));
+            SRE_HIP_TRY(hipEventRecord(sc->ev1, stream));
+            if (nfa_finish(sc, NULL, stream) != 0) return -1;
+        }
+        if (nshort) {
+            SRE_HIP_TRY(hipEventRecord(sc->ev_l0, stream));
+            SRE_HIP_TRY(sre_launch_lines_nfa(ltab, d_buf, sc->d_ends, i0, (uint32_t) nb, (uint32_t) short_lim,
+                                             sc->mode == SRE_HIP_THOMPSON, sc->d_nstatus, sc->d_records, sc->ovec_slots, sc->d_lo,
+                                             stream));
+            SRE_HIP_TRY(hipEventRecord(sc->ev_l1, stream));
+            if (sc->mode != SRE_HIP_THOMPSON && nfa_windows(sc, sc->d_lo, stream) != 0) return -1;
+        }
+        if (nsegs) {
+            /* fix-up rounds over the long lines that are not verified, as streams_feed_nfa runs them: the work
+             * list and its length are made on the device, the host reads one word per round */
+            for (;;) {
+                SRE_HIP_TRY(sre_launch_streams_nfa_lo(sc->d_nstatus, (uint32_t) nb, sc->d_lo, &sc->d_linfo->pending, stream));
+                SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                           stream));
+                SRE_HIP_TRY(hipStreamSynchronize(stream));
+                if (sc->h_linfo->pending == 0) break;
+                if (nfa_fixup_round(sc, stream) != 0) return -1;
+            }
+        }
+        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
+                                             sc->d_linfo, sc->d_rows, rcap, stream));
+        {
+            float ms = 0.0f;
+            if (nsegs) {
+                SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
+                *kms += ms;
+            }
+            if (nshort) {
+                SRE_HIP_TRY(hipEventSynchronize(sc->ev_l1));
+                SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev_l0, sc->ev_l1));
+                *kms += ms;
+            }
+        }
+        *fixups += sc->fixup_rounds;
+        *exact += sc->exact_passes;
+        *nshort_all += (size_t) nshort;
+        sc->line_batches++;
+        i0 = i1;
+    }
+    SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->reported, &sc->d_linfo->reported, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                               stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    *pnrep = n ? sc->h_linfo->reported : 0;
+    {
+        const uint64_t take = *pnrep < rcap ? *pnrep : rcap;
+        if (take) {
+            SRE_HIP_TRY(hipMemcpyAsync(out, sc->d_rows, take * width * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* find-all counting on the NFA tier and the exact VM (and the NFA tier under SRE_HIP_LINES_NFA_HOST): each
+ * batch's slice of the line table comes to the host and goes through sre_hip_scan_enqueue /
+ * sre_hip_scan_results; the rows are compacted on the host */
 static int
 lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
                 uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms)
@@ -1699,13 +1863,20 @@ sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     uint64_t    n = 0, nrep = 0;
     int         fixups = 0, exact = 0, lineage = 0, rc = -1;
     double      kms = sc->engine == SRE_HIP_ENGINE_VM ? -1.0 : 0.0;
+    size_t      nshort = 0;
+    /* 0: per-line host work, 1: the table-driven scanner's device route, 2: the NFA tier's */
+    int         route = sc->engine == SRE_HIP_ENGINE_SCAN ? 1 : 0;
+    if (sc->engine == SRE_HIP_ENGINE_NFA && sc->cnt == NULL) {
+        const char *e = getenv("SRE_HIP_LINES_NFA_HOST");       /* the per-line host route, for A/B measurements and tests */
+        if (e == NULL || atoi(e) == 0) route = 2;
+    }
     sc->line_batches = 0;
     if (sc->d_linfo == NULL) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_linfo), sizeof(sre_lines_info_t)));
     if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
     if (lines_split(sc, d_buf, len, delim, stream, &n) == 0) {
-        rc = sc->engine == SRE_HIP_ENGINE_SCAN
-                 ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms)
-                 : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms);
+        rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms)
+             : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &kms, &nshort)
+                          : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms);
     }
 hip_failed:
     /* this call replaces the scanner's last one; its diagnostics describe the whole call */
@@ -1716,6 +1887,8 @@ hip_failed:
     sc->exact_passes = exact;
     sc->lineage_passes = lineage;
     sc->lines_kernel_ms = rc == 0 ? kms : -1.0;
+    sc->lines_device = rc == 0 && route != 0;
+    sc->short_lines = rc == 0 ? nshort : 0;
     if (rc != 0) return -1;
     if (nlines) *nlines = (size_t) n;
     if (nreported) *nreported = (size_t) nrep;
@@ -1726,6 +1899,18 @@ extern "C" SRE_API int
 sre_hip_scanner_last_line_batches(sre_hip_scanner_t *sc)
 {
     return sc->line_batches;
+}
+
+extern "C" SRE_API int
+sre_hip_scanner_last_lines_device(sre_hip_scanner_t *sc)
+{
+    return sc->lines_device ? 1 : 0;
+}
+
+extern "C" SRE_API size_t
+sre_hip_scanner_last_short_lines(sre_hip_scanner_t *sc)
+{
+    return sc->short_lines;
 }
 
 /* One device-resident buffer through the scanner, for sre_vm_*_exec on large

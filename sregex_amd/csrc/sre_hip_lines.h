@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sre_hip_scan.h"
+#include "sre_hip_nfa.h"
+#include "sre_lines_nfa.h"
 
 /* split: a workgroup of SRE_LINES_THREADS lanes owns one tile of 16-byte aligned chunks, each lane
  * loads SRE_LINES_CHUNKS chunks of it (lane x, step k: chunk k * SRE_LINES_THREADS + x of the tile).
@@ -23,6 +25,10 @@
  * take: lines x (segment + 16) x 2 B — 1 Mi lines of 96 B take 570 MB at 256-byte segments */
 #define SRE_LINES_BATCH       (1u << 20)
 #define SRE_LINES_WALK_MAX (1ull << 30)
+/* NFA tier: the most per-segment working set (summaries, beliefs, the wide kernel's sets) a batch may take, and
+ * the longest line the short-line kernel takes by default (SRE_HIP_LINES_SHORT_MAX overrides; 0: off) */
+#define SRE_LINES_NFA_WORK_MAX  (1ull << 30)
+#define SRE_LINES_SHORT_MAX     512u
 
 /* device words of one line-mode call; the host reads them in small copies */
 typedef struct {
@@ -34,6 +40,7 @@ typedef struct {
     uint64_t reported;      /* running count of reported lines, all batches so far */
     uint64_t pending;       /* settle: streams of the batch whose status is not done */
     uint64_t maps;          /* settle: streams that asked for lineage maps (need_maps) */
+    uint64_t nshort;        /* batch, NFA tier: lines the short-line kernel takes (they have no segment) */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -53,6 +60,14 @@ hipError_t sre_launch_lines_geometry(const void *d_buf, const uint64_t *d_ends, 
     uint64_t nmax, uint64_t scratch_max, uint64_t seg_fixed, uint64_t resident, uint64_t seg_cap,
     const uint8_t **d_ptrs, uint64_t *d_lens, uint64_t *d_seg_first, uint64_t *d_blk,
     sre_lines_info_t *d_info, hipStream_t stream);
+/* the same for the NFA tier.  Lines shorter than short_lim bytes get NO segment (the short-line kernel takes
+ * them; 0: none does, an empty line then keeps its one segment); the batch is the longest of at most nmax lines
+ * whose segments' working set fits: (bytes / seg + lines) * seg_cost <= work_max, a single line always does.
+ * The segment size goes by the bytes of all the batch's lines.  info->i1, bytes, seg, nsegs, nshort */
+hipError_t sre_launch_lines_geometry_nfa(const void *d_buf, const uint64_t *d_ends, uint64_t nlines, uint64_t i0,
+    uint64_t nmax, uint64_t short_lim, uint64_t work_max, uint64_t seg_cost, uint64_t seg_fixed, uint64_t resident,
+    uint64_t seg_cap, const uint8_t **d_ptrs, uint64_t *d_lens, uint64_t *d_seg_first, uint64_t *d_blk,
+    sre_lines_info_t *d_info, hipStream_t stream);
 /* info->pending / info->maps of the batch's n status words (zeroed first) */
 hipError_t sre_launch_lines_settle(const sre_stream_status_t *d_status, uint32_t n, sre_lines_info_t *d_info,
     hipStream_t stream);
@@ -61,6 +76,16 @@ hipError_t sre_launch_lines_settle(const sre_stream_status_t *d_status, uint32_t
 hipError_t sre_launch_lines_compact(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0,
     int all, const uint64_t *d_ends, uint64_t *d_blk, sre_lines_info_t *d_info, int64_t *d_rows, uint64_t cap,
     hipStream_t stream);
+/* the short-line kernel (sre_hip_lines_nfa.hip): the tables of a 64-bit form as its step reads them
+ * (sre_lines_nfa.h; device pointers inside) ... */
+sre_lnfa_t sre_lines_nfa_tables_plain(const sre_nfa_tables_t *p);
+sre_lnfa_t sre_lines_nfa_tables_sa(const sre_nfa_sa_tables_t *a);
+/* ... and one lane per line of the batch (lines i0 .. i0 + nb): a line shorter than short_lim bytes gets its
+ * status block, its record (as the chain check writes them: Pike records with an event wait for the window
+ * kernel) and lo = 0 when the window kernel has to run over it, else -1; a longer line gets lo = -1 only */
+hipError_t sre_launch_lines_nfa(sre_lnfa_t tab, const void *d_buf, const uint64_t *d_ends, uint64_t i0, uint32_t nb,
+    uint32_t short_lim, int thompson, sre_nfa_status_t *d_status, int64_t *d_records, uint32_t ovec_slots,
+    int64_t *d_lo, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -271,6 +271,94 @@ sre_k_lines_geom_write(const uint8_t *__restrict__ buf, const uint64_t *__restri
     }
 }
 
+/* ---- geometry of one batch on the NFA tier ---- */
+
+/* one lane: the longest batch from i0 of at most nmax lines whose per-segment working set fits.  The segments
+ * of a batch are at most bytes / seg + lines whatever the short-line limit takes away */
+__global__ void
+sre_k_lines_plan_nfa(const uint64_t *__restrict__ ends, uint64_t i0, uint64_t nmax, uint64_t work_max, uint64_t seg_cost,
+                     uint64_t seg_fixed, uint64_t resident, uint64_t seg_cap, sre_lines_info_t *__restrict__ info)
+{
+    if (threadIdx.x != 0) return;
+    const uint64_t s0 = line_start(ends, i0);
+    auto bytes = [&](uint64_t i1) { return ends[i1 - 1] - s0 - (i1 - 1 - i0); };
+    auto seg_of = [&](uint64_t total) { return seg_fixed ? seg_fixed : sre_scan_auto_segment(total, resident, seg_cap); };
+    auto fits = [&](uint64_t i1) { return (bytes(i1) / seg_of(bytes(i1)) + (i1 - i0)) * seg_cost <= work_max; };
+    uint64_t lo = i0 + 1, hi = i0 + nmax;
+    if (fits(hi)) {
+        lo = hi;
+    } else {
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo + 1) / 2;
+            if (fits(mid)) lo = mid;
+            else hi = mid - 1;
+        }
+    }
+    info->i1 = lo;
+    info->bytes = bytes(lo);
+    info->seg = seg_of(info->bytes);
+    info->nshort = 0;
+}
+
+/* segments of line i: none for a line the short-line kernel takes */
+__device__ inline uint64_t
+line_segs_nfa(const uint64_t *ends, uint64_t i, uint64_t seg, uint64_t short_lim)
+{
+    const uint64_t n = ends[i] - line_start(ends, i);
+    if (n < short_lim) return 0;
+    return n ? (n + seg - 1) / seg : 1;
+}
+
+__global__ __launch_bounds__(256) void
+sre_k_lines_geom_count_nfa(const uint64_t *__restrict__ ends, uint64_t i0, uint64_t short_lim,
+                           sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ blk)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      nb = info->i1 - i0, seg = info->seg;
+    const uint64_t      q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint64_t            s = 0, sh = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        if (q0 + q < nb) {
+            s += line_segs_nfa(ends, i0 + q0 + q, seg, short_lim);
+            sh += ends[i0 + q0 + q] - line_start(ends, i0 + q0 + q) < short_lim ? 1 : 0;
+        }
+    }
+    uint64_t total, nshort;
+    (void) block_excl_scan<256>(s, wsum, total);
+    (void) block_excl_scan<256>(sh, wsum, nshort);
+    if (threadIdx.x == 0) {
+        blk[blockIdx.x] = total;
+        if (nshort) atomicAdd(reinterpret_cast<unsigned long long *>(&info->nshort), (unsigned long long) nshort);
+    }
+}
+
+__global__ __launch_bounds__(256) void
+sre_k_lines_geom_write_nfa(const uint8_t *__restrict__ buf, const uint64_t *__restrict__ ends, uint64_t i0, uint64_t short_lim,
+                           const sre_lines_info_t *__restrict__ info, const uint64_t *__restrict__ blk,
+                           const uint8_t **__restrict__ ptrs, uint64_t *__restrict__ lens, uint64_t *__restrict__ seg_first)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      nb = info->i1 - i0, seg = info->seg;
+    const uint64_t      q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint64_t            k[4], s = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        k[q] = q0 + q < nb ? line_segs_nfa(ends, i0 + q0 + q, seg, short_lim) : 0;
+        s += k[q];
+    }
+    uint64_t total;
+    uint64_t run = blk[blockIdx.x] + block_excl_scan<256>(s, wsum, total);
+    for (uint32_t q = 0; q < 4; q++) {
+        const uint64_t j = q0 + q;
+        if (j >= nb) break;
+        const uint64_t st = line_start(ends, i0 + j);
+        ptrs[j] = buf + st;
+        lens[j] = ends[i0 + j] - st;
+        seg_first[j] = run;
+        run += k[q];
+        if (j == nb - 1) seg_first[nb] = run;
+    }
+}
+
 /* ---- settle counters ---- */
 
 __global__ __launch_bounds__(256) void
@@ -388,6 +476,23 @@ sre_launch_lines_geometry(const void *d_buf, const uint64_t *d_ends, uint64_t nl
     hipLaunchKernelGGL(sre_k_lines_scan, dim3(1), dim3(1024), 0, stream, d_blk, (uint64_t) nblk, &d_info->nsegs, 0);
     hipLaunchKernelGGL(sre_k_lines_geom_write, dim3(nblk), dim3(256), 0, stream, static_cast<const uint8_t *>(d_buf), d_ends,
                        i0, d_info, d_blk, d_ptrs, d_lens, d_seg_first);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_lines_geometry_nfa(const void *d_buf, const uint64_t *d_ends, uint64_t nlines, uint64_t i0, uint64_t nmax,
+                              uint64_t short_lim, uint64_t work_max, uint64_t seg_cost, uint64_t seg_fixed, uint64_t resident,
+                              uint64_t seg_cap, const uint8_t **d_ptrs, uint64_t *d_lens, uint64_t *d_seg_first,
+                              uint64_t *d_blk, sre_lines_info_t *d_info, hipStream_t stream)
+{
+    if (nmax == 0 || i0 + nmax > nlines || seg_cost == 0) return hipErrorInvalidValue;
+    const uint32_t nblk = (uint32_t) ((nmax + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
+    hipLaunchKernelGGL(sre_k_lines_plan_nfa, dim3(1), dim3(64), 0, stream, d_ends, i0, nmax, work_max, seg_cost, seg_fixed,
+                       resident, seg_cap, d_info);
+    hipLaunchKernelGGL(sre_k_lines_geom_count_nfa, dim3(nblk), dim3(256), 0, stream, d_ends, i0, short_lim, d_info, d_blk);
+    hipLaunchKernelGGL(sre_k_lines_scan, dim3(1), dim3(1024), 0, stream, d_blk, (uint64_t) nblk, &d_info->nsegs, 0);
+    hipLaunchKernelGGL(sre_k_lines_geom_write_nfa, dim3(nblk), dim3(256), 0, stream, static_cast<const uint8_t *>(d_buf),
+                       d_ends, i0, short_lim, d_info, d_blk, d_ptrs, d_lens, d_seg_first);
     return hipGetLastError();
 }
 
