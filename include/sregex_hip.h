@@ -238,6 +238,67 @@ SRE_API int sre_hip_scanner_last_lines_device(sre_hip_scanner_t *sc);
 /* lines of the last sre_hip_scan_lines call that the NFA tier's short-line kernel took */
 SRE_API size_t sre_hip_scanner_last_short_lines(sre_hip_scanner_t *sc);
 
+/* ---- line filter: the selected lines themselves, compacted into a device buffer ---- */
+
+enum { SRE_HIP_LINES_INVERT = 2 };   /* select the lines WITHOUT a match (grep -v) */
+
+typedef struct {
+    size_t nlines;      /* lines in the buffer (as sre_hip_scan_lines) */
+    size_t nselected;   /* lines selected */
+    size_t need_bytes;  /* bytes all selected lines take in the output: sum of (len + 1) */
+    size_t nwritten;    /* selected lines actually written (whole lines only) */
+    size_t out_bytes;   /* bytes written to d_out */
+} sre_hip_filter_info_t;
+
+/*
+ * Line filter: grep and grep -v from one device buffer to another.  The split of d_buf, the
+ * matching of every line and the engine a scanner routes to are exactly those of
+ * sre_hip_scan_lines on the same arguments; what comes back is the text of the selected
+ * lines in device memory, not rows on the host.
+ *
+ * Which lines are selected:
+ *   - flags == 0: the lines sre_hip_scan_lines reports without SRE_HIP_LINES_ALL, that is the
+ *     lines whose rc is not SRE_DECLINED (COUNT mode's SRE_ERROR lines are selected);
+ *   - SRE_HIP_LINES_INVERT: the lines whose rc is SRE_DECLINED instead;
+ *   - SRE_HIP_LINES_ALL: every line;
+ *   - ALL | INVERT, and any other flag bit, return -1.
+ *
+ * Output.  d_out is a DEVICE pointer at any alignment to out_cap bytes that do not overlap
+ * [d_buf, d_buf + len) (an overlap returns -1).  It receives the selected lines in line order,
+ * each as its bytes followed by ONE `delim` byte; a final line that had no delimiter in the
+ * source gets one too.  The output is therefore a well-formed line buffer itself: without
+ * INVERT, filtering it again with the same scanner and flags selects all its lines and
+ * reproduces it byte for byte.  info->need_bytes is the sum of len + 1 over the selected lines
+ * whatever out_cap is.
+ *
+ * Truncation.  Only whole lines are written: info->nwritten is the largest k for which the
+ * first k selected lines take at most out_cap bytes, info->out_bytes that total.  No byte of
+ * d_out at or beyond out_bytes is touched and nothing is written in front of d_out.  d_out may
+ * be NULL when out_cap == 0 (a sizing call).
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten)
+ * written lines it receives 4 sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the line in d_out.
+ * d_index may be NULL when index_cap == 0.  info may be NULL.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  On the routes where
+ * sre_hip_scanner_last_lines_device() is 1 (the table-driven scanner; Thompson and first-match
+ * scanners of the NFA tier) the host reads a fixed number of words per batch and per call: no
+ * rows, records or per-line values travel to the host.  The other routes (find-all counting on
+ * the tier, the exact VM, SRE_HIP_LINES_NFA_HOST=1) keep their per-line host work and upload
+ * one word per line.  The call replaces the scanner's last call exactly as sre_hip_scan_lines
+ * does, and the diagnostics (last_fixups, last_line_batches, last_lines_device,
+ * last_short_lines, last_kernel_ms: the scan kernels, not the gather) describe it the same
+ * way.  len == 0 gives all zeros in info and success.  All offsets and totals are 64-bit.
+ * Beyond what line mode takes, a scanner keeps 8 bytes per line of the largest call (plus 16
+ * bytes per 1024 lines) of device memory, grow-only, freed with the scanner.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap,
+    sre_hip_filter_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

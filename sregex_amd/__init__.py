@@ -16,6 +16,7 @@ plus the additive device-resident batched API of include/sregex_hip.h
 exec calls return SRE_ERROR and the scanner constructors raise.  Nothing here
 imports or calls the test oracle.
 """
+import collections
 import ctypes
 import os
 import tempfile
@@ -25,6 +26,7 @@ SRE_REGEX_CASELESS, SRE_REGEX_NEWLINE = 1, 2
 HIP_THOMPSON, HIP_PIKE_FIRST, HIP_PIKE_COUNT = 0, 1, 2
 ENGINE_AUTO, ENGINE_VM, ENGINE_SCAN, ENGINE_NFA = 0, 1, 2, 3
 HIP_LINES_ALL = 1
+HIP_LINES_INVERT = 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -77,6 +79,7 @@ API = {
     "sre_hip_scan_batch": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), _sz, _pssz, _vp]),
     "sre_hip_scan_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _pssz, _sz,
                                           ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
+    "sre_hip_filter_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -403,6 +406,19 @@ class Scanner:
         rows = [list(out[i * width:(i + 1) * width]) for i in range(take)]
         return nl.value, nr.value, rows
 
+    def filter_lines(self, ptr, length, out_ptr, out_cap, delim=0x0A, invert=False, all_lines=False, index_ptr=None,
+                     index_cap=0, hip_stream=None):
+        """sre_hip_filter_lines: the selected lines of the device buffer (ptr, length), each followed by one
+        delimiter, compacted in order into the device buffer (out_ptr, out_cap); index_ptr: an optional device
+        array of index_cap rows [line no, offset in the buffer, length, offset in the output].  Returns
+        FilterInfo(nlines, nselected, need_bytes, nwritten, out_bytes)."""
+        flags = (HIP_LINES_ALL if all_lines else 0) | (HIP_LINES_INVERT if invert else 0)
+        info = (_sz * 5)()
+        if self.lib.sre_hip_filter_lines(self.h, ptr, length, delim, flags, out_ptr, out_cap, index_ptr, index_cap,
+                                         info, hip_stream) != 0:
+            raise RuntimeError("sre_hip_filter_lines failed")
+        return FilterInfo(*info)
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -416,6 +432,9 @@ class Scanner:
     def last_short_lines(self):
         """lines of the last scan_lines call that the NFA tier's short-line kernel took"""
         return self.lib.sre_hip_scanner_last_short_lines(self.h)
+
+
+FilterInfo = collections.namedtuple("FilterInfo", "nlines nselected need_bytes nwritten out_bytes")
 
 
 class StreamSet:

@@ -131,6 +131,11 @@ struct sre_hip_scanner_s {
     bool                      lines_device;     /* ... every batch ran on the device, no per-line host work */
     size_t                    short_lines;      /* ... lines the short-line kernel took (NFA tier) */
     hipEvent_t                ev_l0, ev_l1;     /* around a batch's short-line kernel */
+    /* the line filter (sre_hip_filter_lines), grown on demand */
+    uint64_t                 *d_fval;           /* per-line values, then the offset table: lines + 1 words */
+    size_t                    fval_cap;
+    uint64_t                 *d_fblk;           /* per-workgroup sums of the scan: 2 words per SRE_LINES_ITEMS lines */
+    size_t                    fblk_cap;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -188,6 +193,8 @@ scanner_release(void *data)
     if (sc->d_ends) (void) hipFree(sc->d_ends);
     if (sc->d_lblk) (void) hipFree(sc->d_lblk);
     if (sc->d_rows) (void) hipFree(sc->d_rows);
+    if (sc->d_fval) (void) hipFree(sc->d_fval);
+    if (sc->d_fblk) (void) hipFree(sc->d_fblk);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -1558,10 +1565,24 @@ hip_failed:
     return -1;
 }
 
+/* the line filter's sink (sre_hip_filter_lines): with one, a batch ends with the select pass into d_val in place of
+ * the compaction of its rows, and no row goes to the host (out / cap are NULL / 0 then) */
+struct LinesSink {
+    int       mode;     /* 0: the lines with a match, 1: the lines without one, 2: every line */
+    uint64_t *d_val;    /* one word per line of the call */
+};
+
+static bool
+sink_selects(const LinesSink *sink, sre_int_t rc)
+{
+    return sink->mode == 2 || (rc != SRE_DECLINED) != (sink->mode == 1);
+}
+
 /* table-driven scanner: every batch on the device; the host reads a few words per batch */
 static int
 lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
-                  uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms)
+                  uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms,
+                  const LinesSink *sink)
 {
     const size_t   slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
     const uint64_t bmax = lines_batch_limit();
@@ -1612,8 +1633,13 @@ lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all,
         if (lines_status_counters(sc, nb, stream) != 0) return -1;
         if (scan_settle(sc, nb, stream, true, NULL, true) != 0) return -1;
         if (sc->mode != SRE_HIP_THOMPSON && sc->h_linfo->maps != 0 && scan_lineage_pass(sc, stream) != 0) return -1;
-        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
-                                             sc->d_linfo, sc->d_rows, rcap, stream));
+        if (sink) {
+            SRE_HIP_TRY(sre_launch_filter_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode, sc->d_ends, sc->d_linfo,
+                                                 sink->d_val, stream));
+        } else {
+            SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
+                                                 sc->d_linfo, sc->d_rows, rcap, stream));
+        }
         {
             float ms = 0.0f;
             SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
@@ -1625,6 +1651,7 @@ lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all,
         sc->line_batches++;
         i0 = i1;
     }
+    if (sink) return 0;
     SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->reported, &sc->d_linfo->reported, sizeof(uint64_t), hipMemcpyDeviceToHost,
                                stream));
     SRE_HIP_TRY(hipStreamSynchronize(stream));
@@ -1662,7 +1689,8 @@ lines_short_max(const sre_hip_scanner_t *sc)
  * the status blocks, in which every short line is done. */
 static int
 lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
-               uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, double *kms, size_t *nshort_all)
+               uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, double *kms, size_t *nshort_all,
+               const LinesSink *sink)
 {
     const size_t   slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
     const uint64_t rcap = cap < n ? cap : n;
@@ -1753,8 +1781,13 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
                 if (nfa_fixup_round(sc, stream) != 0) return -1;
             }
         }
-        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
-                                             sc->d_linfo, sc->d_rows, rcap, stream));
+        if (sink) {
+            SRE_HIP_TRY(sre_launch_filter_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode, sc->d_ends, sc->d_linfo,
+                                                 sink->d_val, stream));
+        } else {
+            SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
+                                                 sc->d_linfo, sc->d_rows, rcap, stream));
+        }
         {
             float ms = 0.0f;
             if (nsegs) {
@@ -1773,6 +1806,7 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
         sc->line_batches++;
         i0 = i1;
     }
+    if (sink) return 0;
     SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->reported, &sc->d_linfo->reported, sizeof(uint64_t), hipMemcpyDeviceToHost,
                                stream));
     SRE_HIP_TRY(hipStreamSynchronize(stream));
@@ -1794,7 +1828,8 @@ hip_failed:
  * sre_hip_scan_results; the rows are compacted on the host */
 static int
 lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
-                uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms)
+                uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms,
+                const LinesSink *sink)
 {
     const size_t              slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
     const uint64_t            bmax = lines_batch_limit();
@@ -1803,6 +1838,7 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
     std::vector<const void *> ptrs;
     std::vector<size_t>       lens;
     std::vector<sre_int_t>    recs;
+    std::vector<uint64_t>     vals;             /* with a sink: the batch's per-line values, uploaded */
     uint64_t                  nrep = 0;
     for (uint64_t i0 = 0; i0 < n;) {
         const uint64_t nb = bmax < n - i0 ? bmax : n - i0;
@@ -1828,7 +1864,13 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
         *lineage += sc->lineage_passes;
         const double ms = sre_hip_scanner_last_kernel_ms(sc);
         *kms = (ms < 0 || *kms < 0) ? -1.0 : *kms + ms;
-        for (uint64_t j = 0; j < nb; j++) {
+        if (sink) {
+            vals.resize(nb);
+            for (uint64_t j = 0; j < nb; j++) vals[j] = sink_selects(sink, recs[j * slots]) ? (uint64_t) lens[j] + 1 : 0;
+            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0, vals.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
+        for (uint64_t j = 0; !sink && j < nb; j++) {
             const sre_int_t *rec = recs.data() + j * slots;
             if (!all && rec[0] == SRE_DECLINED) continue;
             if (nrep < cap) {
@@ -1849,17 +1891,12 @@ hip_failed:
     return -1;
 }
 
-extern "C" SRE_API int
-sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags,
-    sre_int_t *out, size_t cap, size_t *nlines, size_t *nreported, void *hip_stream)
+/* a line-mode call: the split and the driver of the scanner's route; with a sink its per-line array is grown to the
+ * call's lines first.  The call replaces the scanner's last one; its diagnostics describe the whole call. */
+static int
+lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int all, sre_int_t *out, size_t cap,
+           LinesSink *sink, uint64_t *pn, uint64_t *pnrep, hipStream_t stream)
 {
-    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || (cap != 0 && out == NULL)
-        || (len != 0 && d_buf == NULL))
-    {
-        return -1;
-    }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const int   all = (flags & SRE_HIP_LINES_ALL) != 0;
     uint64_t    n = 0, nrep = 0;
     int         fixups = 0, exact = 0, lineage = 0, rc = -1;
     double      kms = sc->engine == SRE_HIP_ENGINE_VM ? -1.0 : 0.0;
@@ -1874,9 +1911,13 @@ sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     if (sc->d_linfo == NULL) SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_linfo), sizeof(sre_lines_info_t)));
     if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
     if (lines_split(sc, d_buf, len, delim, stream, &n) == 0) {
-        rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms)
-             : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &kms, &nshort)
-                          : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms);
+        if (sink) {
+            if (lines_grow(&sc->d_fval, &sc->fval_cap, (n + 1) * sizeof(uint64_t)) != 0) goto hip_failed;
+            sink->d_val = sc->d_fval;
+        }
+        rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms, sink)
+             : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &kms, &nshort, sink)
+                          : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms, sink);
     }
 hip_failed:
     /* this call replaces the scanner's last one; its diagnostics describe the whole call */
@@ -1890,9 +1931,76 @@ hip_failed:
     sc->lines_device = rc == 0 && route != 0;
     sc->short_lines = rc == 0 ? nshort : 0;
     if (rc != 0) return -1;
+    *pn = n;
+    *pnrep = nrep;
+    return 0;
+}
+
+extern "C" SRE_API int
+sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags,
+    sre_int_t *out, size_t cap, size_t *nlines, size_t *nreported, void *hip_stream)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || (cap != 0 && out == NULL)
+        || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    uint64_t n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, (flags & SRE_HIP_LINES_ALL) != 0, out, cap, NULL, &n, &nrep,
+                   static_cast<hipStream_t>(hip_stream)) != 0)
+    {
+        return -1;
+    }
     if (nlines) *nlines = (size_t) n;
     if (nreported) *nreported = (size_t) nrep;
     return 0;
+}
+
+/* The line filter: the line-mode call with a sink, then on the device the scan of the per-line
+ * values to the offset table, the cut at out_cap, one read of four words, the gather and the index rows. */
+extern "C" SRE_API int
+sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, void *d_out,
+    size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream)
+{
+    const int known = SRE_HIP_LINES_ALL | SRE_HIP_LINES_INVERT;
+    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~known) != 0 || (flags & known) == known
+        || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0, NULL};
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_filter_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_fval, n, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nselected = (size_t) sc->h_linfo->fsel;
+        res.need_bytes = (size_t) sc->h_linfo->fneed;
+        res.nwritten = (size_t) sc->h_linfo->fwritten;
+        res.out_bytes = (size_t) sc->h_linfo->fbytes;
+        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
+        SRE_HIP_TRY(sre_launch_lines_gather(d_buf, d_out, sc->d_fval, sc->d_ends, n, res.out_bytes, (uint32_t) delim, stream));
+        if (res.nwritten != 0) {
+            SRE_HIP_TRY(sre_launch_filter_index(sc->d_fval, sc->d_ends, n, sc->d_fblk, sc->d_linfo, index_cap, d_index, stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
 }
 
 extern "C" SRE_API int

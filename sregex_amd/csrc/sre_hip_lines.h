@@ -41,6 +41,11 @@ typedef struct {
     uint64_t pending;       /* settle: streams of the batch whose status is not done */
     uint64_t maps;          /* settle: streams that asked for lineage maps (need_maps) */
     uint64_t nshort;        /* batch, NFA tier: lines the short-line kernel takes (they have no segment) */
+    /* the line filter (sre_hip_filter_lines): the four words the host reads before the gather */
+    uint64_t fsel;          /* lines selected */
+    uint64_t fneed;         /* bytes all of them take */
+    uint64_t fwritten;      /* selected lines that fit out_cap whole */
+    uint64_t fbytes;        /* bytes of those */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -86,6 +91,22 @@ sre_lnfa_t sre_lines_nfa_tables_sa(const sre_nfa_sa_tables_t *a);
 hipError_t sre_launch_lines_nfa(sre_lnfa_t tab, const void *d_buf, const uint64_t *d_ends, uint64_t i0, uint32_t nb,
     uint32_t short_lim, int thompson, sre_nfa_status_t *d_status, int64_t *d_records, uint32_t ovec_slots,
     int64_t *d_lo, hipStream_t stream);
+/* ---- the line filter (sre_hip_lines_gather.hip) ---- */
+/* select pass of the batch (lines i0 .. info->i1, at most nmax): d_val[i] = len + 1 of a selected line, else 0;
+ * mode 0: rc != SRE_DECLINED, 1: rc == SRE_DECLINED, 2: every line */
+hipError_t sre_launch_filter_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int mode,
+    const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val, hipStream_t stream);
+/* d_val[0 .. n) becomes the offset table off[0 .. n] in place (n + 1 words); d_blk: 2 x ceil(n / SRE_LINES_ITEMS)
+ * words, the second half keeps the selected lines in front of each workgroup for the index; info->fsel, fneed,
+ * fwritten, fbytes */
+hipError_t sre_launch_filter_offsets(uint64_t *d_val, uint64_t n, uint64_t *d_blk, uint64_t out_cap,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* the gather: output bytes [0, out_bytes) of the selected lines and their delimiters to d_out */
+hipError_t sre_launch_lines_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_ends,
+    uint64_t nlines, uint64_t out_bytes, uint32_t delim, hipStream_t stream);
+/* rows [line, start, len, output offset] of the first min(index_cap, info->fwritten) written lines */
+hipError_t sre_launch_filter_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
+    const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,361 @@
+/*
+ * sre_hip_lines_gather.hip — the line filter on the device (sregex_hip.h sre_hip_filter_lines).
+ *
+ *   select     per batch: val[i] = len + 1 of a selected line, 0 of the others, from the batch's records;
+ *   scan       after the last batch: val becomes the offset table off[0 .. n] in place (per-workgroup sums, a
+ *              single-workgroup scan of the sums, then the prefixes), the sums of the selected lines stay in
+ *              blk for the index; `finish` cuts the output at whole lines that fit out_cap;
+ *   gather     output-driven: a workgroup owns 16 KiB of the output, a lane builds 16-byte chunks of it at a
+ *              stride of the workgroup with the chunk logic of sre_lines_gather.h;
+ *   index      the rows [line, start, len, output offset] of the first written lines.
+ *
+ * No workgroup waits for another.  Plain C++ and vector memory operations only.
+ */
+#include <sregex/sregex.h>
+#include "sre_hip_lines.h"
+#include "sre_lines_gather.h"
+#include "sre_hip_tile.h"
+
+namespace {
+
+/* exclusive prefix of v over the workgroup (NT lanes, a multiple of 64), and the total */
+template <uint32_t NT>
+__device__ inline uint64_t
+block_excl_scan(uint64_t v, uint64_t *wsum, uint64_t &total)
+{
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t       x = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint64_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < NT / 64; i++) {
+        const uint64_t s = wsum[i];
+        before += i < w ? s : 0;
+        all += s;
+    }
+    __syncthreads();
+    total = all;
+    return before + x - v;
+}
+
+__device__ inline uint64_t
+line_start(const uint64_t *ends, uint64_t i)
+{
+    return i == 0 ? 0 : ends[i - 1] + 1;
+}
+
+/* ---- select ---- */
+
+/* lane per line of the batch (lines i0 .. info->i1): mode 0 selects rc != SRE_DECLINED, 1 the others, 2 all */
+__global__ __launch_bounds__(256) void
+sre_k_filter_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t i0, int mode,
+                    const uint64_t *__restrict__ ends, const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ val)
+{
+    const uint64_t nb = info->i1 - i0;
+    const uint64_t j = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (j >= nb) return;
+    const bool     hit = records[j * slots] != SRE_DECLINED;
+    const bool     sel = mode == 2 || hit != (mode == 1);
+    const uint64_t i = i0 + j;
+    val[i] = sel ? ends[i] - line_start(ends, i) + 1 : 0;
+}
+
+/* ---- scan ---- */
+
+/* lane x of workgroup b: lines b * 1024 + 4x .. + 3; the workgroup's bytes and selected lines */
+__global__ __launch_bounds__(256) void
+sre_k_filter_sums(const uint64_t *__restrict__ val, uint64_t n, uint64_t *__restrict__ blkv, uint64_t *__restrict__ blkc)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint64_t            s = 0, k = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        if (q0 + q < n) {
+            const uint64_t v = val[q0 + q];
+            s += v;
+            k += v ? 1 : 0;
+        }
+    }
+    uint64_t ts, tk;
+    (void) block_excl_scan<256>(s, wsum, ts);
+    (void) block_excl_scan<256>(k, wsum, tk);
+    if (threadIdx.x == 0) {
+        blkv[blockIdx.x] = ts;
+        blkc[blockIdx.x] = tk;
+    }
+}
+
+/* in-place exclusive scan of the two arrays of n sums by one workgroup (a contiguous run per lane);
+ * info->fneed / fsel = their totals */
+__global__ __launch_bounds__(1024) void
+sre_k_filter_scan(uint64_t *__restrict__ blkv, uint64_t *__restrict__ blkc, uint64_t n, sre_lines_info_t *__restrict__ info)
+{
+    __shared__ uint64_t wsum[16];
+    const uint64_t      per = (n + 1023) / 1024;
+    const uint64_t      lo = min(n, (uint64_t) threadIdx.x * per), hi = min(n, lo + per);
+    uint64_t            s = 0, k = 0;
+    for (uint64_t i = lo; i < hi; i++) {
+        s += blkv[i];
+        k += blkc[i];
+    }
+    uint64_t ts, tk;
+    uint64_t rs = block_excl_scan<1024>(s, wsum, ts);
+    uint64_t rk = block_excl_scan<1024>(k, wsum, tk);
+    for (uint64_t i = lo; i < hi; i++) {
+        const uint64_t x = blkv[i], y = blkc[i];
+        blkv[i] = rs;
+        blkc[i] = rk;
+        rs += x;
+        rk += y;
+    }
+    if (threadIdx.x == 0) {
+        info->fneed = ts;
+        info->fsel = tk;
+    }
+}
+
+/* val[0 .. n) becomes off[0 .. n] in place: a lane reads its own four values before it writes them */
+__global__ __launch_bounds__(256) void
+sre_k_filter_offsets(uint64_t *__restrict__ val, uint64_t n, const uint64_t *__restrict__ blkv)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint64_t            v[4], s = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        v[q] = q0 + q < n ? val[q0 + q] : 0;
+        s += v[q];
+    }
+    uint64_t total;
+    uint64_t run = blkv[blockIdx.x] + block_excl_scan<256>(s, wsum, total);
+    for (uint32_t q = 0; q < 4; q++) {
+        if (q0 + q >= n) break;
+        val[q0 + q] = run;
+        run += v[q];
+        if (q0 + q == n - 1) val[n] = run;
+    }
+}
+
+/* one workgroup: the first line i whose end lies beyond out_cap (n when all fit) cuts the output:
+ * info->fbytes = off[i], info->fwritten = selected lines in front of i */
+__global__ __launch_bounds__(1024) void
+sre_k_filter_finish(const uint64_t *__restrict__ off, uint64_t n, const uint64_t *__restrict__ blkc, uint64_t out_cap,
+                    sre_lines_info_t *__restrict__ info)
+{
+    __shared__ uint64_t cut;
+    if (threadIdx.x == 0) {
+        uint64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (off[mid + 1] > out_cap) hi = mid;
+            else lo = mid + 1;
+        }
+        cut = lo;
+    }
+    __syncthreads();
+    const uint64_t i = cut, b = i / SRE_LINES_ITEMS, j = b * SRE_LINES_ITEMS + threadIdx.x;
+    const int      before = __syncthreads_count(j < i && off[j + 1] > off[j]);
+    if (threadIdx.x == 0) {
+        info->fbytes = off[i];
+        info->fwritten = i == n ? info->fsel : blkc[b] + (uint64_t) before;
+    }
+}
+
+/* ---- gather ---- */
+
+typedef const __attribute__((address_space(1))) sre_u32x4_unaligned *lg_unaligned_ptr;
+
+/* 16-byte loads and stores of the two aligned extents (sre_lines_gather.h) */
+struct GatherMem {
+    const uint8_t *src;         /* the 16-byte aligned address at or below d_buf */
+    uint8_t       *dst;         /* ... at or below d_out */
+
+    __device__ inline sre_lg_u128 load(uint64_t q) const
+    {
+        const uint4 v = reinterpret_cast<const uint4 *>(src)[q];
+        sre_lg_u128 r;
+        r.lo = ((uint64_t) v.y << 32) | v.x;
+        r.hi = ((uint64_t) v.w << 32) | v.z;
+        return r;
+    }
+    __device__ inline sre_lg_u128 loadu(uint64_t s) const
+    {
+        /* any alignment, which the hardware handles (as sre_hip_tile.h loads its rows) */
+        const sre_u32x4 v = *reinterpret_cast<lg_unaligned_ptr>(reinterpret_cast<uintptr_t>(src) + s);
+        sre_lg_u128     r;
+        r.lo = ((uint64_t) v.y << 32) | v.x;
+        r.hi = ((uint64_t) v.w << 32) | v.z;
+        return r;
+    }
+    __device__ inline void store(uint64_t c, sre_lg_u128 v) const
+    {
+        reinterpret_cast<uint4 *>(dst)[c] = make_uint4((uint32_t) v.lo, (uint32_t) (v.lo >> 32), (uint32_t) v.hi, (uint32_t) (v.hi >> 32));
+    }
+    __device__ inline void store_bytes(uint64_t c, sre_lg_u128 v, uint32_t first, uint32_t count) const
+    {
+        for (uint32_t k = first; k < first + count; k++) {
+            dst[c * 16 + k] = (uint8_t) ((k < 8 ? v.lo >> (8 * k) : v.hi >> (8 * (k - 8))) & 0xFFu);
+        }
+    }
+};
+
+/* sre_lg_find over the global table by a whole wave: 64 probes a step, so a table of a million lines takes four
+ * dependent loads instead of twenty.  Every lane of the wave calls it and gets the same answer */
+__device__ inline uint64_t
+wave_find(const uint64_t *__restrict__ off, uint64_t o, uint64_t lo, uint64_t hi)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    while (hi - lo >= 64) {
+        /* probes lo + step, lo + 2 step, ..: the last one is at or beyond hi and clamped to it */
+        const uint64_t step = (hi - lo + 63) / 64;
+        const uint64_t p = min(lo + step * (lane + 1), hi);
+        const uint32_t k = (uint32_t) __popcll(__ballot(off[p] <= o));     /* monotone: the first k probes hold */
+        if (k == 64) return hi;
+        const uint64_t nlo = k ? lo + step * k : lo;
+        hi = min(lo + step * (k + 1), hi + 1) - 1;
+        lo = nlo;
+    }
+    const uint64_t p = lo + 1 + lane;
+    return lo + (uint32_t) __popcll(__ballot(p <= hi && off[p] <= o));
+}
+
+template <class Tab>
+__device__ inline void
+gather_tile(const Tab &tab, const sre_lg_geom_t &g, uint64_t la, uint64_t lb, const GatherMem &mem)
+{
+    const uint64_t nchunks = sre_lg_nchunks(g);
+    const uint64_t c0 = (uint64_t) blockIdx.x * SRE_LG_TILE_CHUNKS + threadIdx.x;
+#pragma unroll
+    for (uint32_t k = 0; k < SRE_LG_CHUNKS; k++) {
+        const uint64_t c = c0 + (uint64_t) k * SRE_LG_THREADS;
+        if (c < nchunks) sre_lg_chunk(tab, g, c, la, lb, mem);
+    }
+}
+
+__global__ __launch_bounds__(SRE_LG_THREADS) void
+sre_k_lines_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const uint64_t *__restrict__ off,
+                   const uint64_t *__restrict__ ends, sre_lg_geom_t g)
+{
+    __shared__ uint64_t w_off[SRE_LG_WINDOW + 1], w_start[SRE_LG_WINDOW], slice[2];
+    const sre_lg_tab_global tab = {off, ends};
+    const GatherMem         mem = {src, dst};
+    /* the tile's slice of the table, found once: wave 0 searches the line of the tile's first byte, wave 1 that
+     * of its last byte */
+    if (threadIdx.x < 128) {
+        uint64_t o_lo = 0, o_hi = 1;
+        (void) sre_lg_span(g, (uint64_t) blockIdx.x * SRE_LG_TILE_CHUNKS, ((uint64_t) blockIdx.x + 1) * SRE_LG_TILE_CHUNKS, &o_lo,
+                           &o_hi);
+        const uint64_t i = wave_find(off, threadIdx.x < 64 ? o_lo : o_hi - 1, 0, g.nlines - 1);
+        if ((threadIdx.x & 63u) == 0) slice[threadIdx.x >> 6] = i;
+    }
+    __syncthreads();
+    const uint64_t la = slice[0], lb = slice[1], cnt = lb - la + 1;
+    if (cnt <= SRE_LG_WINDOW) {
+        for (uint64_t x = threadIdx.x; x <= cnt; x += SRE_LG_THREADS) {
+            w_off[x] = off[la + x];
+            if (x < cnt) w_start[x] = tab.start(la + x);
+        }
+        __syncthreads();
+        const sre_lg_tab_window win = {w_off, w_start, la};
+        gather_tile(win, g, la, lb, mem);
+    } else {
+        /* more lines than the window holds (up to one line per output byte when every selected line is
+         * empty, and any number of unselected ones): the lanes search the slice in the global table */
+        gather_tile(tab, g, la, lb, mem);
+    }
+}
+
+/* ---- index ---- */
+
+/* rows of the first `limit` written lines, limit = min(index_cap, info->fwritten); workgroups as in the scan */
+__global__ __launch_bounds__(256) void
+sre_k_filter_index(const uint64_t *__restrict__ off, const uint64_t *__restrict__ ends, uint64_t n,
+                   const uint64_t *__restrict__ blkc, const sre_lines_info_t *__restrict__ info, uint64_t index_cap,
+                   int64_t *__restrict__ rows)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      limit = index_cap < info->fwritten ? index_cap : info->fwritten;
+    if (blkc[blockIdx.x] >= limit) return;      /* (the whole workgroup) */
+    const uint64_t q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint32_t       f[4];
+    uint64_t       s = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        f[q] = q0 + q < n && off[q0 + q + 1] > off[q0 + q];
+        s += f[q];
+    }
+    uint64_t total;
+    uint64_t r = blkc[blockIdx.x] + block_excl_scan<256>(s, wsum, total);
+    for (uint32_t q = 0; q < 4; q++) {
+        if (!f[q]) continue;
+        if (r < limit) {
+            const uint64_t i = q0 + q, st = line_start(ends, i);
+            int64_t       *row = rows + r * 4;
+            row[0] = (int64_t) i;
+            row[1] = (int64_t) st;
+            row[2] = (int64_t) (ends[i] - st);
+            row[3] = (int64_t) off[i];
+        }
+        r++;
+    }
+}
+
+}  // namespace
+
+extern "C" hipError_t
+sre_launch_filter_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int mode,
+                         const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val, hipStream_t stream)
+{
+    if (nmax == 0) return hipSuccess;
+    hipLaunchKernelGGL(sre_k_filter_select, dim3((uint32_t) ((nmax + 255) / 256)), dim3(256), 0, stream, d_records, slots, i0,
+                       mode, d_ends, d_info, d_val);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_filter_offsets(uint64_t *d_val, uint64_t n, uint64_t *d_blk, uint64_t out_cap, sre_lines_info_t *d_info,
+                          hipStream_t stream)
+{
+    if (n == 0) return hipErrorInvalidValue;
+    const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    uint64_t      *blkv = d_blk, *blkc = d_blk + nblk;
+    hipLaunchKernelGGL(sre_k_filter_sums, dim3((uint32_t) nblk), dim3(256), 0, stream, d_val, n, blkv, blkc);
+    hipLaunchKernelGGL(sre_k_filter_scan, dim3(1), dim3(1024), 0, stream, blkv, blkc, nblk, d_info);
+    hipLaunchKernelGGL(sre_k_filter_offsets, dim3((uint32_t) nblk), dim3(256), 0, stream, d_val, n, blkv);
+    hipLaunchKernelGGL(sre_k_filter_finish, dim3(1), dim3(1024), 0, stream, d_val, n, blkc, out_cap, d_info);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_lines_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_ends, uint64_t nlines,
+                        uint64_t out_bytes, uint32_t delim, hipStream_t stream)
+{
+    if (out_bytes == 0) return hipSuccess;
+    sre_lg_geom_t g;
+    g.nlines = nlines;
+    g.out_bytes = out_bytes;
+    g.src_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_buf) & 15u);
+    g.dst_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_out) & 15u);
+    g.delim = delim;
+    const uint64_t ntiles = (sre_lg_nchunks(g) + SRE_LG_TILE_CHUNKS - 1) / SRE_LG_TILE_CHUNKS;
+    if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_lines_gather, dim3((uint32_t) ntiles), dim3(SRE_LG_THREADS), 0, stream,
+                       static_cast<const uint8_t *>(d_buf) - g.src_head, static_cast<uint8_t *>(d_out) - g.dst_head, d_off, d_ends,
+                       g);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_filter_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
+                        const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream)
+{
+    if (n == 0 || index_cap == 0) return hipSuccess;
+    const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    hipLaunchKernelGGL(sre_k_filter_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_ends, n, d_blk + nblk, d_info,
+                       index_cap, d_index);
+    return hipGetLastError();
+}
