@@ -299,6 +299,65 @@ SRE_API int sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_
     int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap,
     sre_hip_filter_info_t *info, void *hip_stream);
 
+/* ---- line extract: capture groups of each matching line as delimited rows in a device buffer ---- */
+
+enum { SRE_HIP_EXTRACT_MAX_FIELDS = 32 };
+
+/*
+ * Line extract: the text of chosen capture groups of every matching line, as rows of fields in
+ * device memory (cuDF extract, regexp_extract, sed -n 's/../\1/p').  The split of d_buf, the
+ * matching of every line and the engine a scanner routes to are exactly those of
+ * sre_hip_scan_lines on the same (sc, d_buf, len, delim).  sc must have been created with
+ * SRE_HIP_PIKE_FIRST: a line's record then holds the captures of its FIRST match, and those are
+ * the only ones offered.  Thompson and COUNT scanners return -1 with a diagnostic on stderr.
+ *
+ * Groups.  groups[0 .. ngroups) are capture group numbers, 0 the whole match, in any order, with
+ * repeats allowed; 1 <= ngroups <= SRE_HIP_EXTRACT_MAX_FIELDS and every group lies in
+ * [0, max_ncaps] (max_ncaps = (result_slots - 2) / 2 - 1), anything else returns -1.  With
+ * several regexes the group is that of the regex that matched, as the record's ovector has it.
+ *
+ * Which lines are selected:
+ *   - flags == 0: the lines whose rc is not SRE_DECLINED;
+ *   - SRE_HIP_LINES_ALL: every line, a line without a match with every field unset, so row i of
+ *     the output is line i of the input;
+ *   - SRE_HIP_LINES_INVERT, and any other bit, return -1.
+ *
+ * Output.  Each selected line gives one row, in line order: field 0, fsep, field 1, fsep, ..,
+ * field K - 1, delim (K = ngroups, fsep a byte 0..255, for instance '\t').  Field f is the bytes
+ * [ov[2g], ov[2g + 1]) of the line for g = groups[f], and empty when the group is unset
+ * (ov[2g] < 0 or ov[2g + 1] < ov[2g]) or the line has no match.  Nothing is escaped: a field may
+ * contain fsep; it cannot contain delim.  Fields may overlap or nest.  d_out is a DEVICE pointer
+ * at any alignment to out_cap bytes that do not overlap [d_buf, d_buf + len) (an overlap returns
+ * -1).  info->need_bytes is the sum over the selected lines of (field lengths + K) whatever
+ * out_cap is; info->nselected counts lines.
+ *
+ * Truncation.  Only whole rows are written: info->nwritten is the largest k for which the first
+ * k rows take at most out_cap bytes, info->out_bytes that total.  No byte of d_out at or beyond
+ * out_bytes is touched and nothing is written in front of d_out.  d_out may be NULL when
+ * out_cap == 0 (a sizing call).
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten)
+ * rows it receives 4 + 2 * ngroups sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the row in d_out
+ *   then per field [offset of the field in d_buf, length], or [-1, -1] for an unset field (how
+ *   a caller tells unset from empty).
+ * d_index may be NULL when index_cap == 0.  info may be NULL.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  It replaces the scanner's last
+ * call and the diagnostics describe it exactly as for sre_hip_filter_lines.  On the device
+ * routes (the table-driven scanner; first match on the NFA tier, 64-bit and wide forms) the host
+ * reads a fixed number of words per batch and per call; on the host route (the exact VM,
+ * SRE_HIP_LINES_NFA_HOST=1) the host fills the per-field values from the records it holds and
+ * uploads them batch by batch.  len == 0 gives all zeros in info and success.  Beyond what line
+ * mode takes, a scanner keeps 16 bytes per line and field of the largest call (plus 16 bytes
+ * per 1024 of them) of device memory, grow-only, shared with sre_hip_filter_lines, freed with
+ * the scanner.  Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_extract_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, int fsep, int flags, void *d_out, size_t out_cap,
+    sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

@@ -27,6 +27,7 @@ HIP_THOMPSON, HIP_PIKE_FIRST, HIP_PIKE_COUNT = 0, 1, 2
 ENGINE_AUTO, ENGINE_VM, ENGINE_SCAN, ENGINE_NFA = 0, 1, 2, 3
 HIP_LINES_ALL = 1
 HIP_LINES_INVERT = 2
+HIP_EXTRACT_MAX_FIELDS = 32
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -80,6 +81,8 @@ API = {
     "sre_hip_scan_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _pssz, _sz,
                                           ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
     "sre_hip_filter_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_extract_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int,
+                                             ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -417,6 +420,22 @@ class Scanner:
         if self.lib.sre_hip_filter_lines(self.h, ptr, length, delim, flags, out_ptr, out_cap, index_ptr, index_cap,
                                          info, hip_stream) != 0:
             raise RuntimeError("sre_hip_filter_lines failed")
+        return FilterInfo(*info)
+
+    def extract_lines(self, ptr, length, groups, out_ptr, out_cap, delim=0x0A, fsep=0x09, all_lines=False, index_ptr=None,
+                      index_cap=0, hip_stream=None):
+        """sre_hip_extract_lines: for every matching line of the device buffer (ptr, length) (every line with
+        all_lines) one row in the device buffer (out_ptr, out_cap): the text of the capture groups `groups` of the
+        line's first match, separated by fsep and ended by delim; an unset group is an empty field.  index_ptr: an
+        optional device array of index_cap rows [line no, offset in the buffer, length, offset of the row in the
+        output] + [offset in the buffer, length] per field ([-1, -1]: unset).  The scanner's mode must be
+        HIP_PIKE_FIRST.  Returns FilterInfo(nlines, nselected, need_bytes, nwritten, out_bytes), counts of lines."""
+        groups = list(groups)
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        info = (_sz * 5)()
+        if self.lib.sre_hip_extract_lines(self.h, ptr, length, delim, arr, len(groups), fsep, HIP_LINES_ALL if all_lines else 0,
+                                          out_ptr, out_cap, index_ptr, index_cap, info, hip_stream) != 0:
+            raise RuntimeError("sre_hip_extract_lines failed")
         return FilterInfo(*info)
 
     @property

@@ -20,6 +20,7 @@
 #include "sre_hip_nfa_wide.h"
 #include "sre_pwave.h"
 #include "sre_hip_lines.h"
+#include "sre_lines_gather.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
 #include <stdio.h>
@@ -136,6 +137,9 @@ struct sre_hip_scanner_s {
     size_t                    fval_cap;
     uint64_t                 *d_fblk;           /* per-workgroup sums of the scan: 2 words per SRE_LINES_ITEMS lines */
     size_t                    fblk_cap;
+    /* the line extract (sre_hip_extract_lines) shares both, sized by its entries (lines x fields), and adds */
+    uint64_t                 *d_fstart;         /* per-entry source offsets under their flags: lines x fields words */
+    size_t                    fstart_cap;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -195,6 +199,7 @@ scanner_release(void *data)
     if (sc->d_rows) (void) hipFree(sc->d_rows);
     if (sc->d_fval) (void) hipFree(sc->d_fval);
     if (sc->d_fblk) (void) hipFree(sc->d_fblk);
+    if (sc->d_fstart) (void) hipFree(sc->d_fstart);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -1570,12 +1575,28 @@ hip_failed:
 struct LinesSink {
     int       mode;     /* 0: the lines with a match, 1: the lines without one, 2: every line */
     uint64_t *d_val;    /* one word per line of the call */
+    /* the line extract (sre_hip_extract_lines): with groups, the select pass is the extract's over the entries
+     * line * k + field, d_val has one word per entry and d_start the entries' source offsets; mode is 0 or 2 */
+    const sre_extract_groups_t *groups;
+    uint64_t                   *d_start;
 };
 
 static bool
 sink_selects(const LinesSink *sink, sre_int_t rc)
 {
     return sink->mode == 2 || (rc != SRE_DECLINED) != (sink->mode == 1);
+}
+
+/* the select pass of a device batch (lines i0 .. d_linfo->i1, at most nmax) from its records */
+static hipError_t
+sink_select(sre_hip_scanner_t *sc, const LinesSink *sink, size_t slots, uint64_t nmax, uint64_t i0, hipStream_t stream)
+{
+    if (sink->groups) {
+        return sre_launch_extract_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->groups, sc->d_ends,
+                                         sc->d_linfo, sink->d_val, sink->d_start, stream);
+    }
+    return sre_launch_filter_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode, sc->d_ends, sc->d_linfo, sink->d_val,
+                                    stream);
 }
 
 /* table-driven scanner: every batch on the device; the host reads a few words per batch */
@@ -1634,8 +1655,7 @@ lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all,
         if (scan_settle(sc, nb, stream, true, NULL, true) != 0) return -1;
         if (sc->mode != SRE_HIP_THOMPSON && sc->h_linfo->maps != 0 && scan_lineage_pass(sc, stream) != 0) return -1;
         if (sink) {
-            SRE_HIP_TRY(sre_launch_filter_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode, sc->d_ends, sc->d_linfo,
-                                                 sink->d_val, stream));
+            SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
         } else {
             SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
                                                  sc->d_linfo, sc->d_rows, rcap, stream));
@@ -1782,8 +1802,7 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
             }
         }
         if (sink) {
-            SRE_HIP_TRY(sre_launch_filter_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode, sc->d_ends, sc->d_linfo,
-                                                 sink->d_val, stream));
+            SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
         } else {
             SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
                                                  sc->d_linfo, sc->d_rows, rcap, stream));
@@ -1839,6 +1858,7 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
     std::vector<size_t>       lens;
     std::vector<sre_int_t>    recs;
     std::vector<uint64_t>     vals;             /* with a sink: the batch's per-line values, uploaded */
+    std::vector<uint64_t>     starts;           /* ... of the line extract: and the per-entry source offsets */
     uint64_t                  nrep = 0;
     for (uint64_t i0 = 0; i0 < n;) {
         const uint64_t nb = bmax < n - i0 ? bmax : n - i0;
@@ -1864,7 +1884,29 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
         *lineage += sc->lineage_passes;
         const double ms = sre_hip_scanner_last_kernel_ms(sc);
         *kms = (ms < 0 || *kms < 0) ? -1.0 : *kms + ms;
-        if (sink) {
+        if (sink && sink->groups) {
+            /* what sre_k_extract_select writes, from the records the host holds */
+            const uint32_t k = sink->groups->k;
+            vals.resize(nb * k);
+            starts.resize(nb * k);
+            for (uint64_t j = 0; j < nb; j++) {
+                const sre_int_t *rec = recs.data() + j * slots;
+                const bool       hit = rec[0] != SRE_DECLINED;
+                const uint64_t   st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf);
+                for (uint32_t f = 0; f < k; f++) {
+                    const uint32_t  g = sink->groups->g[f];
+                    const sre_int_t a = hit ? rec[2 + 2 * g] : -1, b = hit ? rec[3 + 2 * g] : -1;
+                    const bool      set = a >= 0 && b >= a && (uint64_t) b <= lens[j];
+                    vals[j * k + f] = (hit || sink->mode == 2) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
+                    starts[j * k + f] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
+                                        | (f + 1 == k ? SRE_LG_ENTRY_LAST : 0);
+                }
+            }
+            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0 * k, vals.data(), nb * k * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            SRE_HIP_TRY(hipMemcpyAsync(sink->d_start + i0 * k, starts.data(), nb * k * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                       stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        } else if (sink) {
             vals.resize(nb);
             for (uint64_t j = 0; j < nb; j++) vals[j] = sink_selects(sink, recs[j * slots]) ? (uint64_t) lens[j] + 1 : 0;
             SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0, vals.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
@@ -1912,8 +1954,13 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
     if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
     if (lines_split(sc, d_buf, len, delim, stream, &n) == 0) {
         if (sink) {
-            if (lines_grow(&sc->d_fval, &sc->fval_cap, (n + 1) * sizeof(uint64_t)) != 0) goto hip_failed;
+            const uint64_t k = sink->groups ? sink->groups->k : 1;
+            if (lines_grow(&sc->d_fval, &sc->fval_cap, (n * k + 1) * sizeof(uint64_t)) != 0) goto hip_failed;
             sink->d_val = sc->d_fval;
+            if (sink->groups) {
+                if (lines_grow(&sc->d_fstart, &sc->fstart_cap, n * k * sizeof(uint64_t)) != 0) goto hip_failed;
+                sink->d_start = sc->d_fstart;
+            }
         }
         rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms, sink)
              : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &kms, &nshort, sink)
@@ -1974,7 +2021,7 @@ sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
         if (o < b + len && b < o + out_cap) return -1;
     }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0, NULL};
+    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0, NULL, NULL, NULL};
     uint64_t    n = 0, nrep = 0;
     if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
     sre_hip_filter_info_t res;
@@ -1994,6 +2041,68 @@ sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
         SRE_HIP_TRY(sre_launch_lines_gather(d_buf, d_out, sc->d_fval, sc->d_ends, n, res.out_bytes, (uint32_t) delim, stream));
         if (res.nwritten != 0) {
             SRE_HIP_TRY(sre_launch_filter_index(sc->d_fval, sc->d_ends, n, sc->d_fblk, sc->d_linfo, index_cap, d_index, stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The line extract: the line-mode call with the extract's sink, then the filter's passes over the
+ * entries (lines x fields): scan, cut at a line boundary, one read of four words, gather, index rows. */
+extern "C" SRE_API int
+sre_hip_extract_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+    int fsep, int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info,
+    void *hip_stream)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0
+        || groups == NULL || ngroups < 1 || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (out_cap != 0 && d_out == NULL)
+        || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    if (sc->mode != SRE_HIP_PIKE_FIRST) {
+        fprintf(stderr, "[sregex-hip] line extract: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
+        return -1;
+    }
+    sre_extract_groups_t gr;
+    memset(&gr, 0, sizeof(gr));
+    gr.k = (uint32_t) ngroups;
+    for (size_t f = 0; f < ngroups; f++) {
+        /* ovec_slots = 2 * (max_ncaps + 1) */
+        if (groups[f] < 0 || groups[f] > 0xFFFF || 2 * (size_t) groups[f] + 1 >= (size_t) sc->ovec_slots) return -1;
+        gr.g[f] = (uint16_t) groups[f];
+    }
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, &gr, NULL};
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_filter_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        const uint64_t nent = n * gr.k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+        SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_fval, n, gr.k, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nselected = (size_t) sc->h_linfo->fsel;
+        res.need_bytes = (size_t) sc->h_linfo->fneed;
+        res.nwritten = (size_t) sc->h_linfo->fwritten;
+        res.out_bytes = (size_t) sc->h_linfo->fbytes;
+        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
+        SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, nent, res.out_bytes, (uint32_t) delim,
+                                              (uint32_t) fsep, stream));
+        if (res.nwritten != 0) {
+            SRE_HIP_TRY(sre_launch_extract_index(sc->d_fval, sc->d_fstart, sc->d_ends, n, gr.k, sc->d_fblk, sc->d_linfo, index_cap,
+                                                 d_index, stream));
         }
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }

@@ -107,6 +107,31 @@ hipError_t sre_launch_lines_gather(const void *d_buf, void *d_out, const uint64_
 /* rows [line, start, len, output offset] of the first min(index_cap, info->fwritten) written lines */
 hipError_t sre_launch_filter_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
     const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
+/* ---- the line extract (sre_hip_lines_gather.hip) ---- */
+#define SRE_EXTRACT_MAX_FIELDS 32u
+/* the chosen capture groups: field f of a row is group g[f] of the line's record */
+typedef struct {
+    uint32_t k;
+    uint16_t g[SRE_EXTRACT_MAX_FIELDS];
+} sre_extract_groups_t;
+/* select pass of the batch over its entries e = line * k + f: d_val[e] = field length + 1 for every field of a
+ * selected line (rc != SRE_DECLINED, or every line with `all`), else 0; d_start[e] = the field's offset in the buffer
+ * under the flag bits of sre_lines_gather.h.  A batch may have at most 2^32 - 1 entries */
+hipError_t sre_launch_extract_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int all,
+    const sre_extract_groups_t *groups, const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val,
+    uint64_t *d_start, hipStream_t stream);
+/* sre_launch_filter_offsets over the n * k entries (n * k + 1 words; d_blk: 2 x ceil(n * k / SRE_LINES_ITEMS)), the
+ * cut made at a line boundary; info->fsel and fwritten count lines */
+hipError_t sre_launch_extract_offsets(uint64_t *d_val, uint64_t n, uint32_t k, uint64_t *d_blk, uint64_t out_cap,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* the gather over the entry table: output bytes [0, out_bytes) of the rows to d_out */
+hipError_t sre_launch_extract_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_start,
+    uint64_t nentries, uint64_t out_bytes, uint32_t delim, uint32_t fsep, hipStream_t stream);
+/* rows [line, start, len, output offset, (field offset, field length) x k] of the first min(index_cap,
+ * info->fwritten) written rows; an unset field is (-1, -1) */
+hipError_t sre_launch_extract_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, uint64_t n,
+    uint32_t k, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
+    hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

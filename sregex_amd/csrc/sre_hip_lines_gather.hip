@@ -9,6 +9,11 @@
  *              stride of the workgroup with the chunk logic of sre_lines_gather.h;
  *   index      the rows [line, start, len, output offset] of the first written lines.
  *
+ * The line extract (sre_hip_extract_lines) runs the same passes over a table of entries
+ * e = line * K + f, one per chosen capture group of a line: its own select (field length + 1 and the field's
+ * source offset, from the batch's records), the same scan kernels over n * K entries with the cut made at a line
+ * boundary, the gather over the entry table (sre_lg_tab_fields) and index rows of 4 + 2 K words.
+ *
  * No workgroup waits for another.  Plain C++ and vector memory operations only.
  */
 #include <sregex/sregex.h>
@@ -64,6 +69,33 @@ sre_k_filter_select(const int64_t *__restrict__ records, uint32_t slots, uint64_
     const bool     sel = mode == 2 || hit != (mode == 1);
     const uint64_t i = i0 + j;
     val[i] = sel ? ends[i] - line_start(ends, i) + 1 : 0;
+}
+
+/* the line extract's: LANE PER ENTRY of the batch, entry x = j * K + f of line i0 + j.  The stores of val and start
+ * are then consecutive words of consecutive lanes; the K lanes of a line read the same record, whose two ovector
+ * words lie in the cache lines the neighbouring lanes read too (a lane per line would read the same records and
+ * scatter 2 K stores at a stride of K words).  val = field length + 1 for every entry of a selected line, else 0;
+ * start = the field's source offset (the line's start for an unset field) under the flags of sre_lines_gather.h */
+__global__ __launch_bounds__(256) void
+sre_k_extract_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t i0, int all, sre_extract_groups_t gr,
+                     const uint64_t *__restrict__ ends, const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ val,
+                     uint64_t *__restrict__ start)
+{
+    const uint64_t nb = info->i1 - i0;
+    const uint64_t x = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (x >= nb * gr.k) return;
+    const uint32_t j = (uint32_t) x / gr.k, f = (uint32_t) x - j * gr.k;       /* (a batch has fewer than 2^32 entries) */
+    const int64_t *rec = records + (uint64_t) j * slots;
+    const bool     hit = rec[0] != SRE_DECLINED;
+    const uint64_t i = i0 + j, st = line_start(ends, i), len = ends[i] - st;
+    const uint32_t g = gr.g[f];
+    const int64_t  a = hit ? rec[2 + 2 * g] : -1, b = hit ? rec[3 + 2 * g] : -1;
+    /* (a set group lies inside its line; anything else counts as unset and can never reach outside the buffer) */
+    const bool     set = a >= 0 && b >= a && (uint64_t) b <= len;
+    const uint64_t e = (i0 * gr.k) + x;
+    val[e] = (hit || all) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
+    start[e] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
+               | (f + 1 == gr.k ? SRE_LG_ENTRY_LAST : 0);
 }
 
 /* ---- scan ---- */
@@ -166,6 +198,28 @@ sre_k_filter_finish(const uint64_t *__restrict__ off, uint64_t n, const uint64_t
     }
 }
 
+/* the same over the entry table of n lines x k fields: the cut is the first LINE i with off[(i + 1) k] > out_cap,
+ * so a row is written whole or not at all.  The sums counted selected entries; all k entries of a selected line
+ * are selected, so the entries in front of a line boundary divide by k exactly: info->fsel and info->fwritten
+ * become counts of lines.  (k need not divide the entries of a workgroup: the boundary entry i k lies anywhere in
+ * its workgroup, and the count in front of it is taken there.) */
+__global__ __launch_bounds__(1024) void
+sre_k_extract_finish(const uint64_t *__restrict__ off, uint64_t n, uint64_t k, const uint64_t *__restrict__ blkc,
+                     uint64_t out_cap, sre_lines_info_t *__restrict__ info)
+{
+    __shared__ uint64_t cut;
+    if (threadIdx.x == 0) cut = sre_lg_row_cut(off, n, k, out_cap);
+    __syncthreads();
+    const uint64_t i = cut, e = i * k, b = e / SRE_LINES_ITEMS, j = b * SRE_LINES_ITEMS + threadIdx.x;
+    const int      before = __syncthreads_count(j < e && off[j + 1] > off[j]);
+    if (threadIdx.x == 0) {
+        const uint64_t sel = info->fsel / k;
+        info->fsel = sel;
+        info->fbytes = off[e];
+        info->fwritten = i == n ? sel : (blkc[b] + (uint64_t) before) / k;
+    }
+}
+
 /* ---- gather ---- */
 
 typedef const __attribute__((address_space(1))) sre_u32x4_unaligned *lg_unaligned_ptr;
@@ -237,13 +291,25 @@ gather_tile(const Tab &tab, const sre_lg_geom_t &g, uint64_t la, uint64_t lb, co
     }
 }
 
-__global__ __launch_bounds__(SRE_LG_THREADS) void
-sre_k_lines_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const uint64_t *__restrict__ off,
-                   const uint64_t *__restrict__ ends, sre_lg_geom_t g)
+/* what a window keeps of entry i of the table: the line's start, resp. the entry's start word with its flags */
+__device__ inline uint64_t
+window_start(const sre_lg_tab_global &tab, uint64_t i)
 {
-    __shared__ uint64_t w_off[SRE_LG_WINDOW + 1], w_start[SRE_LG_WINDOW], slice[2];
-    const sre_lg_tab_global tab = {off, ends};
-    const GatherMem         mem = {src, dst};
+    return tab.start(i);
+}
+
+__device__ inline uint64_t
+window_start(const sre_lg_tab_fields &tab, uint64_t i)
+{
+    return tab.raw(i);
+}
+
+/* one tile of the output over the table `tab` (global memory), WTab its window type */
+template <class GTab, class WTab>
+__device__ inline void
+gather_body(const GTab &tab, const uint64_t *__restrict__ off, const sre_lg_geom_t &g, const GatherMem &mem, uint64_t *w_off,
+            uint64_t *w_start, uint64_t *slice)
+{
     /* the tile's slice of the table, found once: wave 0 searches the line of the tile's first byte, wave 1 that
      * of its last byte */
     if (threadIdx.x < 128) {
@@ -258,16 +324,37 @@ sre_k_lines_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, c
     if (cnt <= SRE_LG_WINDOW) {
         for (uint64_t x = threadIdx.x; x <= cnt; x += SRE_LG_THREADS) {
             w_off[x] = off[la + x];
-            if (x < cnt) w_start[x] = tab.start(la + x);
+            if (x < cnt) w_start[x] = window_start(tab, la + x);
         }
         __syncthreads();
-        const sre_lg_tab_window win = {w_off, w_start, la};
+        const WTab win = {w_off, w_start, la};
         gather_tile(win, g, la, lb, mem);
     } else {
         /* more lines than the window holds (up to one line per output byte when every selected line is
          * empty, and any number of unselected ones): the lanes search the slice in the global table */
         gather_tile(tab, g, la, lb, mem);
     }
+}
+
+__global__ __launch_bounds__(SRE_LG_THREADS) void
+sre_k_lines_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const uint64_t *__restrict__ off,
+                   const uint64_t *__restrict__ ends, sre_lg_geom_t g)
+{
+    __shared__ uint64_t w_off[SRE_LG_WINDOW + 1], w_start[SRE_LG_WINDOW], slice[2];
+    const sre_lg_tab_global tab = {off, ends};
+    const GatherMem         mem = {src, dst};
+    gather_body<sre_lg_tab_global, sre_lg_tab_window>(tab, off, g, mem, w_off, w_start, slice);
+}
+
+/* the line extract's: g.nlines counts entries, the window holds at most SRE_LG_WINDOW of them */
+__global__ __launch_bounds__(SRE_LG_THREADS) void
+sre_k_extract_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const uint64_t *__restrict__ off,
+                     const uint64_t *__restrict__ starts, sre_lg_geom_t g)
+{
+    __shared__ uint64_t w_off[SRE_LG_WINDOW + 1], w_start[SRE_LG_WINDOW], slice[2];
+    const sre_lg_tab_fields tab = {off, starts, 0};
+    const GatherMem         mem = {src, dst};
+    gather_body<sre_lg_tab_fields, sre_lg_tab_fields>(tab, off, g, mem, w_off, w_start, slice);
 }
 
 /* ---- index ---- */
@@ -299,6 +386,46 @@ sre_k_filter_index(const uint64_t *__restrict__ off, const uint64_t *__restrict_
             row[1] = (int64_t) st;
             row[2] = (int64_t) (ends[i] - st);
             row[3] = (int64_t) off[i];
+        }
+        r++;
+    }
+}
+
+/* the line extract's rows, 4 + 2 k words: workgroups over the ENTRIES as in the scan; the lane that holds the first
+ * entry of a selected line writes the line's row.  Its rank is the selected entries in front of it over k */
+__global__ __launch_bounds__(256) void
+sre_k_extract_index(const uint64_t *__restrict__ off, const uint64_t *__restrict__ starts, const uint64_t *__restrict__ ends,
+                    uint64_t nent, uint64_t k, const uint64_t *__restrict__ blkc, const sre_lines_info_t *__restrict__ info,
+                    uint64_t index_cap, int64_t *__restrict__ rows)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      limit = index_cap < info->fwritten ? index_cap : info->fwritten;
+    if (blkc[blockIdx.x] >= limit * k) return;      /* (the whole workgroup) */
+    const uint64_t q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint32_t       f[4];
+    uint64_t       s = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        f[q] = q0 + q < nent && off[q0 + q + 1] > off[q0 + q];
+        s += f[q];
+    }
+    uint64_t total;
+    uint64_t r = blkc[blockIdx.x] + block_excl_scan<256>(s, wsum, total);
+    for (uint32_t q = 0; q < 4; q++) {
+        if (!f[q]) continue;
+        const uint64_t e = q0 + q;
+        if ((starts[e] & SRE_LG_ENTRY_FIRST) && r / k < limit) {
+            const uint64_t i = e / k, st = line_start(ends, i);
+            int64_t       *row = rows + (r / k) * (4 + 2 * k);
+            row[0] = (int64_t) i;
+            row[1] = (int64_t) st;
+            row[2] = (int64_t) (ends[i] - st);
+            row[3] = (int64_t) off[e];
+            for (uint64_t x = 0; x < k; x++) {
+                const uint64_t w = starts[e + x];
+                const bool     unset = (w & SRE_LG_ENTRY_UNSET) != 0;
+                row[4 + 2 * x] = unset ? -1 : (int64_t) (w & SRE_LG_ENTRY_START);
+                row[5 + 2 * x] = unset ? -1 : (int64_t) (off[e + x + 1] - off[e + x] - 1);
+            }
         }
         r++;
     }
@@ -341,6 +468,7 @@ sre_launch_lines_gather(const void *d_buf, void *d_out, const uint64_t *d_off, c
     g.src_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_buf) & 15u);
     g.dst_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_out) & 15u);
     g.delim = delim;
+    g.fsep = delim;
     const uint64_t ntiles = (sre_lg_nchunks(g) + SRE_LG_TILE_CHUNKS - 1) / SRE_LG_TILE_CHUNKS;
     if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sre_k_lines_gather, dim3((uint32_t) ntiles), dim3(SRE_LG_THREADS), 0, stream,
@@ -357,5 +485,67 @@ sre_launch_filter_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t 
     const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
     hipLaunchKernelGGL(sre_k_filter_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_ends, n, d_blk + nblk, d_info,
                        index_cap, d_index);
+    return hipGetLastError();
+}
+
+/* ---- the line extract ---- */
+
+extern "C" hipError_t
+sre_launch_extract_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int all,
+                          const sre_extract_groups_t *groups, const uint64_t *d_ends, const sre_lines_info_t *d_info,
+                          uint64_t *d_val, uint64_t *d_start, hipStream_t stream)
+{
+    if (nmax == 0) return hipSuccess;
+    const uint64_t nent = nmax * groups->k;
+    if (groups->k == 0 || groups->k > SRE_EXTRACT_MAX_FIELDS || nent > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_extract_select, dim3((uint32_t) ((nent + 255) / 256)), dim3(256), 0, stream, d_records, slots, i0, all,
+                       *groups, d_ends, d_info, d_val, d_start);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_extract_offsets(uint64_t *d_val, uint64_t n, uint32_t k, uint64_t *d_blk, uint64_t out_cap,
+                           sre_lines_info_t *d_info, hipStream_t stream)
+{
+    if (n == 0 || k == 0) return hipErrorInvalidValue;
+    const uint64_t nent = n * k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    uint64_t      *blkv = d_blk, *blkc = d_blk + nblk;
+    if (nblk > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_filter_sums, dim3((uint32_t) nblk), dim3(256), 0, stream, d_val, nent, blkv, blkc);
+    hipLaunchKernelGGL(sre_k_filter_scan, dim3(1), dim3(1024), 0, stream, blkv, blkc, nblk, d_info);
+    hipLaunchKernelGGL(sre_k_filter_offsets, dim3((uint32_t) nblk), dim3(256), 0, stream, d_val, nent, blkv);
+    hipLaunchKernelGGL(sre_k_extract_finish, dim3(1), dim3(1024), 0, stream, d_val, n, (uint64_t) k, blkc, out_cap, d_info);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_extract_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_start, uint64_t nentries,
+                          uint64_t out_bytes, uint32_t delim, uint32_t fsep, hipStream_t stream)
+{
+    if (out_bytes == 0) return hipSuccess;
+    sre_lg_geom_t g;
+    g.nlines = nentries;
+    g.out_bytes = out_bytes;
+    g.src_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_buf) & 15u);
+    g.dst_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_out) & 15u);
+    g.delim = delim;
+    g.fsep = fsep;
+    const uint64_t ntiles = (sre_lg_nchunks(g) + SRE_LG_TILE_CHUNKS - 1) / SRE_LG_TILE_CHUNKS;
+    if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_extract_gather, dim3((uint32_t) ntiles), dim3(SRE_LG_THREADS), 0, stream,
+                       static_cast<const uint8_t *>(d_buf) - g.src_head, static_cast<uint8_t *>(d_out) - g.dst_head, d_off,
+                       d_start, g);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_extract_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, uint64_t n, uint32_t k,
+                         const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
+                         hipStream_t stream)
+{
+    if (n == 0 || index_cap == 0) return hipSuccess;
+    const uint64_t nent = n * k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    hipLaunchKernelGGL(sre_k_extract_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_start, d_ends, nent,
+                       (uint64_t) k, d_blk + nblk, d_info, index_cap, d_index);
     return hipGetLastError();
 }

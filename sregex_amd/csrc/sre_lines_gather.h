@@ -13,6 +13,11 @@
  *   P = dst_head + output offset   (dst_head = d_out % 16),  output chunk c covers P in [16c, 16c + 16)
  *   S = src_head + source offset   (src_head = d_buf % 16),  source block q covers S in [16q, 16q + 16)
  * All offsets are 64-bit.
+ *
+ * Line extract (sre_hip_extract_lines) gathers with the same logic over a table of ENTRIES
+ * e = line * K + f, field f of the K chosen capture groups of a line: off[] is the prefix sum of (field length + 1)
+ * of the selected lines' entries, the text of an entry starts at its word of the call's starts array, and the
+ * byte behind it is the field separator, or the delimiter behind the last field of a line (sre_lg_tab_fields).
  */
 #ifndef SRE_LINES_GATHER_H
 #define SRE_LINES_GATHER_H
@@ -39,12 +44,13 @@ typedef struct {
     uint64_t lo, hi;            /* bytes 0..7 and 8..15 of a chunk, little endian */
 } sre_lg_u128;
 
-typedef struct {
+typedef struct sre_lg_geom_t {
     uint64_t nlines;
     uint64_t out_bytes;         /* bytes the call writes: whole lines only */
     uint32_t src_head;          /* d_buf % 16 */
     uint32_t dst_head;          /* d_out % 16 */
     uint32_t delim;
+    uint32_t fsep = 0;          /* line extract only: the byte behind a field that is not the last of its line */
 } sre_lg_geom_t;
 
 /* v moved down / up by k bytes (k >= 16 gives 0), and the mask of the first n bytes */
@@ -88,6 +94,7 @@ struct sre_lg_tab_global {
     const uint64_t *ends;
     SRE_LG_MEMBER uint64_t off(uint64_t i) const { return offs[i]; }
     SRE_LG_MEMBER uint64_t start(uint64_t i) const { return i ? ends[i - 1] + 1 : 0; }
+    template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t, uint32_t d) const { sink.delim(d); }
 };
 
 /* a window of it: lines base .. base + count - 1, offs[0 .. count] and starts[0 .. count - 1] */
@@ -97,6 +104,29 @@ struct sre_lg_tab_window {
     uint64_t        base;
     SRE_LG_MEMBER uint64_t off(uint64_t i) const { return offs[i - base]; }
     SRE_LG_MEMBER uint64_t start(uint64_t i) const { return starts[i - base]; }
+    template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t, uint32_t d) const { sink.delim(d); }
+};
+
+/* the entry table of the line extract, whole (base 0, global memory) or a window of it (entries base .. , LDS):
+ * offs as above, starts[e] = the source offset of the entry's text with flag bits on top.  The flags spare the
+ * gather a division by K per entry and tell the index an unset field from an empty one */
+#define SRE_LG_ENTRY_LAST   (1ull << 63)        /* the last field of its line: the delimiter follows, not fsep */
+#define SRE_LG_ENTRY_UNSET  (1ull << 62)        /* the group is unset (index rows only) */
+#define SRE_LG_ENTRY_FIRST  (1ull << 61)        /* the first field of its line (index rows only) */
+#define SRE_LG_ENTRY_START  (SRE_LG_ENTRY_FIRST - 1)
+
+struct sre_lg_tab_fields {
+    const uint64_t *offs;
+    const uint64_t *starts;
+    uint64_t        base;
+    SRE_LG_MEMBER uint64_t off(uint64_t e) const { return offs[e - base]; }
+    SRE_LG_MEMBER uint64_t raw(uint64_t e) const { return starts[e - base]; }
+    SRE_LG_MEMBER uint64_t start(uint64_t e) const { return starts[e - base] & SRE_LG_ENTRY_START; }
+    template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t e, uint32_t d) const
+    {
+        if (starts[e - base] & SRE_LG_ENTRY_LAST) sink.delim(d);
+        else sink.sep(d);
+    }
 };
 
 /* the last i of [lo, hi] with off(i) <= o; the caller knows off(lo) <= o */
@@ -108,6 +138,20 @@ sre_lg_find(const Tab &tab, uint64_t o, uint64_t lo, uint64_t hi)
         const uint64_t mid = lo + (hi - lo + 1) / 2;
         if (tab.off(mid) <= o) lo = mid;
         else hi = mid - 1;
+    }
+    return lo;
+}
+
+/* the cut of the line extract's output at out_cap: the first line i of n (n when all fit) whose row ends beyond
+ * it, off[(i + 1) k] > out_cap, so that off[i k] bytes are written and every row is whole */
+SRE_LG_FN uint64_t
+sre_lg_row_cut(const uint64_t *off, uint64_t n, uint64_t k, uint64_t out_cap)
+{
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (off[(mid + 1) * k] > out_cap) hi = mid;
+        else lo = mid + 1;
     }
     return lo;
 }
@@ -149,6 +193,7 @@ sre_lg_tile_slice(const Tab &tab, const sre_lg_geom_t &g, uint64_t tile, uint64_
  * The plan of output chunk c, searched in the lines [lo, hi] (a tile's slice): the pieces in output order,
  *   sink.text(S, d, cnt)   cnt source bytes from position S go to bytes d .. d + cnt - 1 of the chunk
  *   sink.delim(d)          byte d of the chunk is the delimiter
+ *   sink.sep(d)            ... the field separator (the entry table of the line extract only)
  * and the chunk's bytes [*first, *first + *count) are the ones the call owns (all 16 except in the first and
  * the last chunk of the output).  Every selected line takes at least its delimiter byte, so a chunk meets at
  * most 16 lines and the loop runs at most 16 times; stepping to the next selected line is one look at the
@@ -173,7 +218,7 @@ sre_lg_walk(const Tab &tab, const sre_lg_geom_t &g, uint64_t c, uint64_t lo, uin
             o = t_end;
         }
         if (o < o_hi) {
-            sink.delim((uint32_t) (o + g.dst_head - p0));
+            tab.end(sink, i, (uint32_t) (o + g.dst_head - p0));
             o++;
         }
         if (o >= o_hi) break;
@@ -195,10 +240,10 @@ sre_lg_walk(const Tab &tab, const sre_lg_geom_t &g, uint64_t c, uint64_t lo, uin
 template <class Mem>
 struct sre_lg_assembler {
     Mem        &mem;
-    uint32_t    delim_byte;
+    uint32_t    delim_byte, sep_byte;
     sre_lg_u128 acc;
 
-    SRE_LG_MEMBER sre_lg_assembler(Mem &m, uint32_t d) : mem(m), delim_byte(d) { acc.lo = 0; acc.hi = 0; }
+    SRE_LG_MEMBER sre_lg_assembler(Mem &m, uint32_t d, uint32_t s) : mem(m), delim_byte(d), sep_byte(s) { acc.lo = 0; acc.hi = 0; }
 
     SRE_LG_MEMBER void text(uint64_t s, uint32_t d, uint32_t cnt)
     {
@@ -222,15 +267,17 @@ struct sre_lg_assembler {
         acc.hi |= v.hi;
     }
 
-    SRE_LG_MEMBER void delim(uint32_t d)
+    SRE_LG_MEMBER void byte(uint32_t b, uint32_t d)
     {
         sre_lg_u128 v;
-        v.lo = delim_byte & 0xFFu;
+        v.lo = b & 0xFFu;
         v.hi = 0;
         v = sre_lg_shl(v, d);
         acc.lo |= v.lo;
         acc.hi |= v.hi;
     }
+    SRE_LG_MEMBER void delim(uint32_t d) { byte(delim_byte, d); }
+    SRE_LG_MEMBER void sep(uint32_t d) { byte(sep_byte, d); }
 };
 
 /* one output chunk: plan, assemble, store.  mem.store(c, v) writes the aligned chunk whole, mem.store_bytes(c,
@@ -239,7 +286,7 @@ template <class Tab, class Mem>
 SRE_LG_FN void
 sre_lg_chunk(const Tab &tab, const sre_lg_geom_t &g, uint64_t c, uint64_t lo, uint64_t hi, Mem &mem)
 {
-    sre_lg_assembler<Mem> as(mem, g.delim);
+    sre_lg_assembler<Mem> as(mem, g.delim, g.fsep);
     uint32_t              first, count;
     if (!sre_lg_walk(tab, g, c, lo, hi, as, &first, &count)) return;
     if (count == 16) mem.store(c, as.acc);

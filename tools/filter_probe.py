@@ -118,7 +118,7 @@ def profile(percents, calls, stats_out):
         ns = [int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in rows]
         assert len(ns) == len(percents) * (calls + 1), (len(ns), percents, calls)
         with open(stats[0], newline="") as f:
-            top = [{"name": r["Name"].split("(")[0].replace("void ", "").replace("anonymous namespace)::", ""), "calls": int(r["Calls"]),
+            top = [{"name": r["Name"].replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0], "calls": int(r["Calls"]),
                     "total_ns": int(r["TotalDurationNs"]), "percent": float(r["Percentage"])} for r in csv.DictReader(f)][:12]
         return {p: ns[i * (calls + 1) + 1:(i + 1) * (calls + 1)] for i, p in enumerate(percents)}, top
     finally:
