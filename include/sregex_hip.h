@@ -358,6 +358,83 @@ SRE_API int sre_hip_extract_lines(sre_hip_scanner_t *sc, const void *d_buf, size
     const int *groups, size_t ngroups, int fsep, int flags, void *d_out, size_t out_cap,
     sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream);
 
+/* ---- line substitute: the first match of each line rewritten by a template, into a device buffer ---- */
+
+enum { SRE_HIP_SUBST_MAX_PIECES = 30, SRE_HIP_SUBST_MAX_LITERAL = 4096 };
+
+/*
+ * The template of sre_hip_substitute_lines, parsed on the host (no device needed).  tmpl is
+ * tmpl_len bytes, NUL allowed, in the syntax of ngx.re.sub:
+ *   - `$` and the longest run of decimal digits behind it: that capture group (0: the match);
+ *   - `${digits}`: that group, so that `${1}0` is group 1 and then the literal `0`;
+ *   - `$$`: one `$`;
+ *   - every other byte is literal.  Adjacent literal bytes are ONE piece.
+ * Returns -1 for a `$` in front of anything else or at the end, `${` without digits or without
+ * `}`, a group above max_group, more than SRE_HIP_SUBST_MAX_PIECES pieces, or more than
+ * SRE_HIP_SUBST_MAX_LITERAL literal bytes in all.  The empty template is valid and has no piece
+ * (it deletes the match).  On success *npieces (may be NULL) is the number of pieces and
+ * piece_groups (NULL, or SRE_HIP_SUBST_MAX_PIECES ints) receives for each piece its group
+ * number, or -1 for a literal piece.  For a scanner, max_group is its max_ncaps,
+ * (result_slots - 2) / 2 - 1.
+ */
+SRE_API int sre_hip_subst_template_check(const void *tmpl, size_t tmpl_len, int max_group,
+    int *piece_groups, size_t *npieces);
+
+/*
+ * Line substitute: sed 's/RE/TEMPLATE/' from one device buffer to another (ngx.re.sub, cuDF
+ * replace_with_backrefs).  The split of d_buf, the matching of every line, the routing and the
+ * demand for an SRE_HIP_PIKE_FIRST scanner are exactly those of sre_hip_extract_lines on the
+ * same (sc, d_buf, len, delim); Thompson and COUNT scanners return -1 with a diagnostic.  Only
+ * the FIRST match of a line is rewritten (sed without `g`).
+ *
+ * Template.  tmpl is HOST memory, parsed as sre_hip_subst_template_check parses it with
+ * max_group = the scanner's max_ncaps; what fails there returns -1 here, and so does a literal
+ * byte equal to delim (a row would no longer be one line).
+ *
+ * Which lines are selected:
+ *   - flags == 0: the lines with a match (sed -n 's/../../p');
+ *   - SRE_HIP_LINES_ALL: every line, a line without a match copied unchanged (sed 's/../../'),
+ *     so row i of the output is line i of the input;
+ *   - SRE_HIP_LINES_INVERT, and any other bit, return -1.
+ *
+ * Output.  Each selected line gives one row, in line order.  With [m0, m1) = [ov[0], ov[1]) the
+ * first match of the line, the row is line[0, m0), each piece of the template in order,
+ * line[m1, len), one delim.  A literal piece is its bytes; a group piece is the bytes
+ * [ov[2g], ov[2g + 1]) of the line, and empty when the group is unset (anything but
+ * 0 <= ov[2g] <= ov[2g + 1] <= len).  With several regexes the groups are those of the regex that
+ * matched.  A selected line whose group 0 fails that rule is copied unchanged.  d_out is a DEVICE
+ * pointer at any alignment to out_cap bytes that do not overlap [d_buf, d_buf + len) (an overlap
+ * returns -1).  info->need_bytes is the sum over the selected lines of
+ * len - (m1 - m0) + replacement length + 1 whatever out_cap is; info->nselected counts lines.
+ *
+ * Truncation.  Only whole rows are written: info->nwritten is the largest k for which the first
+ * k rows take at most out_cap bytes, info->out_bytes that total.  No byte of d_out at or beyond
+ * out_bytes is touched and nothing is written in front of d_out.  d_out may be NULL when
+ * out_cap == 0 (a sizing call).
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten)
+ * rows it receives 8 sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the row in d_out
+ *   [4] offset of the match in d_buf   [5] its length
+ *   [6] offset of the replacement in d_out   [7] its length
+ * with [4] .. [7] all -1 for a line that was copied unchanged (no match, with SRE_HIP_LINES_ALL).
+ * d_index may be NULL when index_cap == 0.  info may be NULL.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  It replaces the scanner's last
+ * call and the diagnostics describe it exactly as for sre_hip_extract_lines; the routes, and what
+ * the host reads and uploads on each, are the extract's too.  len == 0 gives all zeros in info
+ * and success.  Beyond what line mode takes, a scanner keeps 16 bytes per line and entry
+ * (pieces + 2 entries a line) of the largest call (plus 16 bytes per 1024 of them) of device
+ * memory, grow-only, shared with sre_hip_filter_lines and sre_hip_extract_lines, and 4 KiB for
+ * the literal bytes of the last template, which a repeated call does not upload again; all freed
+ * with the scanner.  A batch holds at most 2^24 lines x 32 entries.  Returns 0 on success, -1 on
+ * bad arguments or failure.
+ */
+SRE_API int sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const void *tmpl, size_t tmpl_len, int flags, void *d_out, size_t out_cap,
+    sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

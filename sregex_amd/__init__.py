@@ -28,6 +28,8 @@ ENGINE_AUTO, ENGINE_VM, ENGINE_SCAN, ENGINE_NFA = 0, 1, 2, 3
 HIP_LINES_ALL = 1
 HIP_LINES_INVERT = 2
 HIP_EXTRACT_MAX_FIELDS = 32
+HIP_SUBST_MAX_PIECES = 30
+HIP_SUBST_MAX_LITERAL = 4096
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -83,6 +85,10 @@ API = {
     "sre_hip_filter_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_extract_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int,
                                              ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_subst_template_check": (ctypes.c_int, [ctypes.c_char_p, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                    ctypes.POINTER(_sz)]),
+    "sre_hip_substitute_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_char_p, _sz, ctypes.c_int, _vp, _sz, _vp, _sz,
+                                                _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -143,6 +149,18 @@ def load_library(path=None):
     if path is None:
         _lib = lib
     return lib
+
+
+def template_pieces(template, max_group):
+    """sre_hip_subst_template_check: the pieces of a substitute template (Scanner.substitute_lines) as a list, the
+    capture group number of each piece or -1 for a literal piece; max_group is the largest group the template may
+    name (a scanner's (slots - 2) // 2 - 1).  Raises ValueError for an invalid template.  Needs no device."""
+    template = bytes(template)
+    groups = (ctypes.c_int * HIP_SUBST_MAX_PIECES)()
+    n = _sz()
+    if load_library().sre_hip_subst_template_check(template, len(template), max_group, groups, ctypes.byref(n)) != 0:
+        raise ValueError("invalid substitute template %r for max_group %d" % (template, max_group))
+    return list(groups[:n.value])
 
 
 def _capture_stdout(fn):
@@ -436,6 +454,23 @@ class Scanner:
         if self.lib.sre_hip_extract_lines(self.h, ptr, length, delim, arr, len(groups), fsep, HIP_LINES_ALL if all_lines else 0,
                                           out_ptr, out_cap, index_ptr, index_cap, info, hip_stream) != 0:
             raise RuntimeError("sre_hip_extract_lines failed")
+        return FilterInfo(*info)
+
+    def substitute_lines(self, ptr, length, template, out_ptr, out_cap, delim=0x0A, all_lines=False, index_ptr=None,
+                         index_cap=0, hip_stream=None):
+        """sre_hip_substitute_lines: for every matching line of the device buffer (ptr, length) one row in the device
+        buffer (out_ptr, out_cap): the line with its FIRST match replaced by `template` (host bytes: $1 / ${1} a
+        capture group, $$ a dollar, anything else literal), ended by delim; with all_lines every line, a line
+        without a match copied unchanged.  index_ptr: an optional device array of index_cap rows [line no, offset in
+        the buffer, length, offset of the row in the output, offset in the buffer and length of the match, offset in
+        the output and length of the replacement] (the last four -1 for an unmatched line).  The scanner's mode must
+        be HIP_PIKE_FIRST.  Returns FilterInfo(nlines, nselected, need_bytes, nwritten, out_bytes), counts of lines."""
+        template = bytes(template)
+        info = (_sz * 5)()
+        if self.lib.sre_hip_substitute_lines(self.h, ptr, length, delim, template, len(template),
+                                             HIP_LINES_ALL if all_lines else 0, out_ptr, out_cap, index_ptr, index_cap, info,
+                                             hip_stream) != 0:
+            raise RuntimeError("sre_hip_substitute_lines failed")
         return FilterInfo(*info)
 
     @property

@@ -140,6 +140,11 @@ struct sre_hip_scanner_s {
     /* the line extract (sre_hip_extract_lines) shares both, sized by its entries (lines x fields), and adds */
     uint64_t                 *d_fstart;         /* per-entry source offsets under their flags: lines x fields words */
     size_t                    fstart_cap;
+    /* the line substitute (sre_hip_substitute_lines) shares the three, sized by its entries (lines x (pieces + 2)), and adds */
+    uint8_t                  *d_lit;            /* the literal block: SRE_SUBST_MAX_LITERAL bytes, zero behind the literals */
+    uint8_t                  *h_lit;            /* the literals the block holds, so that a repeated template uploads nothing */
+    size_t                    lit_len;
+    bool                      lit_valid;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -200,6 +205,8 @@ scanner_release(void *data)
     if (sc->d_fval) (void) hipFree(sc->d_fval);
     if (sc->d_fblk) (void) hipFree(sc->d_fblk);
     if (sc->d_fstart) (void) hipFree(sc->d_fstart);
+    if (sc->d_lit) (void) hipFree(sc->d_lit);
+    free(sc->h_lit);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -1579,7 +1586,17 @@ struct LinesSink {
      * line * k + field, d_val has one word per entry and d_start the entries' source offsets; mode is 0 or 2 */
     const sre_extract_groups_t *groups;
     uint64_t                   *d_start;
+    /* the line substitute (sre_hip_substitute_lines): with pieces, the select pass is the substitute's over the entries
+     * line * (np + 2) + piece, into d_val and d_start as above; mode is 0 or 2 */
+    const sre_subst_pieces_t   *pieces;
 };
+
+/* entries per line of the sink's table */
+static uint64_t
+sink_entries(const LinesSink *sink)
+{
+    return sink->pieces ? sink->pieces->np + 2 : sink->groups ? sink->groups->k : 1;
+}
 
 static bool
 sink_selects(const LinesSink *sink, sre_int_t rc)
@@ -1591,6 +1608,10 @@ sink_selects(const LinesSink *sink, sre_int_t rc)
 static hipError_t
 sink_select(sre_hip_scanner_t *sc, const LinesSink *sink, size_t slots, uint64_t nmax, uint64_t i0, hipStream_t stream)
 {
+    if (sink->pieces) {
+        return sre_launch_subst_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->pieces, sc->d_ends,
+                                       sc->d_linfo, sink->d_val, sink->d_start, stream);
+    }
     if (sink->groups) {
         return sre_launch_extract_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->groups, sc->d_ends,
                                          sc->d_linfo, sink->d_val, sink->d_start, stream);
@@ -1884,7 +1905,41 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
         *lineage += sc->lineage_passes;
         const double ms = sre_hip_scanner_last_kernel_ms(sc);
         *kms = (ms < 0 || *kms < 0) ? -1.0 : *kms + ms;
-        if (sink && sink->groups) {
+        if (sink && sink->pieces) {
+            /* what sre_k_subst_select writes, from the records the host holds */
+            const sre_subst_pieces_t *pc = sink->pieces;
+            const uint32_t            P = pc->np + 2;
+            vals.resize(nb * P);
+            starts.resize(nb * P);
+            for (uint64_t j = 0; j < nb; j++) {
+                const sre_int_t *rec = recs.data() + j * slots;
+                const bool       hit = rec[0] != SRE_DECLINED, sel = hit || sink->mode == 2;
+                const uint64_t   st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf), len = lens[j];
+                const sre_int_t  m0 = hit ? rec[2] : -1, m1 = hit ? rec[3] : -1;
+                const bool       ok = m0 >= 0 && m1 >= m0 && (uint64_t) m1 <= len;
+                uint64_t        *v = vals.data() + j * P, *w = starts.data() + j * P;
+                v[0] = ok ? (uint64_t) m0 : len;
+                w[0] = st | SRE_LG_ENTRY_FIRST | (ok ? 0 : SRE_LG_ENTRY_UNSET);
+                for (uint32_t q = 0; q < pc->np; q++) {
+                    if (pc->g[q] < 0) {
+                        v[1 + q] = ok ? pc->len[q] : 0;
+                        w[1 + q] = (uint64_t) pc->off[q] | SRE_LG_ENTRY_LITERAL;
+                    } else {
+                        const sre_int_t a = ok ? rec[2 + 2 * pc->g[q]] : -1, b = ok ? rec[3 + 2 * pc->g[q]] : -1;
+                        const bool      set = a >= 0 && b >= a && (uint64_t) b <= len;
+                        v[1 + q] = set ? (uint64_t) (b - a) : 0;
+                        w[1 + q] = set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET;
+                    }
+                }
+                v[P - 1] = (ok ? len - (uint64_t) m1 : 0) + 1;
+                w[P - 1] = (ok ? st + (uint64_t) m1 : st + len) | SRE_LG_ENTRY_LAST;
+                for (uint32_t f = 0; !sel && f < P; f++) v[f] = 0;
+            }
+            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0 * P, vals.data(), nb * P * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            SRE_HIP_TRY(hipMemcpyAsync(sink->d_start + i0 * P, starts.data(), nb * P * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                       stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        } else if (sink && sink->groups) {
             /* what sre_k_extract_select writes, from the records the host holds */
             const uint32_t k = sink->groups->k;
             vals.resize(nb * k);
@@ -1954,10 +2009,10 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
     if (sc->h_linfo == NULL) SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_linfo), sizeof(sre_lines_info_t), 0));
     if (lines_split(sc, d_buf, len, delim, stream, &n) == 0) {
         if (sink) {
-            const uint64_t k = sink->groups ? sink->groups->k : 1;
+            const uint64_t k = sink_entries(sink);
             if (lines_grow(&sc->d_fval, &sc->fval_cap, (n * k + 1) * sizeof(uint64_t)) != 0) goto hip_failed;
             sink->d_val = sc->d_fval;
-            if (sink->groups) {
+            if (sink->groups || sink->pieces) {
                 if (lines_grow(&sc->d_fstart, &sc->fstart_cap, n * k * sizeof(uint64_t)) != 0) goto hip_failed;
                 sink->d_start = sc->d_fstart;
             }
@@ -2107,6 +2162,157 @@ sre_hip_extract_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int 
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
     if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The template of the line substitute: the pieces in order, the literal bytes of all literal pieces back to back in
+ * lit (SRE_SUBST_MAX_LITERAL bytes).  $digits and ${digits} are groups, $$ is one '$', every other byte is literal and
+ * adjacent literals are one piece.  -1: a '$' in front of anything else, a group above max_group, too many pieces or
+ * literal bytes */
+static int
+subst_parse(const uint8_t *t, size_t n, int max_group, sre_subst_pieces_t *pc, uint8_t *lit, size_t *lit_len)
+{
+    size_t nlit = 0;
+    bool   in_literal = false;
+    memset(pc, 0, sizeof(*pc));
+    for (size_t i = 0; i < n;) {
+        int group = -1;
+        if (t[i] == '$' && !(i + 1 < n && t[i + 1] == '$')) {
+            size_t     j = i + 1;
+            const bool brace = j < n && t[j] == '{';
+            if (brace) j++;
+            const size_t d0 = j;
+            long         v = 0;
+            while (j < n && t[j] >= '0' && t[j] <= '9') {
+                v = v * 10 + (t[j] - '0');
+                if (v > 0xFFFF) return -1;
+                j++;
+            }
+            if (j == d0) return -1;
+            if (brace) {
+                if (j >= n || t[j] != '}') return -1;
+                j++;
+            }
+            if (v > max_group) return -1;
+            group = (int) v;
+            i = j;
+        }
+        if (group >= 0) {
+            if (pc->np >= SRE_SUBST_MAX_PIECES) return -1;
+            pc->g[pc->np++] = (int16_t) group;
+            in_literal = false;
+            continue;
+        }
+        const uint8_t c = t[i];
+        i += c == '$' ? 2 : 1;
+        if (nlit >= SRE_SUBST_MAX_LITERAL) return -1;
+        if (!in_literal) {
+            if (pc->np >= SRE_SUBST_MAX_PIECES) return -1;
+            pc->g[pc->np] = -1;
+            pc->off[pc->np] = (uint16_t) nlit;
+            pc->len[pc->np] = 0;
+            pc->np++;
+            in_literal = true;
+        }
+        if (lit) lit[nlit] = c;
+        nlit++;
+        pc->len[pc->np - 1]++;
+    }
+    *lit_len = nlit;
+    return 0;
+}
+
+extern "C" SRE_API int
+sre_hip_subst_template_check(const void *tmpl, size_t tmpl_len, int max_group, int *piece_groups, size_t *npieces)
+{
+    sre_subst_pieces_t pc;
+    size_t             nlit = 0;
+    if (tmpl_len != 0 && tmpl == NULL) return -1;
+    if (subst_parse(static_cast<const uint8_t *>(tmpl), tmpl_len, max_group, &pc, NULL, &nlit) != 0) return -1;
+    for (uint32_t q = 0; piece_groups && q < pc.np; q++) piece_groups[q] = pc.g[q];
+    if (npieces) *npieces = pc.np;
+    return 0;
+}
+
+/* The line substitute: the template parsed and its literals put into the scanner's literal block,
+ * the line-mode call with the substitute's sink, then the extract's passes over the entries (lines x (pieces + 2)) with
+ * the lines counted by their last entries: scan, cut at a line boundary, one read of four words, gather, index rows. */
+extern "C" SRE_API int
+sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const void *tmpl, size_t tmpl_len,
+    int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || (tmpl_len != 0 && tmpl == NULL)
+        || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    if (sc->mode != SRE_HIP_PIKE_FIRST) {
+        fprintf(stderr, "[sregex-hip] line substitute: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
+        return -1;
+    }
+    sre_subst_pieces_t pc;
+    uint8_t            lit[SRE_SUBST_MAX_LITERAL];
+    size_t             nlit = 0;
+    /* ovec_slots = 2 * (max_ncaps + 1) */
+    if (subst_parse(static_cast<const uint8_t *>(tmpl), tmpl_len, (int) sc->ovec_slots / 2 - 1, &pc, lit, &nlit) != 0) return -1;
+    /* a literal delimiter would make two rows of one line */
+    if (nlit != 0 && memchr(lit, delim, nlit) != NULL) return -1;
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    /* the literal block: allocated once, uploaded when the literals differ from the ones it holds */
+    if (sc->d_lit == NULL) {
+        sc->lit_valid = false;
+        if (sc->h_lit == NULL) sc->h_lit = static_cast<uint8_t *>(calloc(1, SRE_SUBST_MAX_LITERAL));
+        if (sc->h_lit == NULL) return -1;
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_lit), SRE_SUBST_MAX_LITERAL));
+    }
+    if (!sc->lit_valid || sc->lit_len != nlit || memcmp(sc->h_lit, lit, nlit) != 0) {
+        const size_t padded = (nlit + 15) / 16 * 16;
+        sc->lit_valid = false;
+        memset(sc->h_lit, 0, SRE_SUBST_MAX_LITERAL);
+        memcpy(sc->h_lit, lit, nlit);
+        sc->lit_len = nlit;
+        if (padded) SRE_HIP_TRY(hipMemcpyAsync(sc->d_lit, sc->h_lit, padded, hipMemcpyHostToDevice, stream));
+        sc->lit_valid = true;
+    }
+    {
+        const uint32_t P = pc.np + 2;
+        LinesSink      sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, NULL, NULL, &pc};
+        uint64_t       n = 0, nrep = 0;
+        if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) {
+            sc->lit_valid = false;      /* (the upload may not have run) */
+            return -1;
+        }
+        sre_hip_filter_info_t res;
+        memset(&res, 0, sizeof(res));
+        if (n != 0) {
+            const uint64_t nent = n * P, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+            if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+            SRE_HIP_TRY(sre_launch_subst_offsets(sc->d_fval, n, P, sc->d_fblk, out_cap, sc->d_linfo, stream));
+            SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            res.nlines = (size_t) n;
+            res.nselected = (size_t) sc->h_linfo->fsel;
+            res.need_bytes = (size_t) sc->h_linfo->fneed;
+            res.nwritten = (size_t) sc->h_linfo->fwritten;
+            res.out_bytes = (size_t) sc->h_linfo->fbytes;
+            if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
+            SRE_HIP_TRY(sre_launch_subst_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, sc->d_lit, nent, res.out_bytes,
+                                                (uint32_t) delim, stream));
+            if (res.nwritten != 0) {
+                SRE_HIP_TRY(sre_launch_subst_index(sc->d_fval, sc->d_fstart, sc->d_ends, n, P, sc->d_fblk, sc->d_linfo, index_cap,
+                                                   d_index, stream));
+            }
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
+        if (info) *info = res;
+    }
     return 0;
 hip_failed:
     return -1;

@@ -132,6 +132,37 @@ hipError_t sre_launch_extract_gather(const void *d_buf, void *d_out, const uint6
 hipError_t sre_launch_extract_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, uint64_t n,
     uint32_t k, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
+/* ---- the line substitute (sre_hip_lines_gather.hip) ---- */
+#define SRE_SUBST_MAX_PIECES  30u
+#define SRE_SUBST_MAX_LITERAL 4096u
+/* the parsed template: piece q is capture group g[q] of the line's record, or with g[q] < 0 the len[q] bytes at off[q]
+ * of the call's literal block */
+typedef struct {
+    uint32_t np;
+    int16_t  g[SRE_SUBST_MAX_PIECES];
+    uint16_t off[SRE_SUBST_MAX_PIECES];
+    uint16_t len[SRE_SUBST_MAX_PIECES];
+} sre_subst_pieces_t;
+/* select pass of the batch over its entries e = line * p + f, p = np + 2: d_val[e] = the bytes of the entry (the line's
+ * text in front of the match, a piece, the text behind the match + 1 for the delimiter) for a selected line (rc !=
+ * SRE_DECLINED, or every line with `all`: a line without a match is its own row), else 0; d_start[e] = where the
+ * entry's text starts, under the flag bits of sre_lines_gather.h.  A batch may have at most 2^32 - 1 entries */
+hipError_t sre_launch_subst_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int all,
+    const sre_subst_pieces_t *pieces, const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val,
+    uint64_t *d_start, hipStream_t stream);
+/* sre_launch_extract_offsets over the n * p entries, lines counted by their last entries (the others may be empty);
+ * info->fsel and fwritten count lines */
+hipError_t sre_launch_subst_offsets(uint64_t *d_val, uint64_t n, uint32_t p, uint64_t *d_blk, uint64_t out_cap,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* the gather over the piece table: output bytes [0, out_bytes) of the rows to d_out.  d_lit: the literal block, 16-byte
+ * aligned and a multiple of 16 bytes */
+hipError_t sre_launch_subst_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_start,
+    const void *d_lit, uint64_t nentries, uint64_t out_bytes, uint32_t delim, hipStream_t stream);
+/* rows [line, start, len, output offset of the row, match offset, match length, output offset of the replacement, its
+ * length] of the first min(index_cap, info->fwritten) written rows; a line without a match has -1 in the last four */
+hipError_t sre_launch_subst_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, uint64_t n,
+    uint32_t p, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
+    hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

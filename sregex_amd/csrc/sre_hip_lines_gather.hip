@@ -14,6 +14,11 @@
  * source offset, from the batch's records), the same scan kernels over n * K entries with the cut made at a line
  * boundary, the gather over the entry table (sre_lg_tab_fields) and index rows of 4 + 2 K words.
  *
+ * The line substitute (sre_hip_substitute_lines) runs them over a table of pieces e = line * P + f:
+ * the text in front of the first match, the template's pieces, the text behind the match and the delimiter.  Entries of
+ * a selected line may be empty there, so its sums, finish and index count LINES by their last entries, which always
+ * take a byte; the gather is the same chunk walk over sre_lg_tab_pieces with the literal block as a second source.
+ *
  * No workgroup waits for another.  Plain C++ and vector memory operations only.
  */
 #include <sregex/sregex.h>
@@ -96,6 +101,49 @@ sre_k_extract_select(const int64_t *__restrict__ records, uint32_t slots, uint64
     val[e] = (hit || all) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
     start[e] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
                | (f + 1 == gr.k ? SRE_LG_ENTRY_LAST : 0);
+}
+
+/* the line substitute's: LANE PER ENTRY of the batch, entry x = j * P + f of line i0 + j, P = pieces + 2.  f = 0 is the
+ * line's text in front of the match [m0, m1) = group 0, f = 1 .. P - 2 the template's pieces (a literal: its length and
+ * its offset in the literal block; a group: as the extract's field, without the byte behind it), f = P - 1 the text
+ * behind the match and the delimiter.  A selected line without a match, or whose group 0 does not lie inside the line,
+ * is copied whole: its text is the first entry, its pieces are empty.  Every entry of an unselected line is 0 */
+__global__ __launch_bounds__(256) void
+sre_k_subst_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t i0, int all, sre_subst_pieces_t pc,
+                   const uint64_t *__restrict__ ends, const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ val,
+                   uint64_t *__restrict__ start)
+{
+    const uint64_t nb = info->i1 - i0;
+    const uint32_t P = pc.np + 2;
+    const uint64_t x = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (x >= nb * P) return;
+    const uint32_t j = (uint32_t) x / P, f = (uint32_t) x - j * P;             /* (a batch has fewer than 2^32 entries) */
+    const int64_t *rec = records + (uint64_t) j * slots;
+    const bool     hit = rec[0] != SRE_DECLINED;
+    const uint64_t i = i0 + j, st = line_start(ends, i), len = ends[i] - st;
+    const int64_t  m0 = hit ? rec[2] : -1, m1 = hit ? rec[3] : -1;
+    /* (nothing but a match that lies inside its line is ever turned into offsets) */
+    const bool     ok = m0 >= 0 && m1 >= m0 && (uint64_t) m1 <= len;
+    uint64_t       v, w;
+    if (f == 0) {
+        v = ok ? (uint64_t) m0 : len;
+        w = st | SRE_LG_ENTRY_FIRST | (ok ? 0 : SRE_LG_ENTRY_UNSET);
+    } else if (f + 1 == P) {
+        v = (ok ? len - (uint64_t) m1 : 0) + 1;
+        w = (ok ? st + (uint64_t) m1 : st + len) | SRE_LG_ENTRY_LAST;
+    } else if (pc.g[f - 1] < 0) {
+        v = ok ? pc.len[f - 1] : 0;
+        w = (uint64_t) pc.off[f - 1] | SRE_LG_ENTRY_LITERAL;
+    } else {
+        const uint32_t g = (uint32_t) pc.g[f - 1];
+        const int64_t  a = ok ? rec[2 + 2 * g] : -1, b = ok ? rec[3 + 2 * g] : -1;
+        const bool     set = a >= 0 && b >= a && (uint64_t) b <= len;
+        v = set ? (uint64_t) (b - a) : 0;
+        w = set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET;
+    }
+    const uint64_t e = (i0 * P) + x;
+    val[e] = (hit || all) ? v : 0;
+    start[e] = w;
 }
 
 /* ---- scan ---- */
@@ -220,6 +268,49 @@ sre_k_extract_finish(const uint64_t *__restrict__ off, uint64_t n, uint64_t k, c
     }
 }
 
+/* the line substitute's sums over n entries of lines of p pieces: the workgroup's bytes as sre_k_filter_sums has them,
+ * and its selected LINES.  Entries of a selected line may be empty here, but its last one (e % p == p - 1) always
+ * takes the delimiter: the lines are the last entries with a value */
+__global__ __launch_bounds__(256) void
+sre_k_subst_sums(const uint64_t *__restrict__ val, uint64_t n, uint64_t p, uint64_t *__restrict__ blkv, uint64_t *__restrict__ blkc)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint64_t            s = 0, k = 0, r = q0 % p;
+    for (uint32_t q = 0; q < 4; q++) {
+        if (q0 + q < n) {
+            const uint64_t v = val[q0 + q];
+            s += v;
+            k += (v && r == p - 1) ? 1 : 0;
+        }
+        r = r + 1 == p ? 0 : r + 1;
+    }
+    uint64_t ts, tk;
+    (void) block_excl_scan<256>(s, wsum, ts);
+    (void) block_excl_scan<256>(k, wsum, tk);
+    if (threadIdx.x == 0) {
+        blkv[blockIdx.x] = ts;
+        blkc[blockIdx.x] = tk;
+    }
+}
+
+/* the cut at a line boundary as sre_k_extract_finish makes it; info->fsel counts lines already, and the written lines
+ * in front of the boundary entry i p are the selected last entries in front of it */
+__global__ __launch_bounds__(1024) void
+sre_k_subst_finish(const uint64_t *__restrict__ off, uint64_t n, uint64_t p, const uint64_t *__restrict__ blkc,
+                   uint64_t out_cap, sre_lines_info_t *__restrict__ info)
+{
+    __shared__ uint64_t cut;
+    if (threadIdx.x == 0) cut = sre_lg_row_cut(off, n, p, out_cap);
+    __syncthreads();
+    const uint64_t i = cut, e = i * p, b = e / SRE_LINES_ITEMS, j = b * SRE_LINES_ITEMS + threadIdx.x;
+    const int      before = __syncthreads_count(j < e && j % p == p - 1 && off[j + 1] > off[j]);
+    if (threadIdx.x == 0) {
+        info->fbytes = off[e];
+        info->fwritten = i == n ? info->fsel : blkc[b] + (uint64_t) before;
+    }
+}
+
 /* ---- gather ---- */
 
 typedef const __attribute__((address_space(1))) sre_u32x4_unaligned *lg_unaligned_ptr;
@@ -258,6 +349,28 @@ struct GatherMem {
     }
 };
 
+/* ... and of the literal block of the line substitute: a 16-byte aligned address, a multiple of 16 bytes */
+struct SubstMem : GatherMem {
+    const uint8_t *lit;
+
+    __device__ inline sre_lg_u128 lit_load(uint64_t q) const
+    {
+        const uint4 v = reinterpret_cast<const uint4 *>(lit)[q];
+        sre_lg_u128 r;
+        r.lo = ((uint64_t) v.y << 32) | v.x;
+        r.hi = ((uint64_t) v.w << 32) | v.z;
+        return r;
+    }
+    __device__ inline sre_lg_u128 lit_loadu(uint64_t s) const
+    {
+        const sre_u32x4 v = *reinterpret_cast<lg_unaligned_ptr>(reinterpret_cast<uintptr_t>(lit) + s);
+        sre_lg_u128     r;
+        r.lo = ((uint64_t) v.y << 32) | v.x;
+        r.hi = ((uint64_t) v.w << 32) | v.z;
+        return r;
+    }
+};
+
 /* sre_lg_find over the global table by a whole wave: 64 probes a step, so a table of a million lines takes four
  * dependent loads instead of twenty.  Every lane of the wave calls it and gets the same answer */
 __device__ inline uint64_t
@@ -278,9 +391,9 @@ wave_find(const uint64_t *__restrict__ off, uint64_t o, uint64_t lo, uint64_t hi
     return lo + (uint32_t) __popcll(__ballot(p <= hi && off[p] <= o));
 }
 
-template <class Tab>
+template <class Tab, class Mem>
 __device__ inline void
-gather_tile(const Tab &tab, const sre_lg_geom_t &g, uint64_t la, uint64_t lb, const GatherMem &mem)
+gather_tile(const Tab &tab, const sre_lg_geom_t &g, uint64_t la, uint64_t lb, const Mem &mem)
 {
     const uint64_t nchunks = sre_lg_nchunks(g);
     const uint64_t c0 = (uint64_t) blockIdx.x * SRE_LG_TILE_CHUNKS + threadIdx.x;
@@ -304,10 +417,16 @@ window_start(const sre_lg_tab_fields &tab, uint64_t i)
     return tab.raw(i);
 }
 
+__device__ inline uint64_t
+window_start(const sre_lg_tab_pieces &tab, uint64_t i)
+{
+    return tab.raw(i);
+}
+
 /* one tile of the output over the table `tab` (global memory), WTab its window type */
-template <class GTab, class WTab>
+template <class GTab, class WTab, class Mem>
 __device__ inline void
-gather_body(const GTab &tab, const uint64_t *__restrict__ off, const sre_lg_geom_t &g, const GatherMem &mem, uint64_t *w_off,
+gather_body(const GTab &tab, const uint64_t *__restrict__ off, const sre_lg_geom_t &g, const Mem &mem, uint64_t *w_off,
             uint64_t *w_start, uint64_t *slice)
 {
     /* the tile's slice of the table, found once: wave 0 searches the line of the tile's first byte, wave 1 that
@@ -355,6 +474,20 @@ sre_k_extract_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     const sre_lg_tab_fields tab = {off, starts, 0};
     const GatherMem         mem = {src, dst};
     gather_body<sre_lg_tab_fields, sre_lg_tab_fields>(tab, off, g, mem, w_off, w_start, slice);
+}
+
+/* the line substitute's: g.nlines counts the entries of the piece table, lit is the literal block */
+__global__ __launch_bounds__(SRE_LG_THREADS) void
+sre_k_subst_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const uint64_t *__restrict__ off,
+                   const uint64_t *__restrict__ starts, const uint8_t *__restrict__ lit, sre_lg_geom_t g)
+{
+    __shared__ uint64_t w_off[SRE_LG_WINDOW + 1], w_start[SRE_LG_WINDOW], slice[2];
+    const sre_lg_tab_pieces tab = {off, starts, 0};
+    SubstMem                mem;
+    mem.src = src;
+    mem.dst = dst;
+    mem.lit = lit;
+    gather_body<sre_lg_tab_pieces, sre_lg_tab_pieces>(tab, off, g, mem, w_off, w_start, slice);
 }
 
 /* ---- index ---- */
@@ -426,6 +559,47 @@ sre_k_extract_index(const uint64_t *__restrict__ off, const uint64_t *__restrict
                 row[4 + 2 * x] = unset ? -1 : (int64_t) (w & SRE_LG_ENTRY_START);
                 row[5 + 2 * x] = unset ? -1 : (int64_t) (off[e + x + 1] - off[e + x] - 1);
             }
+        }
+        r++;
+    }
+}
+
+/* the line substitute's rows of 8 words: workgroups over the ENTRIES as in the scan; the lane that holds the LAST entry
+ * of a selected line writes the line's row, its rank the selected last entries in front of it (what the sums counted).
+ * Everything in the row comes from the table: the match starts where the first entry's text ends and ends where the
+ * last entry's text starts, the replacement is the output between them */
+__global__ __launch_bounds__(256) void
+sre_k_subst_index(const uint64_t *__restrict__ off, const uint64_t *__restrict__ starts, const uint64_t *__restrict__ ends,
+                  uint64_t nent, uint64_t p, const uint64_t *__restrict__ blkc, const sre_lines_info_t *__restrict__ info,
+                  uint64_t index_cap, int64_t *__restrict__ rows)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      limit = index_cap < info->fwritten ? index_cap : info->fwritten;
+    if (blkc[blockIdx.x] >= limit) return;      /* (the whole workgroup) */
+    const uint64_t q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint32_t       f[4];
+    uint64_t       s = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        f[q] = q0 + q < nent && (starts[q0 + q] & SRE_LG_ENTRY_LAST) && off[q0 + q + 1] > off[q0 + q];
+        s += f[q];
+    }
+    uint64_t total;
+    uint64_t r = blkc[blockIdx.x] + block_excl_scan<256>(s, wsum, total);
+    for (uint32_t q = 0; q < 4; q++) {
+        if (!f[q]) continue;
+        if (r < limit) {
+            const uint64_t z = q0 + q, e = z - (p - 1), i = e / p, st = line_start(ends, i);
+            const bool     matched = (starts[e] & SRE_LG_ENTRY_UNSET) == 0;
+            const uint64_t m0 = st + (off[e + 1] - off[e]), m1 = starts[z] & SRE_LG_PIECE_START;
+            int64_t       *row = rows + r * 8;
+            row[0] = (int64_t) i;
+            row[1] = (int64_t) st;
+            row[2] = (int64_t) (ends[i] - st);
+            row[3] = (int64_t) off[e];
+            row[4] = matched ? (int64_t) m0 : -1;
+            row[5] = matched ? (int64_t) (m1 - m0) : -1;
+            row[6] = matched ? (int64_t) off[e + 1] : -1;
+            row[7] = matched ? (int64_t) (off[z] - off[e + 1]) : -1;
         }
         r++;
     }
@@ -547,5 +721,68 @@ sre_launch_extract_index(const uint64_t *d_off, const uint64_t *d_start, const u
     const uint64_t nent = n * k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
     hipLaunchKernelGGL(sre_k_extract_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_start, d_ends, nent,
                        (uint64_t) k, d_blk + nblk, d_info, index_cap, d_index);
+    return hipGetLastError();
+}
+
+/* ---- the line substitute ---- */
+
+extern "C" hipError_t
+sre_launch_subst_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int all,
+                        const sre_subst_pieces_t *pieces, const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val,
+                        uint64_t *d_start, hipStream_t stream)
+{
+    if (nmax == 0) return hipSuccess;
+    const uint64_t nent = nmax * (pieces->np + 2);
+    if (pieces->np > SRE_SUBST_MAX_PIECES || nent > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_subst_select, dim3((uint32_t) ((nent + 255) / 256)), dim3(256), 0, stream, d_records, slots, i0, all,
+                       *pieces, d_ends, d_info, d_val, d_start);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_subst_offsets(uint64_t *d_val, uint64_t n, uint32_t p, uint64_t *d_blk, uint64_t out_cap, sre_lines_info_t *d_info,
+                         hipStream_t stream)
+{
+    if (n == 0 || p < 2) return hipErrorInvalidValue;
+    const uint64_t nent = n * p, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    uint64_t      *blkv = d_blk, *blkc = d_blk + nblk;
+    if (nblk > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_subst_sums, dim3((uint32_t) nblk), dim3(256), 0, stream, d_val, nent, (uint64_t) p, blkv, blkc);
+    hipLaunchKernelGGL(sre_k_filter_scan, dim3(1), dim3(1024), 0, stream, blkv, blkc, nblk, d_info);
+    hipLaunchKernelGGL(sre_k_filter_offsets, dim3((uint32_t) nblk), dim3(256), 0, stream, d_val, nent, blkv);
+    hipLaunchKernelGGL(sre_k_subst_finish, dim3(1), dim3(1024), 0, stream, d_val, n, (uint64_t) p, blkc, out_cap, d_info);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_subst_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_start, const void *d_lit,
+                        uint64_t nentries, uint64_t out_bytes, uint32_t delim, hipStream_t stream)
+{
+    if (out_bytes == 0) return hipSuccess;
+    if (d_lit == NULL || (reinterpret_cast<uintptr_t>(d_lit) & 15u) != 0) return hipErrorInvalidValue;
+    sre_lg_geom_t g;
+    g.nlines = nentries;
+    g.out_bytes = out_bytes;
+    g.src_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_buf) & 15u);
+    g.dst_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_out) & 15u);
+    g.delim = delim;
+    g.fsep = delim;
+    const uint64_t ntiles = (sre_lg_nchunks(g) + SRE_LG_TILE_CHUNKS - 1) / SRE_LG_TILE_CHUNKS;
+    if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_subst_gather, dim3((uint32_t) ntiles), dim3(SRE_LG_THREADS), 0, stream,
+                       static_cast<const uint8_t *>(d_buf) - g.src_head, static_cast<uint8_t *>(d_out) - g.dst_head, d_off,
+                       d_start, static_cast<const uint8_t *>(d_lit), g);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_subst_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, uint64_t n, uint32_t p,
+                       const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
+                       hipStream_t stream)
+{
+    if (n == 0 || index_cap == 0) return hipSuccess;
+    const uint64_t nent = n * p, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    hipLaunchKernelGGL(sre_k_subst_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_start, d_ends, nent,
+                       (uint64_t) p, d_blk + nblk, d_info, index_cap, d_index);
     return hipGetLastError();
 }

@@ -18,6 +18,12 @@
  * e = line * K + f, field f of the K chosen capture groups of a line: off[] is the prefix sum of (field length + 1)
  * of the selected lines' entries, the text of an entry starts at its word of the call's starts array, and the
  * byte behind it is the field separator, or the delimiter behind the last field of a line (sre_lg_tab_fields).
+ *
+ * Line substitute (sre_hip_substitute_lines) gathers over a table of PIECES e = line * P + f: the
+ * line's text in front of its first match, the pieces of the template, the text behind the match.  The pieces of a
+ * row abut: only the last entry of a line has a byte behind it (the delimiter), the text of every other entry runs to
+ * off[e + 1]; an entry may take no byte at all and is then never visited.  The text of a literal piece comes from the
+ * call's LITERAL BLOCK, a second 16-byte aligned extent (sre_lg_tab_pieces).
  */
 #ifndef SRE_LINES_GATHER_H
 #define SRE_LINES_GATHER_H
@@ -94,6 +100,11 @@ struct sre_lg_tab_global {
     const uint64_t *ends;
     SRE_LG_MEMBER uint64_t off(uint64_t i) const { return offs[i]; }
     SRE_LG_MEMBER uint64_t start(uint64_t i) const { return i ? ends[i - 1] + 1 : 0; }
+    SRE_LG_MEMBER bool     trails(uint64_t) const { return true; }
+    template <class Sink> SRE_LG_MEMBER void text(Sink &sink, uint64_t i, uint64_t at, uint32_t head, uint32_t d, uint32_t cnt) const
+    {
+        sink.text((uint64_t) head + start(i) + at, d, cnt);
+    }
     template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t, uint32_t d) const { sink.delim(d); }
 };
 
@@ -104,6 +115,11 @@ struct sre_lg_tab_window {
     uint64_t        base;
     SRE_LG_MEMBER uint64_t off(uint64_t i) const { return offs[i - base]; }
     SRE_LG_MEMBER uint64_t start(uint64_t i) const { return starts[i - base]; }
+    SRE_LG_MEMBER bool     trails(uint64_t) const { return true; }
+    template <class Sink> SRE_LG_MEMBER void text(Sink &sink, uint64_t i, uint64_t at, uint32_t head, uint32_t d, uint32_t cnt) const
+    {
+        sink.text((uint64_t) head + start(i) + at, d, cnt);
+    }
     template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t, uint32_t d) const { sink.delim(d); }
 };
 
@@ -122,11 +138,42 @@ struct sre_lg_tab_fields {
     SRE_LG_MEMBER uint64_t off(uint64_t e) const { return offs[e - base]; }
     SRE_LG_MEMBER uint64_t raw(uint64_t e) const { return starts[e - base]; }
     SRE_LG_MEMBER uint64_t start(uint64_t e) const { return starts[e - base] & SRE_LG_ENTRY_START; }
+    SRE_LG_MEMBER bool     trails(uint64_t) const { return true; }
+    template <class Sink> SRE_LG_MEMBER void text(Sink &sink, uint64_t e, uint64_t at, uint32_t head, uint32_t d, uint32_t cnt) const
+    {
+        sink.text((uint64_t) head + start(e) + at, d, cnt);
+    }
     template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t e, uint32_t d) const
     {
         if (starts[e - base] & SRE_LG_ENTRY_LAST) sink.delim(d);
         else sink.sep(d);
     }
+};
+
+/* the piece table of the line substitute, whole (base 0, global memory) or a window of it (LDS): entries
+ * e = line * P + f, f = 0 the line's text in front of the match (FIRST), f = 1 .. P - 2 the template's pieces,
+ * f = P - 1 the text behind the match (LAST; its value counts the delimiter too, so the last entry of a selected line
+ * always takes a byte).  One more flag below the three: the text of a LITERAL entry starts at its offset in the
+ * literal block, not in the source.  UNSET on a piece: the group is unset; on the FIRST entry: the line has no match
+ * and is copied whole (index rows only).  Only the LAST entry has a byte behind its text */
+#define SRE_LG_ENTRY_LITERAL    (1ull << 60)
+#define SRE_LG_PIECE_START      (SRE_LG_ENTRY_LITERAL - 1)
+
+struct sre_lg_tab_pieces {
+    const uint64_t *offs;
+    const uint64_t *starts;
+    uint64_t        base;
+    SRE_LG_MEMBER uint64_t off(uint64_t e) const { return offs[e - base]; }
+    SRE_LG_MEMBER uint64_t raw(uint64_t e) const { return starts[e - base]; }
+    SRE_LG_MEMBER uint64_t start(uint64_t e) const { return starts[e - base] & SRE_LG_PIECE_START; }
+    SRE_LG_MEMBER bool     trails(uint64_t e) const { return (starts[e - base] & SRE_LG_ENTRY_LAST) != 0; }
+    template <class Sink> SRE_LG_MEMBER void text(Sink &sink, uint64_t e, uint64_t at, uint32_t head, uint32_t d, uint32_t cnt) const
+    {
+        const uint64_t w = starts[e - base];
+        if (w & SRE_LG_ENTRY_LITERAL) sink.literal((w & SRE_LG_PIECE_START) + at, d, cnt);
+        else sink.text((uint64_t) head + (w & SRE_LG_PIECE_START) + at, d, cnt);
+    }
+    template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t, uint32_t d) const { sink.delim(d); }
 };
 
 /* the last i of [lo, hi] with off(i) <= o; the caller knows off(lo) <= o */
@@ -194,10 +241,17 @@ sre_lg_tile_slice(const Tab &tab, const sre_lg_geom_t &g, uint64_t tile, uint64_
  *   sink.text(S, d, cnt)   cnt source bytes from position S go to bytes d .. d + cnt - 1 of the chunk
  *   sink.delim(d)          byte d of the chunk is the delimiter
  *   sink.sep(d)            ... the field separator (the entry table of the line extract only)
+ *   sink.literal(L, d, cnt) cnt bytes from offset L of the literal block (the piece table of the line substitute only)
  * and the chunk's bytes [*first, *first + *count) are the ones the call owns (all 16 except in the first and
  * the last chunk of the output).  Every selected line takes at least its delimiter byte, so a chunk meets at
  * most 16 lines and the loop runs at most 16 times; stepping to the next selected line is one look at the
  * table when the next line is selected and a search otherwise, never a walk over the lines in between.
+ *
+ * The table says how an entry ends: tab.trails(i) is true when one byte follows the entry's text (tab.end emits it),
+ * and the text is then output bytes [off(i), off(i + 1) - 1); otherwise the text runs to off(i + 1).  The tables of
+ * the filter and the extract answer true for every entry at compile time.  An entry that takes no byte is never
+ * visited, the step to the next entry that takes bytes skips it, so every visited entry still takes at least one
+ * byte of the chunk.
  */
 template <class Tab, class Sink>
 SRE_LG_FN bool
@@ -212,12 +266,14 @@ sre_lg_walk(const Tab &tab, const sre_lg_geom_t &g, uint64_t c, uint64_t lo, uin
     uint64_t i = sre_lg_find(tab, o, lo, hi);
     for (;;) {
         const uint64_t b = tab.off(i), e = tab.off(i + 1);      /* the line is output bytes [b, e), e - 1 its delimiter */
-        const uint64_t t_end = o_hi < e - 1 ? o_hi : e - 1;
+        const bool     tr = tab.trails(i);
+        const uint64_t t_lim = tr ? e - 1 : e;
+        const uint64_t t_end = o_hi < t_lim ? o_hi : t_lim;
         if (o < t_end) {
-            sink.text((uint64_t) g.src_head + tab.start(i) + (o - b), (uint32_t) (o + g.dst_head - p0), (uint32_t) (t_end - o));
+            tab.text(sink, i, o - b, g.src_head, (uint32_t) (o + g.dst_head - p0), (uint32_t) (t_end - o));
             o = t_end;
         }
-        if (o < o_hi) {
+        if (tr && o < o_hi) {
             tab.end(sink, i, (uint32_t) (o + g.dst_head - p0));
             o++;
         }
@@ -236,6 +292,10 @@ sre_lg_walk(const Tab &tab, const sre_lg_geom_t &g, uint64_t c, uint64_t lo, uin
  * are all text of the line.  A shorter piece comes from the one or two aligned blocks that hold its bytes,
  * funnelled into place; those blocks lie inside the 16-byte aligned extent of the source buffer because they
  * hold bytes of it.
+ *
+ * The text of a literal piece comes the same way from the literal block, through mem.lit_load(q) and
+ * mem.lit_loadu(L): the block starts at a 16-byte aligned address and is padded to a multiple of 16 bytes, so the
+ * aligned blocks that hold bytes of a literal lie inside it.
  */
 template <class Mem>
 struct sre_lg_assembler {
@@ -245,17 +305,31 @@ struct sre_lg_assembler {
 
     SRE_LG_MEMBER sre_lg_assembler(Mem &m, uint32_t d, uint32_t s) : mem(m), delim_byte(d), sep_byte(s) { acc.lo = 0; acc.hi = 0; }
 
-    SRE_LG_MEMBER void text(uint64_t s, uint32_t d, uint32_t cnt)
+    template <bool LIT> SRE_LG_MEMBER sre_lg_u128 block(uint64_t q)
+    {
+        if constexpr (LIT) return mem.lit_load(q);
+        else return mem.load(q);
+    }
+    template <bool LIT> SRE_LG_MEMBER sre_lg_u128 blocku(uint64_t s)
+    {
+        if constexpr (LIT) return mem.lit_loadu(s);
+        else return mem.loadu(s);
+    }
+
+    SRE_LG_MEMBER void text(uint64_t s, uint32_t d, uint32_t cnt) { put<false>(s, d, cnt); }
+    SRE_LG_MEMBER void literal(uint64_t s, uint32_t d, uint32_t cnt) { put<true>(s, d, cnt); }
+
+    template <bool LIT> SRE_LG_MEMBER void put(uint64_t s, uint32_t d, uint32_t cnt)
     {
         if (cnt == 16) {
-            acc = mem.loadu(s);
+            acc = blocku<LIT>(s);
             return;
         }
         const uint64_t q = s >> 4;
         const uint32_t sh = (uint32_t) (s & 15u);
-        sre_lg_u128    v = sre_lg_shr(mem.load(q), sh);
+        sre_lg_u128    v = sre_lg_shr(block<LIT>(q), sh);
         if (sh + cnt > 16) {
-            const sre_lg_u128 w = sre_lg_shl(mem.load(q + 1), 16 - sh);
+            const sre_lg_u128 w = sre_lg_shl(block<LIT>(q + 1), 16 - sh);
             v.lo |= w.lo;
             v.hi |= w.hi;
         }
