@@ -123,6 +123,35 @@ def test_split_edges(gpu):
                         assert info.nselected == info.nlines
 
 
+EMPTY_MATCH_LINES = [b"ab cd", b" x", b"", b"cd ab", b"x", b"b a"]
+
+
+@pytest.mark.parametrize("delim", [0x0A, ord("a")], ids=["newline", "a"])
+def test_an_empty_match_at_either_end_of_the_line(gpu, delim):
+    """^ and \\b match the empty string at offset 0 of a line that is not empty, $ at its end.  With the delimiter "a"
+    the byte behind a line's end (and the one in front of its start) is a word character, and the line is still its own
+    stream: \\b in front of "b cd" and $ behind it match"""
+    data = bytes([delim]).join(EMPTY_MATCH_LINES)
+    lines = split_lines(data, delim)
+    assert sum(1 for _, n in lines if n) >= 5 and any(n == 0 for _, n in lines)
+    with S.Pool() as pool:
+        for pat, at in [(rb"^", "start"), (rb"$", "end"), (rb"\b", None)]:
+            p = Program(pool, [pat], key=False)
+            for all_lines in (False, True):
+                _, want, sel = run_extract(p.sc, p.exp, data, [0], delim, src_off=1, dst_off=3, all_lines=all_lines)
+                if at:
+                    # every line matches, with an empty field: the output is one delimiter a line
+                    assert [(i, st, n) for i, st, n, _ in sel] == [(i, st, n) for i, (st, n) in enumerate(lines)]
+                    assert [f for _, _, _, f in sel] == [[(st + (n if at == "end" else 0), 0)] for st, n in lines]
+                    assert want == bytes([delim]) * len(lines)
+                elif not all_lines:
+                    # a line with a word character has its first boundary in front of its first word
+                    word = [(i, st + min(k for k in range(n) if data[st + k:st + k + 1].isalnum()))
+                            for i, (st, n) in enumerate(lines) if any(data[st + k:st + k + 1].isalnum() for k in range(n))]
+                    assert [(i, f[0]) for i, _, _, f in sel] == [(i, (o, 0)) for i, o in word]
+                    assert any(o == lines[i][0] for i, o in word) and any(o > lines[i][0] for i, o in word)
+
+
 # ------------------------------------------------------------------ 2. alignment and lengths
 
 LENGTHS = [0, 1, 15, 16, 17, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097]
@@ -347,19 +376,23 @@ def test_all_lines(gpu):
 
 # ------------------------------------------------------------------ 8. several batches
 
-@pytest.mark.parametrize("pats,engine,groups", [(URI, S.ENGINE_AUTO, [1, 2, 0]), (DOTTED, S.ENGINE_NFA, [0, 1, 1])],
-                         ids=["scan", "nfa"])
+@pytest.mark.parametrize("pats,engine,groups", [(URI, S.ENGINE_AUTO, [1, 2, 0]), (DOTTED, S.ENGINE_NFA, [0, 1, 1]),
+                                                (URI, S.ENGINE_VM, [2, 0, 4, 1])],
+                         ids=["scan", "nfa", "vm"])
 def test_several_batches(gpu, monkeypatch, pats, engine, groups):
+    """(vm: the per-line host route, which uploads the entries of a batch at d_val + i0 * k and d_start + i0 * k)"""
+    device = 0 if engine == S.ENGINE_VM else 1
     with S.Pool() as pool:
         p = Program(pool, pats, engine)
+        assert engine == S.ENGINE_AUTO or p.sc.engine == engine
         data = small_buffer(12, nlines=100)
         assert len(split_lines(data, 0x0A)) == 100
         info, one, _ = run_extract(p.sc, p.exp, data, groups, src_off=2, dst_off=9)
-        assert p.sc.last_line_batches == 1 and p.sc.last_lines_device == 1 and 0 < info.nselected < 100
+        assert p.sc.last_line_batches == 1 and p.sc.last_lines_device == device and 0 < info.nselected < 100
         monkeypatch.setenv("SRE_HIP_LINES_BATCH", "7")
         for all_lines in (False, True):
             _, many, _ = run_extract(p.sc, p.exp, data, groups, src_off=2, dst_off=9, all_lines=all_lines)
-            assert p.sc.last_line_batches == 15
+            assert p.sc.last_line_batches == 15 and p.sc.last_lines_device == device
             assert all_lines or many == one
 
 

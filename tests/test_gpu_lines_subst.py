@@ -15,8 +15,8 @@ import pytest
 import sregex_amd as S
 from test_gpu_lines import split_lines, upload_at
 from test_gpu_lines_filter import Out, download
-from test_gpu_lines_extract import (BRACKET, DOTTED, HEADLINE, LENGTHS, ROUTES, URI, URI_LINES, Program, bracketed_buffer,
-                                    random_lines, small_buffer)
+from test_gpu_lines_extract import (BRACKET, DOTTED, EMPTY_MATCH_LINES, HEADLINE, LENGTHS, ROUTES, URI, URI_LINES, Program,
+                                    bracketed_buffer, random_lines, small_buffer)
 from test_gpu_nfa_wide import WIDE
 
 pytestmark = pytest.mark.gpu
@@ -135,6 +135,30 @@ def test_split_edges(gpu):
                         if data == b"":
                             assert info == S.FilterInfo(0, 0, 0, 0, 0)
                         assert info.nselected == info.nlines
+
+
+@pytest.mark.parametrize("delim", [0x0A, ord("a")], ids=["newline", "a"])
+def test_an_empty_match_at_either_end_of_the_line(gpu, delim):
+    """sed 's/^/> /' and sed 's/$/;/': the empty match at offset 0 of a line that is not empty, and at its end.  With
+    the delimiter "a" the byte behind a line's end (and the one in front of its start) is a word character, and the line
+    is still its own stream: \\b in front of "b cd" and $ behind it match"""
+    d = bytes([delim])
+    data = d.join(EMPTY_MATCH_LINES)
+    lines = [data[st:st + n] for st, n in split_lines(data, delim)]
+    assert sum(1 for line in lines if line) >= 5 and b"" in lines
+    with S.Pool() as pool:
+        for pat, template, row in [(rb"^", b"> ", lambda line: b"> " + line), (rb"$", b";", lambda line: line + b";"),
+                                   (rb"^", b"", lambda line: line), (rb"\b", b"> ", None), (rb"\b", b";", None)]:
+            p = Program(pool, [pat], key=False)
+            for all_lines in (False, True):
+                _, want, sel = run_subst(p.sc, p.exp, data, template, delim, src_off=1, dst_off=3, all_lines=all_lines)
+                if row:
+                    assert len(sel) == len(lines) and want == b"".join(row(line) + d for line in lines)
+                elif not all_lines:
+                    # a line with a word character gets the template in front of its first word
+                    words = [line for line in lines if any(bytes([c]).isalnum() for c in line)]
+                    assert [r for _, _, _, _, r in sel] == [w[:len(w) - len(w.lstrip())] + template + w.lstrip() for w in words]
+                    assert any(w[:1] != b" " for w in words) and any(w[:1] == b" " for w in words)
 
 
 # ------------------------------------------------------------------ 2. identity
@@ -317,20 +341,24 @@ def test_truncation(gpu):
 
 # ------------------------------------------------------------------ 9. several batches
 
-@pytest.mark.parametrize("pats,engine,template", [(URI, S.ENGINE_AUTO, b"$1:$2"), (DOTTED, S.ENGINE_NFA, b"<$0$1>")],
-                         ids=["scan", "nfa"])
+@pytest.mark.parametrize("pats,engine,template", [(URI, S.ENGINE_AUTO, b"$1:$2"), (DOTTED, S.ENGINE_NFA, b"<$0$1>"),
+                                                  (URI, S.ENGINE_VM, b"$2 $4|$1")],
+                         ids=["scan", "nfa", "vm"])
 def test_several_batches(gpu, monkeypatch, pats, engine, template):
+    """(vm: the per-line host route, which uploads the entries of a batch at d_val + i0 * P and d_start + i0 * P)"""
+    device = 0 if engine == S.ENGINE_VM else 1
     with S.Pool() as pool:
         p = Program(pool, pats, engine)
+        assert engine == S.ENGINE_AUTO or p.sc.engine == engine
         data = small_buffer(12, nlines=100)
         assert len(split_lines(data, 0x0A)) == 100
         info, one, _ = run_subst(p.sc, p.exp, data, template, src_off=2, dst_off=9)
         _, one_all, _ = run_subst(p.sc, p.exp, data, template, src_off=2, dst_off=9, all_lines=True)
-        assert p.sc.last_line_batches == 1 and p.sc.last_lines_device == 1 and 0 < info.nselected < 100
+        assert p.sc.last_line_batches == 1 and p.sc.last_lines_device == device and 0 < info.nselected < 100
         monkeypatch.setenv("SRE_HIP_LINES_BATCH", "7")
         for all_lines in (False, True):
             _, many, _ = run_subst(p.sc, p.exp, data, template, src_off=2, dst_off=9, all_lines=all_lines)
-            assert p.sc.last_line_batches == 15
+            assert p.sc.last_line_batches == 15 and p.sc.last_lines_device == device
             assert many == (one_all if all_lines else one)
 
 
