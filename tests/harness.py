@@ -303,6 +303,31 @@ def random_regex(rng, depth=0, wide=None):
     return b"".join(seq)
 
 
+# ------------------------------------------------------------------ the scanner's 8-bit index form
+
+# The scan kernel indexes its fast table with packed byte classes (1, 2 or 4 bits each) up to 16 classes and
+# with the input byte itself above that.  This alternative adds 17 byte classes to any program and leaves the
+# rest of it alone, so a padded program has more than 16 (tests/test_gpu_scan_forms.py, tests/test_scan_model.py).
+SCAN_PAD = b"|0123456789ABCDEFG"
+
+
+def pad_into_8bit_form(pats):
+    """the same regexes, the first one with the SCAN_PAD alternative"""
+    return [pats[0] + SCAN_PAD] + list(pats[1:])
+
+
+def padded_subject(rng, size, alphabet=b"abcx \n_."):
+    """`size` random bytes over the alphabet and, with probability 1/2, one insertion at a random position: the
+    pad's literal, a prefix of it, or one of the bytes 0x00 0x80 0xff"""
+    d = bytearray(rng.choice(alphabet) for _ in range(size))
+    if rng.random() < 0.5:
+        lit = SCAN_PAD[1:]
+        ins = rng.choice([lit, lit[:rng.randrange(1, len(lit))], bytes([rng.choice(b"\x00\x80\xff")])])
+        at = rng.randrange(0, len(d) + 1)
+        d[at:at] = ins
+    return bytes(d)
+
+
 # ------------------------------------------------------------------ recorded replies of the reference
 
 # The randomised differential tests (test_frontend_fuzz.py, test_oracle.py's live differential) put

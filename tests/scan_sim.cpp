@@ -365,6 +365,20 @@ void scan_sim_count(void *dv, const uint8_t *data, int64_t n, int span, int64_t 
     out[8] = L.f(F_LM_VALID) ? L.lm_pos : -1;
 }
 
+/* which form of the scan kernel the automaton gets (sre_scan_fast_build picks the index width by the number of byte
+ * classes): out[0] = byte classes, out[1] = states, out[2] = class bits of the index, out[3] = 1 when the COUNT
+ * table has FRESH states */
+void scan_sim_shape(void *dv, int64_t *out)
+{
+    const sre_dfa_t *d = static_cast<const sre_dfa_t *>(dv);
+    sre_scan_fast_t  F;
+    sre_scan_fast_build(d, SRE_HIP_PIKE_COUNT, &F);
+    out[0] = d->ncls;
+    out[1] = d->nstates;
+    out[2] = F.bits;
+    out[3] = F.any_fresh;
+}
+
 /* the state of the ONE search that starts at sp, in front of position q (no restarts: the automaton alone) */
 uint32_t scan_sim_state_at(void *dv, const uint8_t *data, int64_t sp, int64_t q)
 {

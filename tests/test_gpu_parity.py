@@ -1446,15 +1446,21 @@ def test_scanner_random_patterns_vs_oracle(gpu, seg):
                                     "s": d.hex(), "got": recs[i], "want": want if want is not None else [th]})
             for b in bufs:
                 b.free()
+    record_fuzz_failures(bad)
+    assert admitted > 400, (tested, admitted)
+    assert nfa_admitted > 300, nfa_admitted
+    assert not bad, (len(bad), [(b["engine"], b["mode"], bytes.fromhex(b["re"][0]), b["got"][:4], b["want"][:4])
+                               for b in bad[:6]])
+
+
+def record_fuzz_failures(bad):
+    """append the failing cases of a randomised test to the log that tools/fuzz_repro.py --file replays"""
+    import json
     if bad:
         os.makedirs(os.path.join(harness.ROOT, "gpurun_out"), exist_ok=True)
         with open(os.path.join(harness.ROOT, "gpurun_out", "fuzz_fail.jsonl"), "a") as f:
             for rec in bad:
                 f.write(json.dumps(rec) + "\n")
-    assert admitted > 400, (tested, admitted)
-    assert nfa_admitted > 300, nfa_admitted
-    assert not bad, (len(bad), [(b["engine"], b["mode"], bytes.fromhex(b["re"][0]), b["got"][:4], b["want"][:4])
-                               for b in bad[:6]])
 
 
 def test_exact_vm_stable_runs_vs_oracle(gpu):

@@ -108,9 +108,9 @@ def check_record(rec, want, ctx):
         assert rec[5 + k] == v, (ctx, k, rec, want)
 
 
-def run_schedules(gpu, pool, prog, ncaps, mode, subs, scheds, rng, idle=0.2):
+def run_schedules(gpu, pool, prog, ncaps, mode, subs, scheds, rng, idle=0.2, engine=None):
     """feed every stream its schedule, all streams in each call; returns the number of
-    (stream, call) pairs compared with the oracle"""
+    (stream, call) pairs compared with the oracle.  engine: the engine the set must run on"""
     ora = harness.OracleEngine()
     n = len(subs)
     blob = b"#" + b"".join(subs)            # natural (odd) offsets
@@ -121,6 +121,7 @@ def run_schedules(gpu, pool, prog, ncaps, mode, subs, scheds, rng, idle=0.2):
     buf = S.DeviceBuffer.from_bytes(blob)
     ss = S.StreamSet(pool, prog, mode, n)
     assert ss.n == n and ss.slots == 5 + 2 * (ncaps + 1)
+    assert engine is None or ss.engine == engine, (ss.engine, engine)
     streams = [OracleStream(ora, prog, ncaps, mode == S.HIP_THOMPSON) for _ in range(n)]
     nxt = [0] * n
     compared = 0

@@ -38,6 +38,7 @@ def sim(lib):
     L.scan_sim_count.argtypes = [_vp, ctypes.c_char_p, _i64, ctypes.c_int, ctypes.POINTER(_i64)]
     L.scan_sim_state_at.restype = ctypes.c_uint32
     L.scan_sim_state_at.argtypes = [_vp, ctypes.c_char_p, _i64, _i64]
+    L.scan_sim_shape.argtypes = [_vp, ctypes.POINTER(_i64)]
     return L
 
 
@@ -129,3 +130,50 @@ def test_count_lane_model_vs_oracle(sim):
     assert n > 3000 and grow > 200 and anchors > 500, (n, grow, anchors)
     # most bytes take fast entries (the folds keep the iteration on the table)
     assert fast > 0.5 * total, (fast, total)
+
+
+def test_count_lane_model_8bit_index_vs_oracle(sim):
+    """The same model on the 8-bit index form (more than 16 byte classes: the table is indexed by the input byte
+    itself, one byte per entry), which the generator's alphabet never reaches by itself: 300 random programs padded
+    with harness.SCAN_PAD, subjects that hold the pad's literal, prefixes of it and the bytes 0x00 0x80 0xff.  A
+    failure of tests/test_gpu_scan_forms.py that this test does not share is a kernel bug, not a table bug."""
+    ora = harness.OracleEngine()
+    rng = random.Random(int(os.environ.get("SRE_FUZZ_SEED", "20261004")) + 8)
+    programs, eight, n = 300, 0, 0
+    bad = []
+    for _ in range(programs):
+        nre = 1 if rng.random() < 0.8 else rng.randrange(2, 4)
+        pats = harness.pad_into_8bit_form([harness.random_regex(rng) for _ in range(nre)])
+        datas = [harness.padded_subject(rng, rng.choice([0, 1, 7, 64, 65, 130, 400, 1500])) for _ in range(6)]
+        with S.Pool() as pool:
+            try:
+                re = S.parse(pool, pats)
+            except Exception:
+                continue
+            prog = S.compile(pool, re)
+            why = ctypes.c_char_p()
+            d = sim.sre_dfa_build(prog.h, 63, ctypes.byref(why))
+            if not d:
+                continue
+            shape = (_i64 * 4)()
+            sim.scan_sim_shape(d, shape)
+            assert (shape[2] == 8) == (shape[0] > 16), list(shape)
+            eight += shape[0] > 16
+            if len(pats) > 1 and any(tok in p for p in pats for tok in (b"^", b"\\A", b"$", b"\\z", b"\\b", b"\\B")):
+                sim.sre_dfa_free(d)
+                continue        # the scanner declines COUNT with ^ or look-ahead over several regexes (sre_scan_host.cpp)
+            for data in datas:
+                want = _want(ora, prog, re.ncaps, data)
+                for span in (64, 16, 0):
+                    out = (_i64 * 9)()
+                    sim.scan_sim_count(d, bytes(data), len(data), span, out)
+                    got = (out[0], out[1], out[2], bool(out[3] & 8))
+                    n += 1
+                    ok = got[0] == want[0] and got[1] == want[1] and got[3] == want[3] and (got[2] < 0 or got[2] == want[2])
+                    if out[3] & 16 or not ok:
+                        bad.append((pats, data[:60], len(data), span, got, want, out[3]))
+            sim.sre_dfa_free(d)
+    assert not bad, (len(bad), bad[:4])
+    # (the rest exceed the builder's cap of 63 states)
+    assert eight >= 0.75 * programs, (eight, programs)
+    assert n > 3000, n
