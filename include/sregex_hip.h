@@ -299,6 +299,76 @@ SRE_API int sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_
     int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap,
     sre_hip_filter_info_t *info, void *hip_stream);
 
+/* ---- line filter with context lines: grep -A / -B / -C ---- */
+
+typedef struct {
+    size_t nlines;      /* lines in the buffer */
+    size_t nmatched;    /* lines the match rule selects (what sre_hip_filter_lines would select) */
+    size_t nselected;   /* nmatched + context-only lines */
+    size_t ngroups;     /* maximal runs of adjacent selected lines (what grep separates with "--") */
+    size_t need_bytes;  /* sum of (len + 1) over the selected lines */
+    size_t nwritten;    /* selected lines written (whole lines only) */
+    size_t out_bytes;   /* bytes written to d_out */
+} sre_hip_context_info_t;
+
+/*
+ * Line filter with context: the matching lines and the lines around them (grep -A after,
+ * -B before, -C both), selected on the device.  The split of d_buf, the matching of every line
+ * and the engine a scanner routes to are exactly those of sre_hip_filter_lines on the same
+ * (sc, d_buf, len, delim); every scanner mode and every engine route is accepted.
+ *
+ * The match rule.  Line j is MATCHED when sre_hip_filter_lines with the same flags would select
+ * it:
+ *   - flags == 0: its rc is not SRE_DECLINED;
+ *   - SRE_HIP_LINES_INVERT: its rc is SRE_DECLINED (grep -v -C);
+ *   - SRE_HIP_LINES_ALL: every line, and then only with before == after == 0: ALL with context
+ *     returns -1;
+ *   - ALL | INVERT, and any other flag bit, return -1.
+ *
+ * Selection.  Line i is SELECTED when it is matched, or when some matched line j has
+ * j < i <= j + after (-A) or i < j <= i + before (-B).  Every selected line is written once, in
+ * line order, however many contexts overlap, as GNU grep does.  before and after may be any
+ * size_t: a value at or above the number of lines means "to the end of the buffer", and nothing
+ * overflows.  The work per line does not depend on them.
+ *
+ * before == after == 0 gives byte for byte the output, the index words [0] .. [3] and the counts
+ * of sre_hip_filter_lines (nselected == nmatched), and no kernel of the context pass runs.
+ *
+ * Output, truncation.  As sre_hip_filter_lines: d_out is a DEVICE pointer at any alignment to
+ * out_cap bytes that do not overlap [d_buf, d_buf + len) (an overlap returns -1); each selected
+ * line is its bytes followed by ONE delim byte, an empty context line still takes that byte, and
+ * a final line without a delimiter gets one; only whole lines are written, no byte at or beyond
+ * out_bytes is touched and nothing in front of d_out; d_out may be NULL when out_cap == 0 (a
+ * sizing call).  Not offered: a group separator in the output (grep's "--").  The output stays a
+ * well-formed line buffer of source lines; a caller that wants the separator puts it in front
+ * of the rows whose index word [4] has bit 1, other than the first.
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten)
+ * written lines it receives FIVE sre_int_t, with or without context,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the line in d_out
+ *   [4] flags: bit 0 set for a context-only line (selected, not matched itself); bit 1 set for
+ *       the first line of a group (line 0, or a line whose predecessor is not selected).
+ * d_index may be NULL when index_cap == 0.  info may be NULL.
+ *
+ * Counts.  info->nmatched, nselected, ngroups and need_bytes are totals over the whole buffer,
+ * whatever out_cap is.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  On the routes where
+ * sre_hip_scanner_last_lines_device() is 1 nothing per line travels to the host: the host reads
+ * two words more than sre_hip_filter_lines does, in the same copy.  The other routes keep their
+ * per-line host work and upload one word per line, as for the filter; the context pass runs
+ * behind them on the device.  Batch cuts need no care: the pass runs once, over the values of
+ * the whole call.  The call replaces the scanner's last call and the diagnostics describe it
+ * exactly as for sre_hip_filter_lines.  len == 0 gives all zeros in info and success.
+ * Beyond what sre_hip_filter_lines takes, a scanner keeps one bit per line of the largest call
+ * with context plus 32 bytes per 1024 lines of the largest call of device memory, grow-only,
+ * freed with the scanner.  Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_filter_lines_context(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    int flags, size_t before, size_t after, void *d_out, size_t out_cap,
+    sre_int_t *d_index, size_t index_cap, sre_hip_context_info_t *info, void *hip_stream);
+
 /* ---- line extract: capture groups of each matching line as delimited rows in a device buffer ---- */
 
 enum { SRE_HIP_EXTRACT_MAX_FIELDS = 32 };

@@ -83,6 +83,8 @@ API = {
     "sre_hip_scan_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _pssz, _sz,
                                           ctypes.POINTER(_sz), ctypes.POINTER(_sz), _vp]),
     "sre_hip_filter_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_filter_lines_context": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _sz, _sz, _vp, _sz, _vp, _sz, _vp,
+                                                    _vp]),
     "sre_hip_extract_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int,
                                              ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_subst_template_check": (ctypes.c_int, [ctypes.c_char_p, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
@@ -440,6 +442,21 @@ class Scanner:
             raise RuntimeError("sre_hip_filter_lines failed")
         return FilterInfo(*info)
 
+    def filter_lines_context(self, ptr, length, out_ptr, out_cap, before=0, after=0, delim=0x0A, invert=False, index_ptr=None,
+                             index_cap=0, hip_stream=None):
+        """sre_hip_filter_lines_context: filter_lines with context lines (grep -B before -A after): the matching lines
+        of the device buffer (ptr, length), with invert the lines without a match, and every line at most `before`
+        lines in front of one or `after` lines behind one, each once, in line order, each followed by one delimiter,
+        in the device buffer (out_ptr, out_cap).  index_ptr: an optional device array of index_cap rows of FIVE words
+        [line no, offset in the buffer, length, offset in the output, flags]; flags bit 0: a context-only line, bit 1:
+        the first line of a group of adjacent selected lines.  Returns ContextInfo(nlines, nmatched, nselected,
+        ngroups, need_bytes, nwritten, out_bytes)."""
+        info = (_sz * 7)()
+        if self.lib.sre_hip_filter_lines_context(self.h, ptr, length, delim, HIP_LINES_INVERT if invert else 0, before, after,
+                                                 out_ptr, out_cap, index_ptr, index_cap, info, hip_stream) != 0:
+            raise RuntimeError("sre_hip_filter_lines_context failed")
+        return ContextInfo(*info)
+
     def extract_lines(self, ptr, length, groups, out_ptr, out_cap, delim=0x0A, fsep=0x09, all_lines=False, index_ptr=None,
                       index_cap=0, hip_stream=None):
         """sre_hip_extract_lines: for every matching line of the device buffer (ptr, length) (every line with
@@ -489,6 +506,7 @@ class Scanner:
 
 
 FilterInfo = collections.namedtuple("FilterInfo", "nlines nselected need_bytes nwritten out_bytes")
+ContextInfo = collections.namedtuple("ContextInfo", "nlines nmatched nselected ngroups need_bytes nwritten out_bytes")
 
 
 class StreamSet:

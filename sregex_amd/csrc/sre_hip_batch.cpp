@@ -137,6 +137,11 @@ struct sre_hip_scanner_s {
     size_t                    fval_cap;
     uint64_t                 *d_fblk;           /* per-workgroup sums of the scan: 2 words per SRE_LINES_ITEMS lines */
     size_t                    fblk_cap;
+    /* its context lines (sre_hip_filter_lines_context) add */
+    uint64_t                 *d_cbits;          /* the context bitmap: one bit per line */
+    size_t                    cbits_cap;
+    uint64_t                 *d_cblk;           /* block words and counts of the context pass: 4 words per SRE_LINES_ITEMS lines */
+    size_t                    cblk_cap;
     /* the line extract (sre_hip_extract_lines) shares both, sized by its entries (lines x fields), and adds */
     uint64_t                 *d_fstart;         /* per-entry source offsets under their flags: lines x fields words */
     size_t                    fstart_cap;
@@ -204,6 +209,8 @@ scanner_release(void *data)
     if (sc->d_rows) (void) hipFree(sc->d_rows);
     if (sc->d_fval) (void) hipFree(sc->d_fval);
     if (sc->d_fblk) (void) hipFree(sc->d_fblk);
+    if (sc->d_cbits) (void) hipFree(sc->d_cbits);
+    if (sc->d_cblk) (void) hipFree(sc->d_cblk);
     if (sc->d_fstart) (void) hipFree(sc->d_fstart);
     if (sc->d_lit) (void) hipFree(sc->d_lit);
     free(sc->h_lit);
@@ -2096,6 +2103,68 @@ sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
         SRE_HIP_TRY(sre_launch_lines_gather(d_buf, d_out, sc->d_fval, sc->d_ends, n, res.out_bytes, (uint32_t) delim, stream));
         if (res.nwritten != 0) {
             SRE_HIP_TRY(sre_launch_filter_index(sc->d_fval, sc->d_ends, n, sc->d_fblk, sc->d_linfo, index_cap, d_index, stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The line filter with context lines: sre_hip_filter_lines with one more device pass between the
+ * line-mode call and the scan, the dilation of the per-line values by `before` and `after` lines, two more words in the
+ * one read, and index rows of five words.  Without context no kernel of the pass runs: the values, the offset table and
+ * the gather are the filter's, and the groups are counted from the offset table. */
+extern "C" SRE_API int
+sre_hip_filter_lines_context(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, size_t before,
+    size_t after, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_context_info_t *info,
+    void *hip_stream)
+{
+    const int  known = SRE_HIP_LINES_ALL | SRE_HIP_LINES_INVERT;
+    const bool context = before != 0 || after != 0;
+    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~known) != 0 || (flags & known) == known
+        || ((flags & SRE_HIP_LINES_ALL) && context) || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL)
+        || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0, NULL, NULL, NULL};
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_context_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_cblk, &sc->cblk_cap, 4 * nblk * sizeof(uint64_t)) != 0) return -1;
+        if (context) {
+            if (lines_grow(&sc->d_cbits, &sc->cbits_cap, (n + 63) / 64 * sizeof(uint64_t)) != 0) return -1;
+            SRE_HIP_TRY(sre_launch_context_select(sc->d_fval, sc->d_ends, n, before, after, sc->d_cbits, sc->d_cblk, sc->d_linfo,
+                                                  stream));
+        }
+        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_fval, n, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        if (!context) SRE_HIP_TRY(sre_launch_context_runs(sc->d_fval, n, sc->d_cblk, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nselected = (size_t) sc->h_linfo->fsel;
+        res.nmatched = context ? (size_t) sc->h_linfo->cmatched : res.nselected;
+        res.ngroups = (size_t) sc->h_linfo->cgroups;
+        res.need_bytes = (size_t) sc->h_linfo->fneed;
+        res.nwritten = (size_t) sc->h_linfo->fwritten;
+        res.out_bytes = (size_t) sc->h_linfo->fbytes;
+        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
+        SRE_HIP_TRY(sre_launch_lines_gather(d_buf, d_out, sc->d_fval, sc->d_ends, n, res.out_bytes, (uint32_t) delim, stream));
+        if (res.nwritten != 0) {
+            SRE_HIP_TRY(sre_launch_context_index(sc->d_fval, sc->d_ends, n, sc->d_fblk, context ? sc->d_cbits : NULL, sc->d_linfo,
+                                                 index_cap, d_index, stream));
         }
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }

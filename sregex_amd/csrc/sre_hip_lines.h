@@ -46,6 +46,9 @@ typedef struct {
     uint64_t fneed;         /* bytes all of them take */
     uint64_t fwritten;      /* selected lines that fit out_cap whole */
     uint64_t fbytes;        /* bytes of those */
+    /* the filter with context (sre_hip_filter_lines_context): two more words, read with the four */
+    uint64_t cmatched;      /* lines the match rule selects (with context only; without, fsel says it) */
+    uint64_t cgroups;       /* maximal runs of adjacent selected lines */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -107,6 +110,21 @@ hipError_t sre_launch_lines_gather(const void *d_buf, void *d_out, const uint64_
 /* rows [line, start, len, output offset] of the first min(index_cap, info->fwritten) written lines */
 hipError_t sre_launch_filter_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
     const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
+/* ---- the filter's context lines (sre_hip_lines_context.hip) ---- */
+/* between the last select pass and sre_launch_filter_offsets: every line within `after` lines behind a line with
+ * d_val[i] > 0 or `before` lines in front of one gets d_val[i] = len + 1 too (marks, carry, apply: a cost per line that
+ * does not depend on before / after).  d_bits: ceil(n / 64) words, bit i set for such a context-only line; d_blk:
+ * 4 x ceil(n / SRE_LINES_ITEMS) words of its own (nothing of it is read afterwards); info->cmatched, cgroups */
+hipError_t sre_launch_context_select(uint64_t *d_val, const uint64_t *d_ends, uint64_t n, uint64_t before, uint64_t after,
+    uint64_t *d_bits, uint64_t *d_blk, sre_lines_info_t *d_info, hipStream_t stream);
+/* the call without context, behind sre_launch_filter_offsets: info->cgroups from the offset table (and cmatched = 0:
+ * info->fsel is the count); d_blk: ceil(n / SRE_LINES_ITEMS) words of its own */
+hipError_t sre_launch_context_runs(const uint64_t *d_off, uint64_t n, uint64_t *d_blk, sre_lines_info_t *d_info,
+    hipStream_t stream);
+/* sre_launch_filter_index with rows of FIVE words: [4] bit 0 = context-only (from d_bits; NULL: no line is), bit 1 =
+ * first line of a group.  d_blk: the words of sre_launch_filter_offsets */
+hipError_t sre_launch_context_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
+    const uint64_t *d_bits, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
 /* ---- the line extract (sre_hip_lines_gather.hip) ---- */
 #define SRE_EXTRACT_MAX_FIELDS 32u
 /* the chosen capture groups: field f of a row is group g[f] of the line's record */
