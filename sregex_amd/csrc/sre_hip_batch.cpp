@@ -75,7 +75,6 @@ struct sre_hip_scanner_s {
     int                       blocks_per_cu;
     hipStream_t               tail_stream;      /* sre_hip_scanner_set_tail_stream */
     bool                      tail_stream_set;
-    uint32_t                  geom_one;         /* SRE_GEOM_ONE when the batch in flight is one stream in the kernel arguments */
     int                       fixup_rounds;     /* of the last scan (diagnostics) */
     hipEvent_t                ev0, ev1;         /* around the dominant scan kernel */
     int                       ev_valid;
@@ -787,6 +786,72 @@ scan_seg_knobs(sre_hip_scanner_t *sc)
     return seg;
 }
 
+/* ... on the NFA tier: the set kernels take any multiple of the 64-byte round (tests cut streams into
+ * segments that are shorter than the warm-up) */
+static uint64_t
+nfa_seg_knobs(sre_hip_scanner_t *sc)
+{
+    uint64_t seg = scan_seg_knobs(sc);
+    const char *e = getenv("SRE_HIP_SEG_BYTES");
+    if (seg == 0 && e && atoi(e) > 0 && atoi(e) % 64 == 0) seg = (uint64_t) atoi(e);
+    return seg;
+}
+
+/* the longest automatic segment (behind scan_seg_knobs: SRE_HIP_SEG_CAP) */
+static uint64_t
+scan_seg_cap(const sre_hip_scanner_t *sc)
+{
+    return sc->seg_cap_env ? sc->seg_cap_env : 40960;
+}
+
+/* the events around the dominant scan kernel */
+static int
+scan_events(sre_hip_scanner_t *sc)
+{
+    if (sc->ev0 == NULL) {
+        SRE_HIP_TRY(hipEventCreate(&sc->ev0));
+        SRE_HIP_TRY(hipEventCreate(&sc->ev1));
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* a call begins: the diagnostics describe it alone */
+static void
+call_begin(sre_hip_scanner_t *sc)
+{
+    sc->last_lines = false;
+    sc->fixup_rounds = 0;
+    sc->exact_passes = 0;
+    sc->lineage_passes = 0;
+    sc->ev_valid = 0;
+}
+
+/* A call's geometry begins cleared, the side channel sc->d_eset with it: what a call adds on top (the
+ * digest, sentry, sflags, the per-stream entry sets) it sets afterwards, and nothing of the call before
+ * is left to undo */
+static void
+geom_clear(sre_hip_scanner_t *sc)
+{
+    sc->geom = sre_scan_geom_t();
+    sc->d_eset = NULL;
+}
+
+/* the geometry of a batch whose stream arrays a kernel wrote into d_ptrs / d_lens / d_seg_first
+ * (never SRE_GEOM_ONE: the arrays live on the device) */
+static void
+geom_device(sre_hip_scanner_t *sc, uint64_t n, uint64_t seg, uint64_t nsegs)
+{
+    geom_clear(sc);
+    sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
+    sc->geom.lens = sc->d_lens;
+    sc->geom.seg_first = sc->d_seg_first;
+    sc->geom.nstreams = (uint32_t) n;
+    sc->geom.seg_bytes = (uint32_t) seg;
+    sc->geom.nsegs = nsegs;
+}
+
 /* lanes the chip holds at once with this scanner's kernel */
 static uint64_t
 scan_resident(sre_hip_scanner_t *sc)
@@ -833,9 +898,11 @@ hip_failed:
  * of workgroups is steered towards a whole multiple of what the chip holds at
  * once (LDS-limited: 160 KiB per CU), so the last round of workgroups is not
  * mostly empty; segments are a multiple of the 64-byte tile and at least 1 KiB
- * so that the speculative warm-up stays a few percent. */
+ * so that the speculative warm-up stays a few percent.  The batch is the one the host
+ * described in h_ptrs / h_lens; init_variant, flags (SRE_GEOM_CONTINUES / _NO_EOF) and
+ * entry_state are the call's. */
 static int
-scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
+scan_geometry(sre_hip_scanner_t *sc, size_t nstreams, uint32_t init_variant, uint32_t flags, uint32_t entry_state)
 {
     uint64_t total = 0;
     for (size_t i = 0; i < nstreams; i++) total += sc->h_lens[i];
@@ -849,7 +916,6 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
          * with 16 640-byte segments = two rounds of resident workgroups, 1.25 ms with 33 280 =
          * one round, and 1.67 ms with 21 760 = one and a half: a whole number of rounds
          * matters, and one long round beats two short ones; profiles/r02_experiments.txt) */
-        const uint64_t seg_cap = sc->seg_cap_env ? sc->seg_cap_env : 40960;
         /* (sre_scan_auto_segment:) ... and a few workgroup slots are left spare: a grid that
          * needs EVERY slot of its last round waits a whole extra round for the stragglers when
          * anything else (the tail kernels of the previous call) holds a slot at launch — 509
@@ -858,7 +924,7 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
          * 64-byte round): short segments, although half of what such a lane reads is then
          * warm-up (a 1 MiB chunk: 35 us at 1 KiB, 13 us at 256 B).  Rows that are a multiple
          * of 4 KiB apart land on the same HBM channels. */
-        seg = sre_scan_auto_segment(total, resident, seg_cap);
+        seg = sre_scan_auto_segment(total, resident, scan_seg_cap(sc));
     }
     uint64_t nsegs = 0;
     for (size_t i = 0; i < nstreams; i++) {
@@ -867,18 +933,20 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams)
         nsegs += k ? k : 1;             /* an empty stream still takes its EOF step */
     }
     sc->h_seg_first[nstreams] = nsegs;
+    geom_clear(sc);
     sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
     sc->geom.lens = sc->d_lens;
     sc->geom.seg_first = sc->d_seg_first;
     sc->geom.nstreams = (uint32_t) nstreams;
     sc->geom.seg_bytes = (uint32_t) seg;
     sc->geom.nsegs = nsegs;
+    sc->geom.init_variant = init_variant;
+    sc->geom.entry_state = entry_state;
     /* one stream: described in the kernel arguments, nothing to upload (table-driven
      * scanner; the NFA tier's window kernel reads the arrays) */
     sc->geom.one_ptr = static_cast<const uint8_t *>(sc->h_ptrs[0]);
     sc->geom.one_len = sc->h_lens[0];
-    sc->geom_one = (nstreams == 1 && sc->engine == SRE_HIP_ENGINE_SCAN) ? SRE_GEOM_ONE : 0u;
-    sc->geom.flags = (sc->geom.flags & ~SRE_GEOM_ONE) | sc->geom_one;
+    sc->geom.flags = flags | ((nstreams == 1 && sc->engine == SRE_HIP_ENGINE_SCAN) ? SRE_GEOM_ONE : 0u);
 
     if (sc->engine == SRE_HIP_ENGINE_NFA) return nfa_buffers(sc, nsegs);
     return scan_buffers(sc, nstreams, seg, nsegs);
@@ -922,21 +990,21 @@ hip_failed:
 }
 
 /* Pike: the exact VM over the window of every stream that is verified and holds an event (d_lo: only
- * the streams it lists) */
+ * the streams it lists; d_creq: the count requests of a find-all round, else NULL) */
 static int
-nfa_windows(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
+nfa_windows(sre_hip_scanner_t *sc, const int64_t *d_lo, const sre_nfa_count_req_t *d_creq, hipStream_t stream)
 {
     const uint32_t n = sc->geom.nstreams;
     if (sc->d_pwave) {
         SRE_HIP_TRY(sre_launch_pike_window_wave(sc->d_pwave, sc->h_pwave, sc->d_ptrs, sc->d_lens, n, sc->d_records,
                                                 sc->ovec_slots, reinterpret_cast<sre_nfa_window_t *>(sc->d_nstatus), d_lo,
-                                                sc->geom.sflags ? sc->d_creq : NULL, stream));
+                                                d_creq, stream));
     } else {
         /* (the window kernel zero-fills the context it uses) */
         SRE_HIP_TRY(sre_launch_pike_window(sc->dp->d_blob, sc->dp->blob_bytes, sc->d_ptrs, sc->d_lens, n, sc->d_ctx, sc->ctx_stride,
                                            sc->d_records, sc->ovec_slots,
                                            reinterpret_cast<sre_nfa_window_t *>(sc->d_nstatus), d_lo,
-                                           sc->geom.sflags ? sc->d_creq : NULL, stream));
+                                           d_creq, stream));
     }
     return 0;
 hip_failed:
@@ -946,7 +1014,7 @@ hip_failed:
 /* chain check of the set pass and, for Pike, the exact VM over the window of every
  * stream that is verified and holds an event (d_lo: the streams of this fix-up round) */
 static int
-nfa_finish(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
+nfa_finish(sre_hip_scanner_t *sc, const int64_t *d_lo, const sre_nfa_count_req_t *d_creq, hipStream_t stream)
 {
     /* (the kernels know two modes: find-all counting is a loop of first-match searches) */
     const int kmode = sc->mode == SRE_HIP_THOMPSON ? SRE_HIP_THOMPSON : SRE_HIP_PIKE_FIRST;
@@ -957,7 +1025,7 @@ nfa_finish(sre_hip_scanner_t *sc, const int64_t *d_lo, hipStream_t stream)
         SRE_HIP_TRY(sre_launch_nfa_verify(kmode, sc->geom, sc->d_nsum, sc->d_nacc, sc->d_nstatus,
                                           sc->d_belief, sc->d_bvalid, sc->d_records, sc->ovec_slots, d_lo, stream));
     }
-    if (sc->mode != SRE_HIP_THOMPSON) return nfa_windows(sc, d_lo, stream);
+    if (sc->mode != SRE_HIP_THOMPSON) return nfa_windows(sc, d_lo, d_creq, stream);
     return 0;
 hip_failed:
     return -1;
@@ -972,18 +1040,18 @@ count_horizon(uint64_t dflt)
 }
 
 /* NFA tier: one pass over the batch in h_ptrs / h_lens (geometry, set kernel, chain check, exact
- * windows), queued; with_copy: the records and status words travel to the host behind it */
+ * windows), queued; the caller queues the copy of the records and status words behind it.  A find-all
+ * round hands in its per-stream flags and count requests (d_sflags / d_creq, else NULL) */
 static int
-nfa_enqueue_pass(sre_hip_scanner_t *sc, size_t nstreams, hipStream_t stream, bool with_copy)
+nfa_enqueue_pass(sre_hip_scanner_t *sc, size_t nstreams, uint32_t init_variant, const uint8_t *d_sflags,
+                 const sre_nfa_count_req_t *d_creq, hipStream_t stream)
 {
-    if (scan_geometry(sc, nstreams) != 0) return -1;
+    if (scan_geometry(sc, nstreams, init_variant, 0, 0) != 0) return -1;
+    sc->geom.sflags = d_sflags;
     /* (a round of a find-all count is a sub-batch: the blocks keep the call's layout) */
     SRE_HIP_TRY(hipMemcpyAsync(sc->d_in, sc->h_in, (3 * sc->layout_n + 1) * sizeof(uint64_t),
                                hipMemcpyHostToDevice, stream));
-    if (sc->ev0 == NULL) {
-        SRE_HIP_TRY(hipEventCreate(&sc->ev0));
-        SRE_HIP_TRY(hipEventCreate(&sc->ev1));
-    }
+    if (scan_events(sc) != 0) return -1;
     {
         /* set pass, chain check, and (Pike) the exact VM over each stream's window */
         const bool timed = !sc->ev_valid;       /* find-all: the first round's scan is the one reported */
@@ -996,9 +1064,7 @@ nfa_enqueue_pass(sre_hip_scanner_t *sc, size_t nstreams, hipStream_t stream, boo
         SRE_HIP_TRY(hipStreamWaitEvent(sc->tail_stream, sc->ev1, 0));
         stream = sc->tail_stream;
     }
-    if (nfa_finish(sc, NULL, stream) != 0) return -1;
-    if (with_copy) return 0;        /* the caller queues the copy */
-    return 0;
+    return nfa_finish(sc, NULL, d_creq, stream);
 hip_failed:
     return -1;
 }
@@ -1006,7 +1072,7 @@ hip_failed:
 /* NFA tier: one fix-up round over the streams listed in d_lo (already on the device): past the
  * speculative rounds every remaining lane's exact entry set first, then the set pass and the chain check */
 static int
-nfa_fixup_round(sre_hip_scanner_t *sc, hipStream_t stream)
+nfa_fixup_round(sre_hip_scanner_t *sc, const sre_nfa_count_req_t *d_creq, hipStream_t stream)
 {
     if (++sc->fixup_rounds > 1000000) {
         fprintf(stderr, "[sregex-hip] NFA scanner fix-up did not converge\n");
@@ -1052,7 +1118,7 @@ nfa_fixup_round(sre_hip_scanner_t *sc, hipStream_t stream)
         }
     }
     SRE_HIP_TRY(nfa_launch_scan(sc, sc->d_lo, sc->d_belief, sc->d_bvalid, stream));
-    return nfa_finish(sc, sc->d_lo, stream);
+    return nfa_finish(sc, sc->d_lo, d_creq, stream);
 hip_failed:
     return -1;
 }
@@ -1062,7 +1128,7 @@ hip_failed:
  * towards the truth, so corrections travel many segments per round) — until every stream's
  * verified prefix reaches its event or its end.  h_nstatus holds the status of the pass before. */
 static int
-nfa_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool *psettled)
+nfa_settle(sre_hip_scanner_t *sc, size_t n, const sre_nfa_count_req_t *d_creq, hipStream_t stream, bool *psettled)
 {
     for (bool first = true;; first = false) {
         if (!first) {
@@ -1082,7 +1148,26 @@ nfa_settle(sre_hip_scanner_t *sc, size_t n, hipStream_t stream, bool *psettled)
         if (pending == 0) break;
         *psettled = false;
         SRE_HIP_TRY(hipMemcpyAsync(sc->d_lo, sc->h_lo, n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-        if (nfa_fixup_round(sc, stream) != 0) return -1;
+        if (nfa_fixup_round(sc, d_creq, stream) != 0) return -1;
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* NFA tier, batches that settle on the device (line mode, stream sets): fix-up rounds over the n streams
+ * until every one is verified; the work list d_lo and its length are made on the device, the host reads
+ * one word per round */
+static int
+nfa_settle_device(sre_hip_scanner_t *sc, size_t n, hipStream_t stream)
+{
+    for (;;) {
+        SRE_HIP_TRY(sre_launch_streams_nfa_lo(sc->d_nstatus, (uint32_t) n, sc->d_lo, &sc->d_linfo->pending, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                   stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        if (sc->h_linfo->pending == 0) break;
+        if (nfa_fixup_round(sc, NULL, stream) != 0) return -1;
     }
     return 0;
 hip_failed:
@@ -1124,7 +1209,7 @@ nfa_count_rounds(sre_hip_scanner_t *sc, sre_int_t *results)
         SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_creq), n * sizeof(sre_nfa_count_req_t), 0));
         sc->cnt_cap = n;
     }
-    sc->tail_stream_set = false;            /* every round is read back: one stream */
+    sc->tail_stream_set = false;            /* every round is read back: one stream; restored on every way out */
     for (;;) {
         c.active.clear();
         for (size_t i = 0; i < n; i++) {
@@ -1135,7 +1220,7 @@ nfa_count_rounds(sre_hip_scanner_t *sc, sre_int_t *results)
         }
         if (c.active.empty()) break;
         const size_t na = c.active.size();
-        if (++sc->count_rounds > 100000000) return -1;
+        if (++sc->count_rounds > 100000000) goto hip_failed;
         for (size_t j = 0; j < na; j++) {
             NfaCountStream &t = c.st[c.active[j]];
             const uint64_t  left = t.n - t.q, len = left < t.horizon ? left : t.horizon;
@@ -1152,15 +1237,13 @@ nfa_count_rounds(sre_hip_scanner_t *sc, sre_int_t *results)
         }
         SRE_HIP_TRY(hipMemcpyAsync(sc->d_sflags, sc->h_sflags, na, hipMemcpyHostToDevice, stream));
         SRE_HIP_TRY(hipMemcpyAsync(sc->d_creq, sc->h_creq, na * sizeof(sre_nfa_count_req_t), hipMemcpyHostToDevice, stream));
-        sc->geom.sflags = sc->d_sflags;
-        sc->geom.flags = 0;
-        if (nfa_enqueue_pass(sc, na, stream, false) != 0) goto hip_failed;
+        if (nfa_enqueue_pass(sc, na, 0, sc->d_sflags, sc->d_creq, stream) != 0) goto hip_failed;
         SRE_HIP_TRY(hipMemcpyAsync(sc->h_out, sc->d_out, record_bytes(sc, sc->layout_n) + sc->layout_n * sizeof(sre_stream_status_t),
                                    hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
         {
             bool settled = true;
-            if (nfa_settle(sc, na, stream, &settled) != 0) goto hip_failed;
+            if (nfa_settle(sc, na, sc->d_creq, stream, &settled) != 0) goto hip_failed;
             if (!settled) {
                 SRE_HIP_TRY(hipMemcpyAsync(sc->h_out, sc->d_out, record_bytes(sc, sc->layout_n) + sc->layout_n * sizeof(sre_stream_status_t),
                                            hipMemcpyDeviceToHost, stream));
@@ -1208,7 +1291,6 @@ nfa_count_rounds(sre_hip_scanner_t *sc, sre_int_t *results)
             }
         }
     }
-    sc->geom.sflags = NULL;
     sc->tail_stream_set = tail_set;
     for (size_t i = 0; i < n; i++) {
         const NfaCountStream &t = c.st[i];
@@ -1225,7 +1307,6 @@ nfa_count_rounds(sre_hip_scanner_t *sc, sre_int_t *results)
     }
     return 0;
 hip_failed:
-    sc->geom.sflags = NULL;
     sc->tail_stream_set = tail_set;
     return -1;
 }
@@ -1240,15 +1321,9 @@ extern "C" SRE_API int
 sre_hip_scan_enqueue(sre_hip_scanner_t *sc, const void *const *d_streams, const size_t *lens,
     size_t nstreams, void *hip_stream)
 {
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    sc->last_lines = false;
-    sc->fixup_rounds = 0;
-    sc->exact_passes = 0;
-    sc->lineage_passes = 0;
-    sc->ev_valid = 0;
-    sc->geom.init_variant = sc->next_init_variant;
-    sc->geom.flags = 0;
-    sc->geom.entry_state = 0;
+    hipStream_t    stream = static_cast<hipStream_t>(hip_stream);
+    const uint32_t init_variant = sc->next_init_variant;
+    call_begin(sc);
     sc->next_init_variant = 0;
     if (nstreams == 0) {
         sc->last_n = 0;
@@ -1285,7 +1360,7 @@ sre_hip_scan_enqueue(sre_hip_scanner_t *sc, const void *const *d_streams, const 
             t.n = lens[i];
             t.cur = t.q = 0;
             t.horizon = count_horizon(8u << 20);
-            t.var_cur = t.var_q = sc->geom.init_variant;
+            t.var_cur = t.var_q = init_variant;
             t.mode_q = 0;
             t.count = 0;
             t.done = t.error = false;
@@ -1295,11 +1370,12 @@ sre_hip_scan_enqueue(sre_hip_scanner_t *sc, const void *const *d_streams, const 
         sc->last_stream = stream;
         return 0;
     } else if (sc->engine == SRE_HIP_ENGINE_NFA) {
-        if (nfa_enqueue_pass(sc, nstreams, stream, true) != 0) return -1;
+        if (nfa_enqueue_pass(sc, nstreams, init_variant, NULL, NULL, stream) != 0) return -1;
         if (sc->tail_stream_set && sc->tail_stream != stream) stream = sc->tail_stream;
     } else {
-        if (scan_geometry(sc, nstreams) != 0) return -1;
-        if (!sc->geom_one) {
+        if (scan_geometry(sc, nstreams, init_variant, 0, 0) != 0) return -1;
+        const bool one = (sc->geom.flags & SRE_GEOM_ONE) != 0;
+        if (!one) {
             static const bool dma = getenv("SRE_HIP_DMA_UPLOAD") != NULL;      /* experiment knob: the old way */
             if (dma) {
                 SRE_HIP_TRY(hipMemcpyAsync(sc->d_in, sc->h_in, (3 * nstreams + 1) * sizeof(uint64_t),
@@ -1310,10 +1386,7 @@ sre_hip_scan_enqueue(sre_hip_scanner_t *sc, const void *const *d_streams, const 
         }
         /* speculative pass, chain check, captures — all queued; results() only
          * has to look at the status words */
-        if (sc->ev0 == NULL) {
-            SRE_HIP_TRY(hipEventCreate(&sc->ev0));
-            SRE_HIP_TRY(hipEventCreate(&sc->ev1));
-        }
+        if (scan_events(sc) != 0) return -1;
         SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
         SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));
         SRE_HIP_TRY(hipEventRecord(sc->ev1, stream));
@@ -1326,7 +1399,7 @@ sre_hip_scan_enqueue(sre_hip_scanner_t *sc, const void *const *d_streams, const 
         }
         {
             /* one small buffer: chain check and captures in one workgroup */
-            const int fused = sc->geom_one && sc->geom.nsegs <= SRE_VERIFY_ONE_SEGS && sc->mode != SRE_HIP_PIKE_COUNT;
+            const int fused = one && sc->geom.nsegs <= SRE_VERIFY_ONE_SEGS && sc->mode != SRE_HIP_PIKE_COUNT;
             if (!fused) SRE_HIP_TRY(sre_launch_verify(sc->tab->h, sc->geom, sc->d_sum, sc->d_acc, sc->d_status, stream));
             SRE_HIP_TRY(sre_launch_captures(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status,
                                             sc->d_scratch, sc->d_records, sc->ovec_slots,
@@ -1476,7 +1549,7 @@ sre_hip_scan_results(sre_hip_scanner_t *sc, sre_int_t *results)
     if (sc->engine == SRE_HIP_ENGINE_NFA && sc->cnt != NULL) return nfa_count_rounds(sc, results);
     /* everything enqueue() queued for this call, result copies included */
     SRE_HIP_TRY(hipEventSynchronize(sc->ev_done));
-    if (sc->engine == SRE_HIP_ENGINE_NFA && nfa_settle(sc, n, stream, &settled) != 0) return -1;
+    if (sc->engine == SRE_HIP_ENGINE_NFA && nfa_settle(sc, n, NULL, stream, &settled) != 0) return -1;
     if (sc->engine == SRE_HIP_ENGINE_SCAN) {
         if (scan_settle(sc, n, stream, true, &settled) != 0) return -1;
         /* a match whose lineage outran the plain backward walk: build the
@@ -1627,78 +1700,52 @@ sink_select(sre_hip_scanner_t *sc, const LinesSink *sink, size_t slots, uint64_t
                                     stream);
 }
 
-/* table-driven scanner: every batch on the device; the host reads a few words per batch */
+/* what a line-mode call sums over its batches (lines_call publishes it) */
+struct LinesTotals {
+    int    fixups, exact, lineage;
+    double kms;         /* the scan kernels, -1 unknown */
+    size_t nshort;      /* lines the short-line kernel took */
+};
+
+/* the device routes of a line-mode call begin: room for the rows the call may report, none reported yet,
+ * the events around the scan kernel */
 static int
-lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
-                  uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms,
-                  const LinesSink *sink)
+lines_device_begin(sre_hip_scanner_t *sc, uint64_t rcap, size_t width, hipStream_t stream)
 {
-    const size_t   slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
-    const uint64_t bmax = lines_batch_limit();
-    const uint64_t rcap = cap < n ? cap : n;
-    const uint64_t seg_fixed = scan_seg_knobs(sc);
-    const uint64_t resident = scan_resident(sc);
-    const uint64_t seg_cap = sc->seg_cap_env ? sc->seg_cap_env : 40960;
     if (rcap && lines_grow(&sc->d_rows, &sc->rows_cap, rcap * width * sizeof(int64_t)) != 0) return -1;
     SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->reported, 0, sizeof(uint64_t), stream));
-    if (sc->ev0 == NULL) {
-        SRE_HIP_TRY(hipEventCreate(&sc->ev0));
-        SRE_HIP_TRY(hipEventCreate(&sc->ev1));
+    return scan_events(sc);
+hip_failed:
+    return -1;
+}
+
+/* ... a batch (lines i0 .. d_linfo->i1, at most nmax) ends: its records go through the sink's select pass, or
+ * its reported rows are compacted behind the call's; the batch's diagnostics join the call's */
+static int
+lines_device_batch_end(sre_hip_scanner_t *sc, LinesTotals *tot, const LinesSink *sink, uint64_t nmax, uint64_t i0, int all,
+                       uint64_t rcap, hipStream_t stream)
+{
+    const size_t slots = 2 + (size_t) sc->ovec_slots;
+    if (sink) {
+        SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
+    } else {
+        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
+                                             sc->d_linfo, sc->d_rows, rcap, stream));
     }
-    for (uint64_t i0 = 0; i0 < n;) {
-        const uint64_t nmax = bmax < n - i0 ? bmax : n - i0;
-        if (scanner_reserve(sc, nmax) != 0) return -1;
-        /* how many lines the batch takes, its segment size and the stream arrays, on the device */
-        SRE_HIP_TRY(sre_launch_lines_geometry(d_buf, sc->d_ends, n, i0, nmax, SRE_LINES_WALK_MAX, seg_fixed, resident,
-                                              seg_cap, reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens,
-                                              sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
-        if (scan_buffers(sc, nb, seg, nsegs) != 0) return -1;
-        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
-        sc->geom.lens = sc->d_lens;
-        sc->geom.seg_first = sc->d_seg_first;
-        sc->geom.nstreams = (uint32_t) nb;
-        sc->geom.seg_bytes = (uint32_t) seg;
-        sc->geom.nsegs = nsegs;
-        sc->geom.init_variant = 0;
-        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
-        sc->geom.entry_state = 0;
-        sc->geom.one_ptr = NULL;
-        sc->geom.one_len = 0;
-        sc->geom_one = 0;
-        sc->fixup_rounds = 0;
-        sc->exact_passes = 0;
-        sc->lineage_passes = 0;
-        /* as sre_hip_scan_enqueue queues them */
-        SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
-        SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));
-        SRE_HIP_TRY(hipEventRecord(sc->ev1, stream));
-        SRE_HIP_TRY(sre_launch_verify(sc->tab->h, sc->geom, sc->d_sum, sc->d_acc, sc->d_status, stream));
-        SRE_HIP_TRY(sre_launch_captures(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status,
-                                        sc->d_scratch, sc->d_records, sc->ovec_slots, NULL, NULL, 0, 0, stream));
-        /* ... and settle as sre_hip_scan_results does, from two device counters */
-        if (lines_status_counters(sc, nb, stream) != 0) return -1;
-        if (scan_settle(sc, nb, stream, true, NULL, true) != 0) return -1;
-        if (sc->mode != SRE_HIP_THOMPSON && sc->h_linfo->maps != 0 && scan_lineage_pass(sc, stream) != 0) return -1;
-        if (sink) {
-            SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
-        } else {
-            SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
-                                                 sc->d_linfo, sc->d_rows, rcap, stream));
-        }
-        {
-            float ms = 0.0f;
-            SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
-            *kms += ms;
-        }
-        *fixups += sc->fixup_rounds;
-        *exact += sc->exact_passes;
-        *lineage += sc->lineage_passes;
-        sc->line_batches++;
-        i0 = i1;
-    }
+    tot->fixups += sc->fixup_rounds;
+    tot->exact += sc->exact_passes;
+    tot->lineage += sc->lineage_passes;
+    sc->line_batches++;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* ... and the call ends: how many rows it reported, and the first min(cap, reported) of them (a sink takes no row) */
+static int
+lines_device_end(sre_hip_scanner_t *sc, const LinesSink *sink, uint64_t n, sre_int_t *out, uint64_t rcap, size_t width,
+                 uint64_t *pnrep, hipStream_t stream)
+{
     if (sink) return 0;
     SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->reported, &sc->d_linfo->reported, sizeof(uint64_t), hipMemcpyDeviceToHost,
                                stream));
@@ -1712,6 +1759,54 @@ lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all,
         }
     }
     return 0;
+hip_failed:
+    return -1;
+}
+
+/* table-driven scanner: every batch on the device; the host reads a few words per batch */
+static int
+lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
+                  uint64_t *pnrep, hipStream_t stream, LinesTotals *tot, const LinesSink *sink)
+{
+    const size_t   width = 3 + 2 + (size_t) sc->ovec_slots;
+    const uint64_t bmax = lines_batch_limit();
+    const uint64_t rcap = cap < n ? cap : n;
+    const uint64_t seg_fixed = scan_seg_knobs(sc);
+    const uint64_t resident = scan_resident(sc);
+    if (lines_device_begin(sc, rcap, width, stream) != 0) return -1;
+    for (uint64_t i0 = 0; i0 < n;) {
+        const uint64_t nmax = bmax < n - i0 ? bmax : n - i0;
+        if (scanner_reserve(sc, nmax) != 0) return -1;
+        /* how many lines the batch takes, its segment size and the stream arrays, on the device */
+        SRE_HIP_TRY(sre_launch_lines_geometry(d_buf, sc->d_ends, n, i0, nmax, SRE_LINES_WALK_MAX, seg_fixed, resident,
+                                              scan_seg_cap(sc), reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens,
+                                              sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
+        call_begin(sc);         /* (to the diagnostics a batch is a call: tot sums them) */
+        geom_device(sc, nb, seg, nsegs);
+        if (scan_buffers(sc, nb, seg, nsegs) != 0) return -1;       /* (a small batch: geom.digest) */
+        /* scan, chain check and captures queued as for a batch of streams */
+        SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
+        SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));
+        SRE_HIP_TRY(hipEventRecord(sc->ev1, stream));
+        SRE_HIP_TRY(sre_launch_verify(sc->tab->h, sc->geom, sc->d_sum, sc->d_acc, sc->d_status, stream));
+        SRE_HIP_TRY(sre_launch_captures(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status,
+                                        sc->d_scratch, sc->d_records, sc->ovec_slots, NULL, NULL, 0, 0, stream));
+        /* ... and settled from two device counters */
+        if (lines_status_counters(sc, nb, stream) != 0) return -1;
+        if (scan_settle(sc, nb, stream, true, NULL, true) != 0) return -1;
+        if (sc->mode != SRE_HIP_THOMPSON && sc->h_linfo->maps != 0 && scan_lineage_pass(sc, stream) != 0) return -1;
+        if (lines_device_batch_end(sc, tot, sink, nmax, i0, all, rcap, stream) != 0) return -1;
+        {
+            float ms = 0.0f;
+            SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
+            tot->kms += ms;
+        }
+        i0 = i1;
+    }
+    return lines_device_end(sc, sink, n, out, rcap, width, pnrep, stream);
 hip_failed:
     return -1;
 }
@@ -1737,24 +1832,17 @@ lines_short_max(const sre_hip_scanner_t *sc)
  * the status blocks, in which every short line is done. */
 static int
 lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
-               uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, double *kms, size_t *nshort_all,
-               const LinesSink *sink)
+               uint64_t *pnrep, hipStream_t stream, LinesTotals *tot, const LinesSink *sink)
 {
-    const size_t   slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
+    const size_t   width = 3 + 2 + (size_t) sc->ovec_slots;
     const uint64_t rcap = cap < n ? cap : n;
     const uint64_t lmax = lines_short_max(sc), short_lim = lmax ? lmax + 1 : 0;
     const uint32_t W = nfa_words(sc);
     /* what a segment costs: its summary, belief and validity byte, and the wide kernel's entry and exit sets */
     const uint64_t seg_cost = sizeof(sre_nfa_summary_t) + W * sizeof(uint64_t) + 1 + (sc->wide_kernel ? 2 * W * sizeof(uint64_t) : 0);
     uint64_t       bmax = lines_batch_limit();
-    uint64_t       seg_fixed = scan_seg_knobs(sc);
-    if (seg_fixed == 0) {
-        /* (the set kernels take any multiple of the 64-byte round, as for stream sets) */
-        const char *e = getenv("SRE_HIP_SEG_BYTES");
-        if (e && atoi(e) > 0 && atoi(e) % 64 == 0) seg_fixed = (uint64_t) atoi(e);
-    }
+    const uint64_t seg_fixed = nfa_seg_knobs(sc);
     const uint64_t resident = scan_resident(sc);
-    const uint64_t seg_cap = sc->seg_cap_env ? sc->seg_cap_env : 40960;
     if (sc->mode != SRE_HIP_THOMPSON && sc->d_pwave == NULL && sc->ctx_stride) {
         /* the exact window's contexts, one per line of the batch */
         const uint64_t most = SRE_LINES_NFA_WORK_MAX / sc->ctx_stride;
@@ -1763,12 +1851,7 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
     sre_lnfa_t ltab;
     memset(&ltab, 0, sizeof(ltab));
     if (short_lim) ltab = sc->use_sa ? sre_lines_nfa_tables_sa(&sc->satab) : sre_lines_nfa_tables_plain(&sc->ntab);
-    if (rcap && lines_grow(&sc->d_rows, &sc->rows_cap, rcap * width * sizeof(int64_t)) != 0) return -1;
-    SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->reported, 0, sizeof(uint64_t), stream));
-    if (sc->ev0 == NULL) {
-        SRE_HIP_TRY(hipEventCreate(&sc->ev0));
-        SRE_HIP_TRY(hipEventCreate(&sc->ev1));
-    }
+    if (lines_device_begin(sc, rcap, width, stream) != 0) return -1;
     if (sc->ev_l0 == NULL) {
         SRE_HIP_TRY(hipEventCreate(&sc->ev_l0));
         SRE_HIP_TRY(hipEventCreate(&sc->ev_l1));
@@ -1777,37 +1860,21 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
         const uint64_t nmax = bmax < n - i0 ? bmax : n - i0;
         if (scanner_reserve(sc, nmax) != 0) return -1;
         SRE_HIP_TRY(sre_launch_lines_geometry_nfa(d_buf, sc->d_ends, n, i0, nmax, short_lim, SRE_LINES_NFA_WORK_MAX, seg_cost,
-                                                  seg_fixed, resident, seg_cap, reinterpret_cast<const uint8_t **>(sc->d_ptrs),
+                                                  seg_fixed, resident, scan_seg_cap(sc), reinterpret_cast<const uint8_t **>(sc->d_ptrs),
                                                   sc->d_lens, sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
         SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->nshort, &sc->d_linfo->nshort, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
         const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
         const uint64_t nshort = sc->h_linfo->nshort;
-        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
-        sc->geom.lens = sc->d_lens;
-        sc->geom.seg_first = sc->d_seg_first;
-        sc->geom.nstreams = (uint32_t) nb;
-        sc->geom.seg_bytes = (uint32_t) seg;
-        sc->geom.nsegs = nsegs;
-        sc->geom.init_variant = 0;
-        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
-        sc->geom.entry_state = 0;
-        sc->geom.one_ptr = NULL;
-        sc->geom.one_len = 0;
-        sc->geom.digest = NULL;
-        sc->geom.sentry = NULL;
-        sc->geom.sflags = NULL;
-        sc->geom_one = 0;
-        sc->d_eset = NULL;
-        sc->fixup_rounds = 0;
-        sc->exact_passes = 0;
+        call_begin(sc);         /* (to the diagnostics a batch is a call: tot sums them) */
+        geom_device(sc, nb, seg, nsegs);
         if (nsegs) {
             if (nfa_buffers(sc, nsegs) != 0) return -1;
             SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
             SRE_HIP_TRY(nfa_launch_scan(sc, NULL, NULL, NULL, stream));
             SRE_HIP_TRY(hipEventRecord(sc->ev1, stream));
-            if (nfa_finish(sc, NULL, stream) != 0) return -1;
+            if (nfa_finish(sc, NULL, NULL, stream) != 0) return -1;
         }
         if (nshort) {
             SRE_HIP_TRY(hipEventRecord(sc->ev_l0, stream));
@@ -1815,57 +1882,27 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
                                              sc->mode == SRE_HIP_THOMPSON, sc->d_nstatus, sc->d_records, sc->ovec_slots, sc->d_lo,
                                              stream));
             SRE_HIP_TRY(hipEventRecord(sc->ev_l1, stream));
-            if (sc->mode != SRE_HIP_THOMPSON && nfa_windows(sc, sc->d_lo, stream) != 0) return -1;
+            if (sc->mode != SRE_HIP_THOMPSON && nfa_windows(sc, sc->d_lo, NULL, stream) != 0) return -1;
         }
-        if (nsegs) {
-            /* fix-up rounds over the long lines that are not verified, as streams_feed_nfa runs them: the work
-             * list and its length are made on the device, the host reads one word per round */
-            for (;;) {
-                SRE_HIP_TRY(sre_launch_streams_nfa_lo(sc->d_nstatus, (uint32_t) nb, sc->d_lo, &sc->d_linfo->pending, stream));
-                SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, sizeof(uint64_t), hipMemcpyDeviceToHost,
-                                           stream));
-                SRE_HIP_TRY(hipStreamSynchronize(stream));
-                if (sc->h_linfo->pending == 0) break;
-                if (nfa_fixup_round(sc, stream) != 0) return -1;
-            }
-        }
-        if (sink) {
-            SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
-        } else {
-            SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
-                                                 sc->d_linfo, sc->d_rows, rcap, stream));
-        }
+        /* fix-up rounds over the long lines that are not verified */
+        if (nsegs && nfa_settle_device(sc, nb, stream) != 0) return -1;
+        if (lines_device_batch_end(sc, tot, sink, nmax, i0, all, rcap, stream) != 0) return -1;
         {
             float ms = 0.0f;
             if (nsegs) {
                 SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev0, sc->ev1));
-                *kms += ms;
+                tot->kms += ms;
             }
             if (nshort) {
                 SRE_HIP_TRY(hipEventSynchronize(sc->ev_l1));
                 SRE_HIP_TRY(hipEventElapsedTime(&ms, sc->ev_l0, sc->ev_l1));
-                *kms += ms;
+                tot->kms += ms;
             }
         }
-        *fixups += sc->fixup_rounds;
-        *exact += sc->exact_passes;
-        *nshort_all += (size_t) nshort;
-        sc->line_batches++;
+        tot->nshort += (size_t) nshort;
         i0 = i1;
     }
-    if (sink) return 0;
-    SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->reported, &sc->d_linfo->reported, sizeof(uint64_t), hipMemcpyDeviceToHost,
-                               stream));
-    SRE_HIP_TRY(hipStreamSynchronize(stream));
-    *pnrep = n ? sc->h_linfo->reported : 0;
-    {
-        const uint64_t take = *pnrep < rcap ? *pnrep : rcap;
-        if (take) {
-            SRE_HIP_TRY(hipMemcpyAsync(out, sc->d_rows, take * width * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-        }
-    }
-    return 0;
+    return lines_device_end(sc, sink, n, out, rcap, width, pnrep, stream);
 hip_failed:
     return -1;
 }
@@ -1875,8 +1912,7 @@ hip_failed:
  * sre_hip_scan_results; the rows are compacted on the host */
 static int
 lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sre_int_t *out, size_t cap,
-                uint64_t *pnrep, hipStream_t stream, int *fixups, int *exact, int *lineage, double *kms,
-                const LinesSink *sink)
+                uint64_t *pnrep, hipStream_t stream, LinesTotals *tot, const LinesSink *sink)
 {
     const size_t              slots = 2 + (size_t) sc->ovec_slots, width = 3 + slots;
     const uint64_t            bmax = lines_batch_limit();
@@ -1907,11 +1943,11 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
         }
         recs.resize(nb * slots);
         if (sre_hip_scan_batch(sc, ptrs.data(), lens.data(), nb, recs.data(), stream) != 0) return -1;
-        *fixups += sc->fixup_rounds;
-        *exact += sc->exact_passes;
-        *lineage += sc->lineage_passes;
+        tot->fixups += sc->fixup_rounds;
+        tot->exact += sc->exact_passes;
+        tot->lineage += sc->lineage_passes;
         const double ms = sre_hip_scanner_last_kernel_ms(sc);
-        *kms = (ms < 0 || *kms < 0) ? -1.0 : *kms + ms;
+        tot->kms = (ms < 0 || tot->kms < 0) ? -1.0 : tot->kms + ms;
         if (sink && sink->pieces) {
             /* what sre_k_subst_select writes, from the records the host holds */
             const sre_subst_pieces_t *pc = sink->pieces;
@@ -2002,9 +2038,8 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
            LinesSink *sink, uint64_t *pn, uint64_t *pnrep, hipStream_t stream)
 {
     uint64_t    n = 0, nrep = 0;
-    int         fixups = 0, exact = 0, lineage = 0, rc = -1;
-    double      kms = sc->engine == SRE_HIP_ENGINE_VM ? -1.0 : 0.0;
-    size_t      nshort = 0;
+    int         rc = -1;
+    LinesTotals tot = {0, 0, 0, sc->engine == SRE_HIP_ENGINE_VM ? -1.0 : 0.0, 0};
     /* 0: per-line host work, 1: the table-driven scanner's device route, 2: the NFA tier's */
     int         route = sc->engine == SRE_HIP_ENGINE_SCAN ? 1 : 0;
     if (sc->engine == SRE_HIP_ENGINE_NFA && sc->cnt == NULL) {
@@ -2024,21 +2059,21 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
                 sink->d_start = sc->d_fstart;
             }
         }
-        rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms, sink)
-             : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &kms, &nshort, sink)
-                          : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &fixups, &exact, &lineage, &kms, sink);
+        rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink)
+             : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink)
+                          : lines_scan_host(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink);
     }
 hip_failed:
     /* this call replaces the scanner's last one; its diagnostics describe the whole call */
     sc->last_lines = true;
     sc->last_n = 0;
     sc->ev_valid = 0;
-    sc->fixup_rounds = fixups;
-    sc->exact_passes = exact;
-    sc->lineage_passes = lineage;
-    sc->lines_kernel_ms = rc == 0 ? kms : -1.0;
+    sc->fixup_rounds = tot.fixups;
+    sc->exact_passes = tot.exact;
+    sc->lineage_passes = tot.lineage;
+    sc->lines_kernel_ms = rc == 0 ? tot.kms : -1.0;
     sc->lines_device = rc == 0 && route != 0;
-    sc->short_lines = rc == 0 ? nshort : 0;
+    sc->short_lines = rc == 0 ? tot.nshort : 0;
     if (rc != 0) return -1;
     *pn = n;
     *pnrep = nrep;
@@ -2449,18 +2484,15 @@ sre_hip_scan_stream_chunk(sre_hip_scanner_t *sc, const void *d_buf, size_t len, 
         ~Midway() { run(); }
     } mid{midway, midway_arg};
     if (sc->engine != SRE_HIP_ENGINE_SCAN || sc->mode == SRE_HIP_PIKE_COUNT) return -1;
-    sc->last_lines = false;
-    sc->fixup_rounds = 0;
-    sc->exact_passes = 0;
-    sc->lineage_passes = 0;
-    sc->ev_valid = 0;
+    call_begin(sc);
     if (scanner_reserve(sc, 1) != 0) return -1;
     sc->h_ptrs[0] = d_buf;
     sc->h_lens[0] = len;
-    sc->geom.init_variant = (uint32_t) init_variant;
-    if (scan_geometry(sc, 1) != 0) return -1;
-    sc->geom.flags = (continues ? SRE_GEOM_CONTINUES : 0u) | (eof ? 0u : SRE_GEOM_NO_EOF) | sc->geom_one;
-    sc->geom.entry_state = entry_state;
+    if (scan_geometry(sc, 1, (uint32_t) init_variant, (continues ? SRE_GEOM_CONTINUES : 0u) | (eof ? 0u : SRE_GEOM_NO_EOF),
+                      entry_state) != 0)
+    {
+        return -1;
+    }
     /* two launches per chunk: the scan, and the chain check + tail in one workgroup; should
      * the speculative entry states of the chunk's lanes have been wrong (rare), the tail
      * says so and the rounds are run first */
@@ -2492,16 +2524,14 @@ sre_hip_scan_stream_chunk(sre_hip_scanner_t *sc, const void *d_buf, size_t len, 
         SRE_HIP_TRY(hipMemcpyAsync(sc->h_status, sc->d_status, sizeof(sre_stream_status_t),
                                    hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
-        if (scan_settle(sc, 1, stream, false, NULL) != 0) goto hip_failed;
+        if (scan_settle(sc, 1, stream, false, NULL) != 0) return -1;
         SRE_HIP_TRY(sre_launch_stream_tail(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status,
                                            sc->d_scratch, d_ctx, d_res, base, eof, ovec_slots, 0, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
-    sc->geom.flags = 0;
     sc->last_n = 0;
     return 0;
 hip_failed:
-    sc->geom.flags = 0;
     return -1;
 }
 
@@ -2738,6 +2768,13 @@ hip_failed:
     return -1;
 }
 
+/* workgroups of the table-driven set's tail kernel: one per active stream, at most SRE_STREAMS_TAIL_GRID */
+static uint32_t
+streams_tail_grid(uint64_t nactive)
+{
+    return (uint32_t) (nactive < SRE_STREAMS_TAIL_GRID ? nactive : SRE_STREAMS_TAIL_GRID);
+}
+
 /* The call on the NFA tier: prologue (geometry, entry sets, the records of streams that need no byte),
  * set pass + chain check, tail; fix-up rounds — the exact-entry fallback among them — run from device
  * counters: per round the host reads one word, never the streams' status blocks. */
@@ -2751,18 +2788,12 @@ streams_feed_nfa(sre_hip_streams_t *ss, sre_int_t *results, hipStream_t stream)
     int64_t            *d_recs = reinterpret_cast<int64_t *>(ss->d_out + sizeof(sre_streams_info_t));
     const size_t        out_bytes = sizeof(sre_streams_info_t) + n * ss->L.rec_slots * sizeof(int64_t);
     {
-        uint64_t seg_fixed = scan_seg_knobs(sc);
-        if (seg_fixed == 0) {
-            /* (the set kernels take any multiple of the 64-byte round: tests cut streams into segments
-             * that are shorter than the warm-up) */
-            const char *e = getenv("SRE_HIP_SEG_BYTES");
-            if (e && atoi(e) > 0 && atoi(e) % 64 == 0) seg_fixed = (uint64_t) atoi(e);
-        }
+        const uint64_t seg_fixed = nfa_seg_knobs(sc);
         const uint64_t resident = scan_resident(sc);
         SRE_HIP_TRY(sre_launch_upload_words(reinterpret_cast<const uint64_t *>(ss->h_feed),
                                             reinterpret_cast<uint64_t *>(ss->d_feed), (uint32_t) (3 * n), stream));
         SRE_HIP_TRY(sre_launch_streams_nfa_prologue(ss->d_feed, (uint32_t) n, ss->d_rows, ss->W, ss->init0, ss->L.rec_slots, seg_fixed,
-                                                    resident, sc->seg_cap_env ? sc->seg_cap_env : 40960,
+                                                    resident, scan_seg_cap(sc),
                                                     reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens, sc->d_seg_first,
                                                     ss->d_sflags, ss->d_eset, d_recs, d_info, stream));
         /* the host sizes the call's buffers and grids from two of its words */
@@ -2772,24 +2803,12 @@ streams_feed_nfa(sre_hip_streams_t *ss, sre_int_t *results, hipStream_t stream)
     }
     if (h_info->nsegs != 0) {
         if (nfa_buffers(sc, h_info->nsegs) != 0) return -1;
-        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
-        sc->geom.lens = sc->d_lens;
-        sc->geom.seg_first = sc->d_seg_first;
-        sc->geom.nstreams = (uint32_t) n;
-        sc->geom.seg_bytes = (uint32_t) h_info->seg;
-        sc->geom.nsegs = h_info->nsegs;
-        sc->geom.init_variant = 0;
-        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
-        sc->geom.entry_state = 0;
-        sc->geom.one_ptr = NULL;
-        sc->geom.one_len = 0;
-        sc->geom.digest = NULL;
-        sc->geom.sentry = NULL;
+        geom_device(sc, n, h_info->seg, h_info->nsegs);
+        /* per stream: whether more chunks follow, and the set it enters with */
         sc->geom.sflags = ss->d_sflags;
-        sc->geom_one = 0;
         sc->d_eset = ss->d_eset;
         SRE_HIP_TRY(nfa_launch_scan(sc, NULL, NULL, NULL, stream));
-        if (nfa_finish(sc, NULL, stream) != 0) goto hip_failed;
+        if (nfa_finish(sc, NULL, NULL, stream) != 0) return -1;
         SRE_HIP_TRY(sre_launch_streams_nfa_tail(ss->d_feed, (uint32_t) n, ss->d_rows, ss->W, sc->d_seg_first, sc->d_nstatus, sc->d_nsum,
                                                 sc->wide_kernel ? sc->d_wsets : NULL, ss->L.rec_slots, d_recs, d_info, 0, stream));
         ss->launches += 1 + 3 + 1;
@@ -2799,14 +2818,8 @@ streams_feed_nfa(sre_hip_streams_t *ss, sre_int_t *results, hipStream_t stream)
     ss->launches += 1;
     if (h_info->unsettled != 0) {
         /* speculative entry sets of some stream's lanes were wrong: fix-up rounds over the streams that
-         * are not verified, their work list and its length made on the device */
-        for (;;) {
-            SRE_HIP_TRY(sre_launch_streams_nfa_lo(sc->d_nstatus, (uint32_t) n, sc->d_lo, &sc->d_linfo->pending, stream));
-            SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-            if (sc->h_linfo->pending == 0) break;
-            if (nfa_fixup_round(sc, stream) != 0) goto hip_failed;
-        }
+         * are not verified */
+        if (nfa_settle_device(sc, n, stream) != 0) return -1;
         SRE_HIP_TRY(hipMemsetAsync(&d_info->unsettled, 0, sizeof(uint64_t), stream));
         SRE_HIP_TRY(sre_launch_streams_nfa_tail(ss->d_feed, (uint32_t) n, ss->d_rows, ss->W, sc->d_seg_first, sc->d_nstatus, sc->d_nsum,
                                                 sc->wide_kernel ? sc->d_wsets : NULL, ss->L.rec_slots, d_recs, d_info, 1, stream));
@@ -2817,16 +2830,12 @@ streams_feed_nfa(sre_hip_streams_t *ss, sre_int_t *results, hipStream_t stream)
         ss->launches += 3;
         if (h_info->unsettled != 0) {
             fprintf(stderr, "[sregex-hip] stream set: %llu streams did not settle\n", (unsigned long long) h_info->unsettled);
-            goto hip_failed;
+            return -1;
         }
     }
-    sc->geom.sflags = NULL;
-    sc->d_eset = NULL;
     memcpy(results, ss->h_out + sizeof(sre_streams_info_t), n * ss->L.rec_slots * sizeof(int64_t));
     return 0;
 hip_failed:
-    sc->geom.sflags = NULL;
-    sc->d_eset = NULL;
     return -1;
 }
 
@@ -2848,12 +2857,8 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
     ss->fixups = 0;
     ss->launches = 0;
     ss->exact_passes = 0;
-    sc->last_lines = false;
+    call_begin(sc);
     sc->last_n = 0;
-    sc->fixup_rounds = 0;
-    sc->exact_passes = 0;
-    sc->lineage_passes = 0;
-    sc->ev_valid = 0;
     for (size_t i = 0; i < n; i++) {
         ss->h_feed[i].ptr = (uint64_t) reinterpret_cast<uintptr_t>(d_chunks[i]);
         ss->h_feed[i].len = d_chunks[i] ? lens[i] : 0;
@@ -2867,7 +2872,7 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
         SRE_HIP_TRY(sre_launch_upload_words(reinterpret_cast<const uint64_t *>(ss->h_feed),
                                             reinterpret_cast<uint64_t *>(ss->d_feed), (uint32_t) (3 * n), stream));
         SRE_HIP_TRY(sre_launch_streams_prologue(ss->d_feed, (uint32_t) n, ss->d_rows, ss->L, ss->d_rekind, sc->tab->h.init[0],
-                                                seg_fixed, resident, sc->seg_cap_env ? sc->seg_cap_env : 40960,
+                                                seg_fixed, resident, scan_seg_cap(sc),
                                                 reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens, sc->d_seg_first,
                                                 ss->d_sentry, d_recs, d_info, stream));
         /* the host sizes the call's buffers and grids from two of its words */
@@ -2876,24 +2881,13 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
         ss->launches += 3;
     }
     if (h_info->nsegs != 0) {
-        const uint64_t seg = h_info->seg, nsegs = h_info->nsegs, nact = h_info->nactive;
-        const uint32_t grid = (uint32_t) (nact < SRE_STREAMS_TAIL_GRID ? nact : SRE_STREAMS_TAIL_GRID);
+        const uint64_t seg = h_info->seg, nsegs = h_info->nsegs;
+        const uint32_t grid = streams_tail_grid(h_info->nactive);
         /* (the walker's scratch: one block per workgroup of the tail kernel, not per stream) */
         if (scan_buffers(sc, grid, seg, nsegs) != 0) return -1;
-        sc->geom.streams = reinterpret_cast<const uint8_t *const *>(sc->d_ptrs);
-        sc->geom.lens = sc->d_lens;
-        sc->geom.seg_first = sc->d_seg_first;
-        sc->geom.nstreams = (uint32_t) n;
-        sc->geom.seg_bytes = (uint32_t) seg;
-        sc->geom.nsegs = nsegs;
-        sc->geom.init_variant = 0;
-        sc->geom.flags = 0;             /* never SRE_GEOM_ONE: the arrays live on the device */
-        sc->geom.entry_state = 0;
-        sc->geom.one_ptr = NULL;
-        sc->geom.one_len = 0;
-        sc->geom.digest = NULL;
+        /* (behind scan_buffers: the set's chain check takes no digest) */
+        geom_device(sc, n, seg, nsegs);
         sc->geom.sentry = ss->d_sentry;
-        sc->geom_one = 0;
         SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));
         SRE_HIP_TRY(sre_launch_verify(sc->tab->h, sc->geom, sc->d_sum, sc->d_acc, sc->d_status, stream));
         SRE_HIP_TRY(sre_launch_streams_tail(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status, sc->d_scratch,
@@ -2906,11 +2900,10 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
     if (h_info->unsettled != 0) {
         /* speculative entry states of some stream's lanes were wrong: the fix-up rounds over the
          * streams that are not done, driven from device counters, then their tails */
-        const uint64_t nact = h_info->nactive;
-        const uint32_t grid = (uint32_t) (nact < SRE_STREAMS_TAIL_GRID ? nact : SRE_STREAMS_TAIL_GRID);
+        const uint32_t grid = streams_tail_grid(h_info->nactive);
         sc->h_linfo->pending = h_info->unsettled;
         sc->h_linfo->maps = 0;
-        if (scan_settle(sc, n, stream, false, NULL, true) != 0) goto hip_failed;
+        if (scan_settle(sc, n, stream, false, NULL, true) != 0) return -1;
         SRE_HIP_TRY(hipMemsetAsync(&d_info->unsettled, 0, sizeof(uint64_t), stream));
         SRE_HIP_TRY(sre_launch_streams_tail(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, sc->d_status, sc->d_scratch,
                                             ss->d_rows, ss->L, ss->d_tailres, d_recs, d_info, grid, 1, stream));
@@ -2921,14 +2914,12 @@ sre_hip_streams_feed(sre_hip_streams_t *ss, const void *const *d_chunks, const s
         ss->launches += 3;
         if (h_info->unsettled != 0) {
             fprintf(stderr, "[sregex-hip] stream set: %llu streams did not settle\n", (unsigned long long) h_info->unsettled);
-            goto hip_failed;
+            return -1;
         }
     }
-    sc->geom.sentry = NULL;
     memcpy(results, ss->h_out + sizeof(sre_streams_info_t), n * ss->L.rec_slots * sizeof(int64_t));
     return 0;
 hip_failed:
-    sc->geom.sentry = NULL;
     return -1;
 }
 
