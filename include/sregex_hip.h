@@ -505,6 +505,74 @@ SRE_API int sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, s
     const void *tmpl, size_t tmpl_len, int flags, void *d_out, size_t out_cap,
     sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream);
 
+/* ---- line route: each line grouped by the regex that matched, bucket by bucket in a device buffer ---- */
+
+enum { SRE_HIP_ROUTE_MAX_BUCKETS = 256 };
+
+typedef struct {
+    size_t nlines;      /* lines of the bucket, over the whole buffer */
+    size_t offset;      /* where the bucket starts in d_out when everything fits: the bytes of the buckets in front */
+    size_t bytes;       /* bytes the bucket takes: sum of (len + 1) over its lines */
+} sre_hip_route_bucket_t;
+
+/*
+ * Line route: every line classified by the regex of a multi-regex program that matched it and
+ * written to the bucket of that regex (awk '/a/{print > "a"} /b/{print > "b"}', the `route`
+ * transform of a log pipeline).  The split of d_buf, the matching of every line, the routing to
+ * an engine, the batching and the diagnostics are exactly those of sre_hip_extract_lines on the
+ * same (sc, d_buf, len, delim).  sc must have been created with SRE_HIP_PIKE_FIRST: a line's rc
+ * is then the id of the regex of its FIRST match, Pike's leftmost-then-priority choice when
+ * several regexes match the line.  Thompson and COUNT scanners return -1 with a diagnostic on
+ * stderr.
+ *
+ * The map.  With R the regexes of the program, bucket_of is a HOST array of R + 1 ints: entry r
+ * (0 <= r < R) is the bucket of a line whose first match belongs to regex r, entry R the bucket
+ * of a line without a match.  -1 drops the line; any other value must lie in [0, nbuckets).
+ * bucket_of == NULL is the identity with unmatched lines dropped, and nbuckets must then be R.
+ * 1 <= nbuckets <= SRE_HIP_ROUTE_MAX_BUCKETS; anything else returns -1.  The call takes no
+ * flags, the map says it all: grep is {0, .., 0, -1}, grep -v is {-1, .., -1, 0}, "route plus
+ * rest" is {0, 1, .., R - 1, R}.  A line whose rc is an error is dropped.
+ *
+ * Output.  ONE device buffer, bucket-major: all lines of bucket 0 in line order, then bucket 1,
+ * and so on, each line as its bytes followed by ONE delim byte (a final source line without a
+ * delimiter gets one too), so the output and every bucket's slice of it are well-formed line
+ * buffers.  d_out is a DEVICE pointer at any alignment to out_cap bytes that do not overlap
+ * [d_buf, d_buf + len) (an overlap returns -1).  buckets is an optional HOST array of nbuckets
+ * entries: buckets[b].nlines and .bytes are the totals of bucket b whatever out_cap is, .offset
+ * is where bucket b starts when everything fits.  info->nselected is the routed lines,
+ * info->need_bytes the sum of the buckets' bytes.
+ *
+ * Truncation.  Whole lines only, in output order: info->nwritten is the largest k for which the
+ * first k rows of the bucket-major order take at most out_cap bytes, info->out_bytes that
+ * total.  No byte of d_out at or beyond out_bytes is touched and nothing is written in front of
+ * d_out.  d_out may be NULL when out_cap == 0 (a sizing call).
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten)
+ * rows in output order it receives 5 sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the line in d_out   [4] bucket.
+ * d_index may be NULL when index_cap == 0.  info may be NULL.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  It replaces the scanner's last
+ * call and the diagnostics describe it exactly as for sre_hip_filter_lines.  On the device
+ * routes (the table-driven scanner; first match on the NFA tier, 64-bit and wide forms) the
+ * host reads a fixed number of words per batch, one word and then 4 + 2 * nbuckets words per
+ * call, and uploads the map only when it differs from the last call's: nothing per line
+ * travels to the host.  On the host route (the exact VM, SRE_HIP_LINES_NFA_HOST=1) the host
+ * fills one word per line from the records it holds and uploads them batch by batch.
+ * len == 0 gives all zeros in info and buckets, and success.  Not offered: a separate output
+ * pointer per bucket, context lines, routing by anything but the first match's regex.
+ * Beyond what line mode takes, a scanner keeps of the largest call 8 bytes per line (shared
+ * with sre_hip_filter_lines), 24 bytes per routed line (8 of them shared with
+ * sre_hip_extract_lines), 8 bytes per bucket and 1024 lines, and 4 bytes per regex; all
+ * grow-only device memory, freed with the scanner.  Returns 0 on success, -1 on bad arguments
+ * or failure.
+ */
+SRE_API int sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *bucket_of, size_t nbuckets, void *d_out, size_t out_cap,
+    sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info,
+    sre_hip_route_bucket_t *buckets, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

@@ -30,6 +30,7 @@ HIP_LINES_INVERT = 2
 HIP_EXTRACT_MAX_FIELDS = 32
 HIP_SUBST_MAX_PIECES = 30
 HIP_SUBST_MAX_LITERAL = 4096
+HIP_ROUTE_MAX_BUCKETS = 256
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -91,6 +92,8 @@ API = {
                                                     ctypes.POINTER(_sz)]),
     "sre_hip_substitute_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_char_p, _sz, ctypes.c_int, _vp, _sz, _vp, _sz,
                                                 _vp, _vp]),
+    "sre_hip_route_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, _sz, _vp, _sz, _vp,
+                                           _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -338,6 +341,7 @@ class Scanner:
                                "engine does not take this program)")
         self.slots = self.lib.sre_hip_scanner_result_slots(self.h)
         self.engine = self.lib.sre_hip_scanner_engine(self.h)
+        self.nregexes = prog.nregexes
         self._n = 0
 
     def set_segment_bytes(self, nbytes):
@@ -490,6 +494,33 @@ class Scanner:
             raise RuntimeError("sre_hip_substitute_lines failed")
         return FilterInfo(*info)
 
+    def route_lines(self, ptr, length, out_ptr, out_cap, bucket_of=None, nbuckets=None, delim=0x0A, index_ptr=None,
+                    index_cap=0, hip_stream=None):
+        """sre_hip_route_lines: every line of the device buffer (ptr, length) goes to the bucket of the regex of its
+        first match: bucket_of[r] for regex r, bucket_of[nregexes] for a line without a match, -1 drops the line; None is
+        the identity with unmatched lines dropped (nbuckets then defaults to the program's regexes).  The device buffer
+        (out_ptr, out_cap) receives all lines of bucket 0 in line order, then bucket 1, .., each followed by one
+        delimiter.  index_ptr: an optional device array of index_cap rows [line no, offset in the buffer, length, offset
+        in the output, bucket] in output order.  The scanner's mode must be HIP_PIKE_FIRST.  Returns (FilterInfo(nlines,
+        nselected, need_bytes, nwritten, out_bytes), [RouteBucket(nlines, offset, bytes)] per bucket): the buckets'
+        totals over the whole buffer whatever out_cap is, offset where the bucket starts when everything fits."""
+        arr = None
+        if bucket_of is not None:
+            bucket_of = list(bucket_of)
+            if len(bucket_of) != self.nregexes + 1:
+                raise ValueError("bucket_of needs nregexes + 1 = %d entries" % (self.nregexes + 1))
+            arr = (ctypes.c_int * len(bucket_of))(*bucket_of)
+            if nbuckets is None:
+                nbuckets = max(bucket_of) + 1
+        elif nbuckets is None:
+            nbuckets = self.nregexes
+        info = (_sz * 5)()
+        bk = (_sz * (3 * max(nbuckets, 1)))()
+        if self.lib.sre_hip_route_lines(self.h, ptr, length, delim, arr, nbuckets, out_ptr, out_cap, index_ptr, index_cap, info,
+                                        bk, hip_stream) != 0:
+            raise RuntimeError("sre_hip_route_lines failed")
+        return FilterInfo(*info), [RouteBucket(*bk[3 * b:3 * b + 3]) for b in range(nbuckets)]
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -506,6 +537,7 @@ class Scanner:
 
 
 FilterInfo = collections.namedtuple("FilterInfo", "nlines nselected need_bytes nwritten out_bytes")
+RouteBucket = collections.namedtuple("RouteBucket", "nlines offset bytes")
 ContextInfo = collections.namedtuple("ContextInfo", "nlines nmatched nselected ngroups need_bytes nwritten out_bytes")
 
 

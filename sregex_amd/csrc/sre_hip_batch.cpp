@@ -21,6 +21,7 @@
 #include "sre_pwave.h"
 #include "sre_hip_lines.h"
 #include "sre_lines_gather.h"
+#include "sre_lines_route.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
 #include <stdio.h>
@@ -149,6 +150,18 @@ struct sre_hip_scanner_s {
     uint8_t                  *h_lit;            /* the literals the block holds, so that a repeated template uploads nothing */
     size_t                    lit_len;
     bool                      lit_valid;
+    /* the line route (sre_hip_route_lines): its keys are d_fval's words (one per line), the compact table's starts
+     * d_fstart's (one per selected line), the scans' sums d_fblk's; it adds */
+    uint64_t                 *d_rcnt;           /* per (bucket, workgroup) counts, then first ranks: nbuckets x ceil(lines / 1024) + 1 words */
+    size_t                    rcnt_cap;
+    uint64_t                 *d_rval;           /* the compact table's values, then its offset table: selected lines + 1 words */
+    size_t                    rval_cap;
+    uint64_t                 *d_rmeta;          /* ... and bucket << 56 | line of each entry, for the index */
+    size_t                    rmeta_cap;
+    int32_t                  *d_rmap;           /* the call's map, nregexes + 1 words */
+    int32_t                  *h_rmap;           /* the map the device holds, so that a repeated map uploads nothing */
+    bool                      rmap_valid;
+    uint64_t                 *d_rres, *h_rres;  /* the words the host reads: SRE_LR_RES_WORDS + 2 x SRE_LR_MAX_BUCKETS */
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -213,6 +226,13 @@ scanner_release(void *data)
     if (sc->d_fstart) (void) hipFree(sc->d_fstart);
     if (sc->d_lit) (void) hipFree(sc->d_lit);
     free(sc->h_lit);
+    if (sc->d_rcnt) (void) hipFree(sc->d_rcnt);
+    if (sc->d_rval) (void) hipFree(sc->d_rval);
+    if (sc->d_rmeta) (void) hipFree(sc->d_rmeta);
+    if (sc->d_rmap) (void) hipFree(sc->d_rmap);
+    free(sc->h_rmap);
+    if (sc->d_rres) (void) hipFree(sc->d_rres);
+    if (sc->h_rres) (void) hipHostFree(sc->h_rres);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -1669,6 +1689,10 @@ struct LinesSink {
     /* the line substitute (sre_hip_substitute_lines): with pieces, the select pass is the substitute's over the entries
      * line * (np + 2) + piece, into d_val and d_start as above; mode is 0 or 2 */
     const sre_subst_pieces_t   *pieces;
+    /* the line route (sre_hip_route_lines): with a map, the select pass writes the route's keys into d_val, one word
+     * per line; h_map / d_map: the nreg + 1 buckets of the call on the host and on the device; mode is unused */
+    const int32_t              *h_map, *d_map;
+    uint32_t                    nreg;
 };
 
 /* entries per line of the sink's table */
@@ -1726,7 +1750,10 @@ lines_device_batch_end(sre_hip_scanner_t *sc, LinesTotals *tot, const LinesSink 
                        uint64_t rcap, hipStream_t stream)
 {
     const size_t slots = 2 + (size_t) sc->ovec_slots;
-    if (sink) {
+    if (sink && sink->h_map) {
+        SRE_HIP_TRY(sre_launch_route_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->nreg, sink->d_map, sc->d_ends,
+                                            sc->d_linfo, sink->d_val, stream));
+    } else if (sink) {
         SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
     } else {
         SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
@@ -2003,6 +2030,14 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
             SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0 * k, vals.data(), nb * k * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             SRE_HIP_TRY(hipMemcpyAsync(sink->d_start + i0 * k, starts.data(), nb * k * sizeof(uint64_t), hipMemcpyHostToDevice,
                                        stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        } else if (sink && sink->h_map) {
+            /* what sre_k_route_select writes, from the records the host holds */
+            vals.resize(nb);
+            for (uint64_t j = 0; j < nb; j++) {
+                vals[j] = sre_lr_key(sre_lr_bucket(recs[j * slots], SRE_DECLINED, sink->nreg, sink->h_map), (uint64_t) lens[j]);
+            }
+            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0, vals.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             SRE_HIP_TRY(hipStreamSynchronize(stream));
         } else if (sink) {
             vals.resize(nb);
@@ -2417,6 +2452,124 @@ sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, i
         }
         if (info) *info = res;
     }
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The line route: the line-mode call with the route's sink (a key per line), then on the device the
+ * per-(bucket, workgroup) counts and their scan, one read of the selected lines, the scatter into the compact table, the
+ * filter's scan over it, the cut and the bucket totals, one read of 4 + 2 nbuckets words, the extract's gather over the
+ * compact table and the index rows. */
+extern "C" SRE_API int
+sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *bucket_of, size_t nbuckets,
+    void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info,
+    sre_hip_route_bucket_t *buckets, void *hip_stream)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || nbuckets < 1 || nbuckets > SRE_LR_MAX_BUCKETS
+        || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
+    {
+        return -1;
+    }
+    if (sc->mode != SRE_HIP_PIKE_FIRST) {
+        fprintf(stderr, "[sregex-hip] line route: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's regex id)\n");
+        return -1;
+    }
+    const uint32_t R = sc->prog->nregexes;
+    if (bucket_of == NULL && nbuckets != R) return -1;
+    std::vector<int32_t> map(R + 1);
+    for (uint32_t r = 0; r <= R; r++) {
+        const int b = bucket_of ? bucket_of[r] : (r < R ? (int) r : -1);
+        if (b < -1 || b >= (int) nbuckets) return -1;
+        map[r] = b;
+    }
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return -1;
+    }
+    hipStream_t           stream = static_cast<hipStream_t>(hip_stream);
+    const uint32_t        nb = (uint32_t) nbuckets;
+    sre_hip_filter_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (buckets) memset(buckets, 0, nbuckets * sizeof(*buckets));
+    /* the map on the device, uploaded when it differs from the one it holds */
+    if (sc->d_rmap == NULL) {
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rmap), (R + 1) * sizeof(int32_t)));
+        sc->h_rmap = static_cast<int32_t *>(malloc((R + 1) * sizeof(int32_t)));
+        if (sc->h_rmap == NULL) return -1;
+        sc->rmap_valid = false;
+    }
+    if (!sc->rmap_valid || memcmp(sc->h_rmap, map.data(), (R + 1) * sizeof(int32_t)) != 0) {
+        sc->rmap_valid = false;
+        memcpy(sc->h_rmap, map.data(), (R + 1) * sizeof(int32_t));
+        SRE_HIP_TRY(hipMemcpyAsync(sc->d_rmap, sc->h_rmap, (R + 1) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        sc->rmap_valid = true;
+    }
+    {
+        LinesSink sink = {0, NULL, NULL, NULL, NULL, sc->h_rmap, sc->d_rmap, R};
+        uint64_t  n = 0, nrep = 0;
+        if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+        if (n != 0) {
+            const uint64_t nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nb * nwg;
+            /* (the scans' sums: over the counts first, then over at most n entries of the compact table) */
+            const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+            const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
+            if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (sc->d_rres == NULL) {
+                SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
+                SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
+            }
+            SRE_HIP_TRY(sre_launch_route_count(sc->d_fval, n, nb, sc->d_rcnt, stream));
+            SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, ncnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+            /* the selected lines size the compact table */
+            SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rcnt + ncnt, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            const uint64_t nsel = sc->h_rres[0];
+            if (nsel > n) return -1;        /* (cannot happen: every line is counted once) */
+            if (nsel != 0) {
+                if (lines_grow(&sc->d_fstart, &sc->fstart_cap, nsel * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_rval, &sc->rval_cap, (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_rmeta, &sc->rmeta_cap, nsel * sizeof(uint64_t)) != 0) return -1;
+                SRE_HIP_TRY(sre_launch_route_scatter(sc->d_fval, sc->d_ends, n, nb, sc->d_rcnt, nsel, sc->d_fstart, sc->d_rval,
+                                                     sc->d_rmeta, stream));
+                SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rval, nsel, sc->d_fblk, out_cap, sc->d_linfo, stream));
+            }
+            SRE_HIP_TRY(sre_launch_route_finish(sc->d_rcnt, n, nb, sc->d_rval, nsel, out_cap, sc->d_rres, stream));
+            SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, (SRE_LR_RES_WORDS + 2 * (size_t) nb) * sizeof(uint64_t),
+                                       hipMemcpyDeviceToHost, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            res.nlines = (size_t) n;
+            res.nselected = (size_t) sc->h_rres[SRE_LR_RES_NSEL];
+            res.need_bytes = (size_t) sc->h_rres[SRE_LR_RES_NEED];
+            res.nwritten = (size_t) sc->h_rres[SRE_LR_RES_WRITTEN];
+            res.out_bytes = (size_t) sc->h_rres[SRE_LR_RES_BYTES];
+            if (res.out_bytes > out_cap || res.nselected != nsel) return -1;     /* (cannot happen) */
+            if (buckets) {
+                size_t at = 0;
+                for (uint32_t b = 0; b < nb; b++) {
+                    buckets[b].nlines = (size_t) sc->h_rres[SRE_LR_RES_WORDS + 2 * b];
+                    buckets[b].bytes = (size_t) sc->h_rres[SRE_LR_RES_WORDS + 2 * b + 1];
+                    buckets[b].offset = at;
+                    at += buckets[b].bytes;
+                }
+            }
+            if (res.out_bytes != 0) {
+                /* the compact table is an entry table with one entry a line: the extract's gather, unchanged */
+                SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_fstart, nsel, res.out_bytes, (uint32_t) delim,
+                                                      (uint32_t) delim, stream));
+            }
+            if (res.nwritten != 0 && index_cap != 0) {
+                const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
+                SRE_HIP_TRY(sre_launch_route_index(sc->d_rval, sc->d_fstart, sc->d_rmeta, sc->d_rres, nrows, index_cap, d_index,
+                                                   stream));
+            }
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    if (info) *info = res;
     return 0;
 hip_failed:
     return -1;

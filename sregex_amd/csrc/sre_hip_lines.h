@@ -181,6 +181,26 @@ hipError_t sre_launch_subst_gather(const void *d_buf, void *d_out, const uint64_
 hipError_t sre_launch_subst_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, uint64_t n,
     uint32_t p, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
+/* ---- the line route (sre_hip_lines_route.hip, sre_lines_route.h) ---- */
+/* select pass of the batch (lines i0 .. info->i1, at most nmax): d_key[i] = bucket << 56 | (len + 1), the bucket
+ * d_map[rc] of the regex that matched (d_map[nreg] without a match), or 0 where the map says -1; d_map: nreg + 1 words */
+hipError_t sre_launch_route_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, uint32_t nreg,
+    const int32_t *d_map, const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_key, hipStream_t stream);
+/* d_cnt[b * nwg + w] = lines of bucket b among the SRE_LINES_ITEMS lines of workgroup w, nwg = ceil(n / SRE_LINES_ITEMS);
+ * sre_launch_filter_offsets over those nbuckets * nwg words (+ 1) then makes them the first ranks */
+hipError_t sre_launch_route_count(const uint64_t *d_key, uint64_t n, uint32_t nbuckets, uint64_t *d_cnt, hipStream_t stream);
+/* the compact table from the scanned counts: entry r of nsel = d_first[nbuckets * nwg] is the line of rank r in the
+ * bucket-major, line-ordered output: d_cstart[r] its source offset under SRE_LG_ENTRY_LAST | FIRST, d_cval[r] = len + 1,
+ * d_cmeta[r] = bucket << 56 | line */
+hipError_t sre_launch_route_scatter(const uint64_t *d_key, const uint64_t *d_ends, uint64_t n, uint32_t nbuckets,
+    const uint64_t *d_first, uint64_t nsel, uint64_t *d_cstart, uint64_t *d_cval, uint64_t *d_cmeta, hipStream_t stream);
+/* behind sre_launch_filter_offsets over d_cval (d_coff[0 .. nsel]; not read when nsel == 0): d_res[0 .. 4) = nsel, the
+ * bytes of all rows, the rows that fit out_cap whole, their bytes; then [lines, bytes] of each bucket */
+hipError_t sre_launch_route_finish(const uint64_t *d_first, uint64_t n, uint32_t nbuckets, const uint64_t *d_coff, uint64_t nsel,
+    uint64_t out_cap, uint64_t *d_res, hipStream_t stream);
+/* rows [line, start, len, output offset, bucket] of the first min(index_cap, d_res[2]) ranks; nrows: that number */
+hipError_t sre_launch_route_index(const uint64_t *d_coff, const uint64_t *d_cstart, const uint64_t *d_cmeta,
+    const uint64_t *d_res, uint64_t nrows, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif
