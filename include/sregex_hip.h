@@ -573,6 +573,73 @@ SRE_API int sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t
     sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info,
     sre_hip_route_bucket_t *buckets, void *hip_stream);
 
+/* ---- line tally: the distinct capture-group texts of the lines and how many lines carry each ---- */
+
+typedef struct {
+    size_t nlines;      /* lines of the buffer */
+    size_t nselected;   /* lines that have a key (sum of all counts) */
+    size_t nkeys;       /* distinct keys */
+    size_t need_bytes;  /* bytes of all key rows */
+    size_t nwritten;    /* key rows written (whole rows only) */
+    size_t out_bytes;
+} sre_hip_tally_info_t;
+
+enum { SRE_HIP_TALLY_OVERFLOW = 1 };
+
+/*
+ * Line tally: `extract | sort | uniq -c` without the sort: one row per DISTINCT tuple of field
+ * texts, and how many lines carry it ("lines per status code / client address / host").  The
+ * split of d_buf, the matching of every line, the routing to an engine, the batching, the
+ * diagnostics, the demand for an SRE_HIP_PIKE_FIRST scanner (Thompson and COUNT scanners return
+ * -1 with a diagnostic), the rules for groups / ngroups / fsep, the flags (0 or
+ * SRE_HIP_LINES_ALL; any other bit returns -1) and the overlap check of d_out are exactly those
+ * of sre_hip_extract_lines on the same (sc, d_buf, len, delim).
+ *
+ * Key.  The key of a selected line is the tuple of its K = ngroups field texts as the extract
+ * defines them; an unset group is an empty field.  Two lines have the same key when every field
+ * has the same length and the same bytes: ("ab", "c") and ("a", "bc") are different keys
+ * although their rows are the same text when a field contains fsep.  With SRE_HIP_LINES_ALL the
+ * lines without a match share the key whose fields are all empty.
+ *
+ * Output.  One row per distinct key in the extract's row format (field 0, fsep, .., field K - 1,
+ * delim), ordered by the FIRST line that carries each key: key k is the k-th key to appear, and
+ * row k is exactly the row sre_hip_extract_lines writes for that first line.  The result does
+ * not depend on the order in which the device processes the lines.  Truncation is the
+ * extract's: whole rows only, info->nwritten of them in info->out_bytes bytes, nothing at or
+ * beyond out_bytes is touched, d_out may be NULL with out_cap == 0 (a sizing call).
+ * info->need_bytes is the bytes of all info->nkeys rows whatever out_cap is.
+ *
+ * d_counts is an optional DEVICE array: d_counts[k], k < min(counts_cap, nkeys), is the number
+ * of lines with key k.  d_keyid is an optional DEVICE array: d_keyid[i], i < min(keyid_cap,
+ * nlines), is the key number of line i, or -1 for a line without a key.  Neither depends on
+ * out_cap: a sizing call delivers both in full.  d_index is an optional DEVICE array of the
+ * extract's index rows (4 + 2 * ngroups sre_int_t) for the first min(index_cap, nwritten) key
+ * rows, each describing the key's first line.  Each may be NULL when its capacity is 0; nothing
+ * beyond the entries named here is touched.  info->nselected is the sum of all counts.
+ *
+ * max_keys and overflow.  1 <= max_keys <= 2^30, anything else returns -1.  When the buffer holds
+ * more than max_keys distinct keys the call returns SRE_HIP_TALLY_OVERFLOW: nothing is written to
+ * d_out, d_counts, d_keyid or d_index, and info holds nlines and nselected and zeros elsewhere.
+ * nkeys == max_keys succeeds.
+ *
+ * The call is synchronous and all its work runs on hip_stream; the host waits exactly as often
+ * as in sre_hip_extract_lines (the overflow flag and nselected travel with the words that call
+ * reads).  On the host route (the exact VM, SRE_HIP_LINES_NFA_HOST=1) the per-field values are
+ * uploaded as there, and everything behind them runs on the device.  len == 0 gives all zeros in
+ * info and success.  Beyond what sre_hip_extract_lines takes (and shares), a scanner keeps 16
+ * bytes per table slot, slots = the power of two >= 2 * max_keys and at least 1024, and 4 bytes
+ * per line of the largest call; grow-only device memory, freed with the scanner.  Not offered:
+ * keys ordered by count or text, top-k, sums of a field, every match of a line, caseless keys.
+ * Returns 0 on success, SRE_HIP_TALLY_OVERFLOW, or -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, int fsep, int flags, size_t max_keys,
+    void *d_out, size_t out_cap,
+    uint64_t *d_counts, size_t counts_cap,
+    sre_int_t *d_keyid, size_t keyid_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_tally_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

@@ -31,6 +31,8 @@ HIP_EXTRACT_MAX_FIELDS = 32
 HIP_SUBST_MAX_PIECES = 30
 HIP_SUBST_MAX_LITERAL = 4096
 HIP_ROUTE_MAX_BUCKETS = 256
+HIP_TALLY_OVERFLOW = 1
+HIP_TALLY_MAX_KEYS = 1 << 30
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -94,6 +96,8 @@ API = {
                                                 _vp, _vp]),
     "sre_hip_route_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, _sz, _vp, _sz, _vp,
                                            _vp, _vp]),
+    "sre_hip_tally_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int,
+                                           ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -521,6 +525,31 @@ class Scanner:
             raise RuntimeError("sre_hip_route_lines failed")
         return FilterInfo(*info), [RouteBucket(*bk[3 * b:3 * b + 3]) for b in range(nbuckets)]
 
+    def tally_lines(self, ptr, length, out_ptr, out_cap, groups, max_keys, delim=0x0A, fsep=0x09, flags=0, counts_ptr=None,
+                    counts_cap=0, keyid_ptr=None, keyid_cap=0, index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_tally_lines: the distinct keys of the device buffer (ptr, length) and how many lines carry each.  The
+        key of a matching line (of every line with flags=HIP_LINES_ALL) is the tuple of the texts of the capture groups
+        `groups` of its first match, as extract_lines defines them.  The device buffer (out_ptr, out_cap) receives one
+        row per distinct key in the extract's row format, ordered by the first line that carries each key: row k is the
+        row extract_lines writes for that line.  counts_ptr: an optional device array of counts_cap uint64, the lines
+        of key k; keyid_ptr: an optional device array of keyid_cap int64, the key number of line i or -1; index_ptr: an
+        optional device array of index_cap of the extract's index rows, each describing a key's first line.  Counts and
+        key ids are complete whatever out_cap is.  The scanner's mode must be HIP_PIKE_FIRST.  Returns
+        TallyInfo(nlines, nselected, nkeys, need_bytes, nwritten, out_bytes).  More than max_keys distinct keys raise
+        TallyOverflow, whose .info holds nlines and nselected and zeros elsewhere; nothing was written then."""
+        groups = list(groups)
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        info = TallyInfoStruct()
+        rc = self.lib.sre_hip_tally_lines(self.h, ptr, length, delim, arr, len(groups), fsep, flags, max_keys, out_ptr, out_cap,
+                                          counts_ptr, counts_cap, keyid_ptr, keyid_cap, index_ptr, index_cap, ctypes.byref(info),
+                                          hip_stream)
+        res = TallyInfo(info.nlines, info.nselected, info.nkeys, info.need_bytes, info.nwritten, info.out_bytes)
+        if rc == HIP_TALLY_OVERFLOW:
+            raise TallyOverflow(res, max_keys)
+        if rc != 0:
+            raise RuntimeError("sre_hip_tally_lines failed")
+        return res
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -539,6 +568,22 @@ class Scanner:
 FilterInfo = collections.namedtuple("FilterInfo", "nlines nselected need_bytes nwritten out_bytes")
 RouteBucket = collections.namedtuple("RouteBucket", "nlines offset bytes")
 ContextInfo = collections.namedtuple("ContextInfo", "nlines nmatched nselected ngroups need_bytes nwritten out_bytes")
+TallyInfo = collections.namedtuple("TallyInfo", "nlines nselected nkeys need_bytes nwritten out_bytes")
+
+
+class TallyInfoStruct(ctypes.Structure):
+    """sre_hip_tally_info_t"""
+    _fields_ = [(name, ctypes.c_size_t) for name in TallyInfo._fields]
+
+
+class TallyOverflow(RuntimeError):
+    """sre_hip_tally_lines returned SRE_HIP_TALLY_OVERFLOW: the buffer holds more than max_keys distinct keys.  .info is
+    the call's TallyInfo (nlines and nselected, zeros elsewhere)."""
+
+    def __init__(self, info, max_keys):
+        RuntimeError.__init__(self, "sre_hip_tally_lines: more than max_keys = %d distinct keys" % max_keys)
+        self.info = info
+        self.max_keys = max_keys
 
 
 class StreamSet:

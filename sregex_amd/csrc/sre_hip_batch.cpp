@@ -22,6 +22,7 @@
 #include "sre_hip_lines.h"
 #include "sre_lines_gather.h"
 #include "sre_lines_route.h"
+#include "sre_lines_tally.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
 #include <stdio.h>
@@ -162,6 +163,11 @@ struct sre_hip_scanner_s {
     int32_t                  *h_rmap;           /* the map the device holds, so that a repeated map uploads nothing */
     bool                      rmap_valid;
     uint64_t                 *d_rres, *h_rres;  /* the words the host reads: SRE_LR_RES_WORDS + 2 x SRE_LR_MAX_BUCKETS */
+    /* the line tally (sre_hip_tally_lines): the entry table is the extract's (d_fval, d_fstart, d_fblk); it adds */
+    uint64_t                 *d_ttab;           /* the table of keys: nslots words of line numbers, then nslots counts */
+    size_t                    ttab_cap;
+    uint32_t                 *d_tslot;          /* the slot of every line */
+    size_t                    tslot_cap;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -233,6 +239,8 @@ scanner_release(void *data)
     free(sc->h_rmap);
     if (sc->d_rres) (void) hipFree(sc->d_rres);
     if (sc->h_rres) (void) hipHostFree(sc->h_rres);
+    if (sc->d_ttab) (void) hipFree(sc->d_ttab);
+    if (sc->d_tslot) (void) hipFree(sc->d_tslot);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -2302,6 +2310,99 @@ sre_hip_extract_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int 
     }
     if (info) *info = res;
     return 0;
+hip_failed:
+    return -1;
+}
+
+/* the hash bits the tally's table index keeps: SRE_HIP_TALLY_HASH_BITS (test knob, read on every call; 0 .. 64), else all */
+static uint64_t
+tally_hash_mask(void)
+{
+    const char *e = getenv("SRE_HIP_TALLY_HASH_BITS");
+    if (e == NULL || *e == 0) return ~(uint64_t) 0;
+    return sre_lt_hash_mask(atoi(e));
+}
+
+/* The line tally: the extract's call up to its select passes, then on the device the insert of every
+ * selected line into the table of keys and the keep pass that leaves the first line of every key selected, then the
+ * extract's scan, cut, one read (its four words and the tally's three), gather and index, and the ranks. */
+extern "C" SRE_API int
+sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups, int fsep,
+    int flags, size_t max_keys, void *d_out, size_t out_cap, uint64_t *d_counts, size_t counts_cap, sre_int_t *d_keyid,
+    size_t keyid_cap, sre_int_t *d_index, size_t index_cap, sre_hip_tally_info_t *info, void *hip_stream)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0
+        || groups == NULL || ngroups < 1 || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (out_cap != 0 && d_out == NULL)
+        || (index_cap != 0 && d_index == NULL) || (counts_cap != 0 && d_counts == NULL) || (keyid_cap != 0 && d_keyid == NULL)
+        || (len != 0 && d_buf == NULL) || max_keys < 1 || max_keys > SRE_LT_MAX_KEYS)
+    {
+        return -1;
+    }
+    if (sc->mode != SRE_HIP_PIKE_FIRST) {
+        fprintf(stderr, "[sregex-hip] line tally: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
+        return -1;
+    }
+    sre_extract_groups_t gr;
+    memset(&gr, 0, sizeof(gr));
+    gr.k = (uint32_t) ngroups;
+    for (size_t f = 0; f < ngroups; f++) {
+        /* ovec_slots = 2 * (max_ncaps + 1) */
+        if (groups[f] < 0 || groups[f] > 0xFFFF || 2 * (size_t) groups[f] + 1 >= (size_t) sc->ovec_slots) return -1;
+        gr.g[f] = (uint16_t) groups[f];
+    }
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, &gr, NULL};
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_tally_info_t res;
+    memset(&res, 0, sizeof(res));
+    int rc = 0;
+    if (n != 0) {
+        const uint64_t nent = n * gr.k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        const uint64_t nslots = sre_lt_nslots(max_keys);
+        uint64_t      *tab, *cnt;
+        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
+        tab = sc->d_ttab;
+        cnt = sc->d_ttab + nslots;
+        SRE_HIP_TRY(hipMemsetAsync(tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
+        SRE_HIP_TRY(hipMemsetAsync(cnt, 0, nslots * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, gr.k, nslots, max_keys, tally_hash_mask(), tab, cnt,
+                                            sc->d_tslot, sc->d_linfo, stream));
+        SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_fval, n, gr.k, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        /* fsel, fneed, fwritten, fbytes, (cmatched, cgroups,) tsel, tclaims, tover */
+        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 9 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nselected = (size_t) sc->h_linfo->tsel;
+        if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
+            rc = SRE_HIP_TALLY_OVERFLOW;
+        } else {
+            res.nkeys = (size_t) sc->h_linfo->fsel;
+            res.need_bytes = (size_t) sc->h_linfo->fneed;
+            res.nwritten = (size_t) sc->h_linfo->fwritten;
+            res.out_bytes = (size_t) sc->h_linfo->fbytes;
+            if (res.out_bytes > out_cap || res.nkeys != sc->h_linfo->tclaims) return -1;    /* (cannot happen) */
+            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, nent, res.out_bytes, (uint32_t) delim,
+                                                  (uint32_t) fsep, stream));
+            if (res.nwritten != 0) {
+                SRE_HIP_TRY(sre_launch_extract_index(sc->d_fval, sc->d_fstart, sc->d_ends, n, gr.k, sc->d_fblk, sc->d_linfo,
+                                                     index_cap, d_index, stream));
+            }
+            SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, gr.k, sc->d_fblk, sc->d_tslot, cnt, d_counts, counts_cap,
+                                               reinterpret_cast<int64_t *>(d_keyid), keyid_cap, stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    if (info) *info = res;
+    return rc;
 hip_failed:
     return -1;
 }

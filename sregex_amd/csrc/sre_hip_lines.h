@@ -49,6 +49,10 @@ typedef struct {
     /* the filter with context (sre_hip_filter_lines_context): two more words, read with the four */
     uint64_t cmatched;      /* lines the match rule selects (with context only; without, fsel says it) */
     uint64_t cgroups;       /* maximal runs of adjacent selected lines */
+    /* the line tally (sre_hip_tally_lines): three more words, read with the four (zeroed in front of the insert) */
+    uint64_t tsel;          /* lines that have a key */
+    uint64_t tclaims;       /* slots of the table claimed */
+    uint64_t tover;         /* not 0: more than max_keys distinct keys, or the table is full */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -201,6 +205,21 @@ hipError_t sre_launch_route_finish(const uint64_t *d_first, uint64_t n, uint32_t
 /* rows [line, start, len, output offset, bucket] of the first min(index_cap, d_res[2]) ranks; nrows: that number */
 hipError_t sre_launch_route_index(const uint64_t *d_coff, const uint64_t *d_cstart, const uint64_t *d_cmeta,
     const uint64_t *d_res, uint64_t nrows, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
+/* ---- the line tally (sre_hip_lines_tally.hip, sre_lines_tally.h) ---- */
+/* between the extract's last select pass and sre_launch_extract_offsets.  insert, a lane per line: a selected line
+ * (d_val[line * k] != 0) finds or claims the slot of its key in d_tab (nslots words, all SRE_LT_EMPTY before) and leaves
+ * the slot in d_lslot[line], SRE_LT_NONE for the others; d_cnt[slot] (zero before) += the lines of the slot, one add per
+ * distinct slot of a wave; info->tsel, tclaims, tover (zero before).  keep, a lane per entry: d_val[e] = 0 for every
+ * entry of a line that is not the final word of its slot, so the table selects the first line of every key */
+hipError_t sre_launch_tally_insert(const void *d_buf, uint64_t *d_val, const uint64_t *d_start, uint64_t n, uint32_t k,
+    uint64_t nslots, uint64_t max_keys, uint64_t hash_mask, uint64_t *d_tab, uint64_t *d_cnt, uint32_t *d_lslot,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* behind sre_launch_extract_offsets (d_off, and d_blk as it left them): the rank r of every kept line among the kept
+ * lines is the number of its key: d_counts[r] = d_cnt[slot] for r < counts_cap, then d_cnt[slot] = r; and, in a second
+ * kernel, d_keyid[i] = d_cnt[d_lslot[i]] for i < min(keyid_cap, n), -1 for a line without a slot */
+hipError_t sre_launch_tally_ranks(const uint64_t *d_off, const uint64_t *d_start, uint64_t n, uint32_t k, const uint64_t *d_blk,
+    const uint32_t *d_lslot, uint64_t *d_cnt, uint64_t *d_counts, uint64_t counts_cap, int64_t *d_keyid, uint64_t keyid_cap,
+    hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif
