@@ -629,7 +629,7 @@ enum { SRE_HIP_TALLY_OVERFLOW = 1 };
  * info and success.  Beyond what sre_hip_extract_lines takes (and shares), a scanner keeps 16
  * bytes per table slot, slots = the power of two >= 2 * max_keys and at least 1024, and 4 bytes
  * per line of the largest call; grow-only device memory, freed with the scanner.  Not offered:
- * keys ordered by count or text, top-k, sums of a field, every match of a line, caseless keys.
+ * keys ordered by count or text, top-k, every match of a line, caseless keys.
  * Returns 0 on success, SRE_HIP_TALLY_OVERFLOW, or -1 on bad arguments or failure.
  */
 SRE_API int sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
@@ -639,6 +639,63 @@ SRE_API int sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t
     sre_int_t *d_keyid, size_t keyid_cap,
     sre_int_t *d_index, size_t index_cap,
     sre_hip_tally_info_t *info, void *hip_stream);
+
+/* ---- line tally with sums: sum, min, max of a numeric capture group per key ---- */
+
+enum { SRE_HIP_TALLY_MAX_VALUES = 8 };
+
+typedef struct {
+    int64_t  sum;   /* of the lines' numbers, modulo 2^64 (two's complement wrap) */
+    int64_t  min;   /* INT64_MAX when n == 0 */
+    int64_t  max;   /* INT64_MIN when n == 0 */
+    uint64_t n;     /* lines of the key whose field is a number */
+} sre_hip_tally_sum_t;
+
+/*
+ * Line tally with sums: `SELECT key, COUNT(*), SUM(v), MIN(v), MAX(v) .. GROUP BY key`, or
+ * awk '{ s[$1] += $10 }' ("bytes sent per client", "total and worst request time per endpoint").
+ * d_out, d_counts, d_keyid, d_index, info, max_keys, overflow, the argument checks and the host's
+ * waits on the stream are exactly those of sre_hip_tally_lines on the same (sc, d_buf, len, delim,
+ * groups, ngroups, fsep, flags, max_keys); that call's contract is not restated here.
+ *
+ * Value columns.  vgroups names 1 <= nvgroups <= SRE_HIP_TALLY_MAX_VALUES capture groups under the
+ * range rule of groups[]; a value group may also be a key group and may appear twice.
+ * nvgroups == 0 or beyond the maximum, vgroups == NULL, sums_cap != 0 with d_sums == NULL, or a
+ * d_sums that is not 8-byte aligned returns -1.
+ *
+ * Number rule.  The text of value group v in a line's first match is a number when it is an
+ * optional single '-' followed by 1 to 18 bytes that are all '0' .. '9', and nothing else.  Its
+ * value is the decimal value, negated after '-': "-0" is 0, "007" is 7.  Anything else is not a
+ * number and touches nothing: an unset or empty group, "+1", "-", "1 ", "12a", 19 or more digits,
+ * and every value column of a line without a match under SRE_HIP_LINES_ALL.  18 digits keep every
+ * value inside int64; only the sum can wrap, and it wraps modulo 2^64.
+ *
+ * d_sums is an optional DEVICE array: d_sums[k * nvgroups + v], k < min(sums_cap, nkeys), is the
+ * aggregate of value column v over all lines of key k; sums_cap counts keys.  A column in which no
+ * line of the key is a number is {0, INT64_MAX, INT64_MIN, 0}.  d_sums does not depend on out_cap:
+ * a sizing call delivers it in full.  Nothing at or beyond row min(sums_cap, nkeys) is touched, and
+ * on SRE_HIP_TALLY_OVERFLOW nothing of d_sums is written.  Sum, min, max and n do not depend on
+ * the order in which the device meets the lines: the result is bit-exact.
+ *
+ * Beyond what sre_hip_tally_lines takes (and shares), a scanner keeps 16 bytes per line and value
+ * column of the largest call, and at most 8 MiB of working copies of the aggregates; grow-only
+ * device memory, freed with the scanner.
+ * sre_hip_tally_lines itself never allocates or fills it.  Not offered: fractions, exponents,
+ * hexadecimal, '+', floating-point sums, averages (divide sum by n), sums over every match of a
+ * line.  Returns 0 on success, SRE_HIP_TALLY_OVERFLOW, or -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_tally_sums_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, const int *vgroups, size_t nvgroups, int fsep, int flags,
+    size_t max_keys, void *d_out, size_t out_cap,
+    uint64_t *d_counts, size_t counts_cap,
+    sre_hip_tally_sum_t *d_sums, size_t sums_cap,
+    sre_int_t *d_keyid, size_t keyid_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_tally_info_t *info, void *hip_stream);
+
+/* host only, needs no device: the number rule above on len bytes of text.  1: a number, *value is
+ * it; 0: not a number, *value is untouched */
+SRE_API int sre_hip_tally_number(const void *text, size_t len, int64_t *value);
 
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 

@@ -33,6 +33,7 @@ HIP_SUBST_MAX_LITERAL = 4096
 HIP_ROUTE_MAX_BUCKETS = 256
 HIP_TALLY_OVERFLOW = 1
 HIP_TALLY_MAX_KEYS = 1 << 30
+HIP_TALLY_MAX_VALUES = 8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -98,6 +99,10 @@ API = {
                                            _vp, _vp]),
     "sre_hip_tally_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int,
                                            ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_tally_sums_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz,
+                                                ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _sz, _vp, _sz, _vp, _sz,
+                                                _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_tally_number": (ctypes.c_int, [ctypes.c_char_p, _sz, ctypes.POINTER(ctypes.c_int64)]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -170,6 +175,16 @@ def template_pieces(template, max_group):
     if load_library().sre_hip_subst_template_check(template, len(template), max_group, groups, ctypes.byref(n)) != 0:
         raise ValueError("invalid substitute template %r for max_group %d" % (template, max_group))
     return list(groups[:n.value])
+
+
+def tally_number(text):
+    """sre_hip_tally_number: the value of `text` (bytes) under the number rule of Scanner.tally_sums_lines (an optional
+    '-' and 1 to 18 decimal digits, nothing else) as an int, or None when it is not a number.  Needs no device."""
+    text = bytes(text)
+    value = ctypes.c_int64()
+    if load_library().sre_hip_tally_number(text, len(text), ctypes.byref(value)) != 1:
+        return None
+    return value.value
 
 
 def _capture_stdout(fn):
@@ -550,6 +565,29 @@ class Scanner:
             raise RuntimeError("sre_hip_tally_lines failed")
         return res
 
+    def tally_sums_lines(self, ptr, length, out_ptr, out_cap, groups, vgroups, max_keys, delim=0x0A, fsep=0x09, flags=0,
+                         counts_ptr=None, counts_cap=0, sums_ptr=None, sums_cap=0, keyid_ptr=None, keyid_cap=0, index_ptr=None,
+                         index_cap=0, hip_stream=None):
+        """sre_hip_tally_sums_lines: tally_lines with the same arguments and results, and per key the sum, minimum,
+        maximum and count of the numbers in the capture groups `vgroups` (1 .. HIP_TALLY_MAX_VALUES of them) of the
+        key's lines.  sums_ptr: an optional device array of sums_cap rows of len(vgroups) TallySumStruct, row k the
+        aggregates of key k; a text is a number when tally_number() says so, anything else touches nothing, and a
+        column without a number is (0, INT64_MAX, INT64_MIN, 0).  The sum wraps modulo 2^64.  Returns TallyInfo; raises
+        TallyOverflow as tally_lines does, with nothing written."""
+        groups, vgroups = list(groups), list(vgroups)
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        varr = (ctypes.c_int * max(len(vgroups), 1))(*vgroups)
+        info = TallyInfoStruct()
+        rc = self.lib.sre_hip_tally_sums_lines(self.h, ptr, length, delim, arr, len(groups), varr, len(vgroups), fsep, flags,
+                                               max_keys, out_ptr, out_cap, counts_ptr, counts_cap, sums_ptr, sums_cap, keyid_ptr,
+                                               keyid_cap, index_ptr, index_cap, ctypes.byref(info), hip_stream)
+        res = TallyInfo(info.nlines, info.nselected, info.nkeys, info.need_bytes, info.nwritten, info.out_bytes)
+        if rc == HIP_TALLY_OVERFLOW:
+            raise TallyOverflow(res, max_keys)
+        if rc != 0:
+            raise RuntimeError("sre_hip_tally_sums_lines failed")
+        return res
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -574,6 +612,11 @@ TallyInfo = collections.namedtuple("TallyInfo", "nlines nselected nkeys need_byt
 class TallyInfoStruct(ctypes.Structure):
     """sre_hip_tally_info_t"""
     _fields_ = [(name, ctypes.c_size_t) for name in TallyInfo._fields]
+
+
+class TallySumStruct(ctypes.Structure):
+    """sre_hip_tally_sum_t"""
+    _fields_ = [("sum", ctypes.c_int64), ("min", ctypes.c_int64), ("max", ctypes.c_int64), ("n", ctypes.c_uint64)]
 
 
 class TallyOverflow(RuntimeError):

@@ -23,6 +23,7 @@
 #include "sre_lines_gather.h"
 #include "sre_lines_route.h"
 #include "sre_lines_tally.h"
+#include "sre_lines_sums.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
 #include <stdio.h>
@@ -168,6 +169,13 @@ struct sre_hip_scanner_s {
     size_t                    ttab_cap;
     uint32_t                 *d_tslot;          /* the slot of every line */
     size_t                    tslot_cap;
+    /* the tally's sums (sre_hip_tally_sums_lines) add a second entry table over the value groups: lines x columns words each */
+    uint64_t                 *d_vval;
+    size_t                    vval_cap;
+    uint64_t                 *d_vstart;
+    size_t                    vstart_cap;
+    sre_ls_agg_t             *d_vcopy;          /* the copies of the aggregates the waves send to: at most SRE_LS_COPY_BYTES */
+    size_t                    vcopy_cap;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -241,6 +249,9 @@ scanner_release(void *data)
     if (sc->h_rres) (void) hipHostFree(sc->h_rres);
     if (sc->d_ttab) (void) hipFree(sc->d_ttab);
     if (sc->d_tslot) (void) hipFree(sc->d_tslot);
+    if (sc->d_vval) (void) hipFree(sc->d_vval);
+    if (sc->d_vstart) (void) hipFree(sc->d_vstart);
+    if (sc->d_vcopy) (void) hipFree(sc->d_vcopy);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -1701,6 +1712,10 @@ struct LinesSink {
      * per line; h_map / d_map: the nreg + 1 buckets of the call on the host and on the device; mode is unused */
     const int32_t              *h_map, *d_map;
     uint32_t                    nreg;
+    /* the tally's sums (sre_hip_tally_sums_lines): with value groups (and groups), the extract's select pass runs a
+     * second time over the entries line * v + column into d_vval and d_vstart; the key table is untouched by it */
+    const sre_extract_groups_t *vgroups;
+    uint64_t                   *d_vval, *d_vstart;
 };
 
 /* entries per line of the sink's table */
@@ -1763,6 +1778,10 @@ lines_device_batch_end(sre_hip_scanner_t *sc, LinesTotals *tot, const LinesSink 
                                             sc->d_linfo, sink->d_val, stream));
     } else if (sink) {
         SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
+        if (sink->vgroups) {
+            SRE_HIP_TRY(sre_launch_extract_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->vgroups,
+                                                  sc->d_ends, sc->d_linfo, sink->d_vval, sink->d_vstart, stream));
+        }
     } else {
         SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
                                              sc->d_linfo, sc->d_rows, rcap, stream));
@@ -1958,6 +1977,7 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
     std::vector<sre_int_t>    recs;
     std::vector<uint64_t>     vals;             /* with a sink: the batch's per-line values, uploaded */
     std::vector<uint64_t>     starts;           /* ... of the line extract: and the per-entry source offsets */
+    std::vector<uint64_t>     vvals, vstarts;   /* ... of the tally's sums: and the same of the value table */
     uint64_t                  nrep = 0;
     for (uint64_t i0 = 0; i0 < n;) {
         const uint64_t nb = bmax < n - i0 ? bmax : n - i0;
@@ -2018,26 +2038,32 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
                                        stream));
             SRE_HIP_TRY(hipStreamSynchronize(stream));
         } else if (sink && sink->groups) {
-            /* what sre_k_extract_select writes, from the records the host holds */
-            const uint32_t k = sink->groups->k;
-            vals.resize(nb * k);
-            starts.resize(nb * k);
-            for (uint64_t j = 0; j < nb; j++) {
-                const sre_int_t *rec = recs.data() + j * slots;
-                const bool       hit = rec[0] != SRE_DECLINED;
-                const uint64_t   st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf);
-                for (uint32_t f = 0; f < k; f++) {
-                    const uint32_t  g = sink->groups->g[f];
-                    const sre_int_t a = hit ? rec[2 + 2 * g] : -1, b = hit ? rec[3 + 2 * g] : -1;
-                    const bool      set = a >= 0 && b >= a && (uint64_t) b <= lens[j];
-                    vals[j * k + f] = (hit || sink->mode == 2) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
-                    starts[j * k + f] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
+            /* what sre_k_extract_select writes, from the records the host holds: the entry table of the groups, and for
+             * the tally's sums the value table of the value groups */
+            for (int pass = 0; pass < (sink->vgroups ? 2 : 1); pass++) {
+                const sre_extract_groups_t *gr = pass ? sink->vgroups : sink->groups;
+                std::vector<uint64_t>      &ev = pass ? vvals : vals, &es = pass ? vstarts : starts;
+                const uint32_t              k = gr->k;
+                ev.resize(nb * k);
+                es.resize(nb * k);
+                for (uint64_t j = 0; j < nb; j++) {
+                    const sre_int_t *rec = recs.data() + j * slots;
+                    const bool       hit = rec[0] != SRE_DECLINED;
+                    const uint64_t   st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf);
+                    for (uint32_t f = 0; f < k; f++) {
+                        const uint32_t  g = gr->g[f];
+                        const sre_int_t a = hit ? rec[2 + 2 * g] : -1, b = hit ? rec[3 + 2 * g] : -1;
+                        const bool      set = a >= 0 && b >= a && (uint64_t) b <= lens[j];
+                        ev[j * k + f] = (hit || sink->mode == 2) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
+                        es[j * k + f] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
                                         | (f + 1 == k ? SRE_LG_ENTRY_LAST : 0);
+                    }
                 }
+                SRE_HIP_TRY(hipMemcpyAsync((pass ? sink->d_vval : sink->d_val) + i0 * k, ev.data(), nb * k * sizeof(uint64_t),
+                                           hipMemcpyHostToDevice, stream));
+                SRE_HIP_TRY(hipMemcpyAsync((pass ? sink->d_vstart : sink->d_start) + i0 * k, es.data(), nb * k * sizeof(uint64_t),
+                                           hipMemcpyHostToDevice, stream));
             }
-            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0 * k, vals.data(), nb * k * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            SRE_HIP_TRY(hipMemcpyAsync(sink->d_start + i0 * k, starts.data(), nb * k * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                       stream));
             SRE_HIP_TRY(hipStreamSynchronize(stream));
         } else if (sink && sink->h_map) {
             /* what sre_k_route_select writes, from the records the host holds */
@@ -2100,6 +2126,13 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
             if (sink->groups || sink->pieces) {
                 if (lines_grow(&sc->d_fstart, &sc->fstart_cap, n * k * sizeof(uint64_t)) != 0) goto hip_failed;
                 sink->d_start = sc->d_fstart;
+            }
+            if (sink->vgroups) {
+                const uint64_t v = sink->vgroups->k;
+                if (lines_grow(&sc->d_vval, &sc->vval_cap, n * v * sizeof(uint64_t)) != 0) goto hip_failed;
+                if (lines_grow(&sc->d_vstart, &sc->vstart_cap, n * v * sizeof(uint64_t)) != 0) goto hip_failed;
+                sink->d_vval = sc->d_vval;
+                sink->d_vstart = sc->d_vstart;
             }
         }
         rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink)
@@ -2323,13 +2356,28 @@ tally_hash_mask(void)
     return sre_lt_hash_mask(atoi(e));
 }
 
+/* the copies of the aggregates the sums' waves spread their atomics over: the rule's (sre_ls_copies), or at most
+ * SRE_HIP_TALLY_SUM_COPIES of them (test knob, read on every call; 1: the caller's rows themselves) */
+static uint32_t
+tally_sum_copies(uint64_t rows, uint32_t v)
+{
+    const uint32_t copies = sre_ls_copies(rows, v);
+    const char    *e = getenv("SRE_HIP_TALLY_SUM_COPIES");
+    if (e == NULL || *e == 0) return copies;
+    const int most = atoi(e);
+    return most < 1 ? 1 : (uint32_t) most < copies ? (uint32_t) most : copies;
+}
+
 /* The line tally: the extract's call up to its select passes, then on the device the insert of every
  * selected line into the table of keys and the keep pass that leaves the first line of every key selected, then the
- * extract's scan, cut, one read (its four words and the tally's three), gather and index, and the ranks. */
-extern "C" SRE_API int
-sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups, int fsep,
-    int flags, size_t max_keys, void *d_out, size_t out_cap, uint64_t *d_counts, size_t counts_cap, sre_int_t *d_keyid,
-    size_t keyid_cap, sre_int_t *d_index, size_t index_cap, sre_hip_tally_info_t *info, void *hip_stream)
+ * extract's scan, cut, one read (its four words and the tally's three), gather and index, and the ranks.
+ * With value groups (sre_hip_tally_sums_lines; vgroups == NULL: the plain tally) every batch also
+ * fills the value table, and the sums kernel is queued behind the ranks, in front of the last wait. */
+static int
+tally_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups, const int *vgroups,
+    size_t nvgroups, int fsep, int flags, size_t max_keys, void *d_out, size_t out_cap, uint64_t *d_counts, size_t counts_cap,
+    sre_hip_tally_sum_t *d_sums, size_t sums_cap, sre_int_t *d_keyid, size_t keyid_cap, sre_int_t *d_index, size_t index_cap,
+    sre_hip_tally_info_t *info, void *hip_stream)
 {
     if (sc == NULL || delim < 0 || delim > 255 || fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0
         || groups == NULL || ngroups < 1 || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (out_cap != 0 && d_out == NULL)
@@ -2342,13 +2390,19 @@ sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
         fprintf(stderr, "[sregex-hip] line tally: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
         return -1;
     }
-    sre_extract_groups_t gr;
+    sre_extract_groups_t gr, vg;
     memset(&gr, 0, sizeof(gr));
     gr.k = (uint32_t) ngroups;
     for (size_t f = 0; f < ngroups; f++) {
         /* ovec_slots = 2 * (max_ncaps + 1) */
         if (groups[f] < 0 || groups[f] > 0xFFFF || 2 * (size_t) groups[f] + 1 >= (size_t) sc->ovec_slots) return -1;
         gr.g[f] = (uint16_t) groups[f];
+    }
+    memset(&vg, 0, sizeof(vg));
+    vg.k = (uint32_t) nvgroups;
+    for (size_t c = 0; c < nvgroups; c++) {
+        if (vgroups[c] < 0 || vgroups[c] > 0xFFFF || 2 * (size_t) vgroups[c] + 1 >= (size_t) sc->ovec_slots) return -1;
+        vg.g[c] = (uint16_t) vgroups[c];
     }
     if (len != 0 && out_cap != 0) {
         /* the output may not overlap the buffer */
@@ -2358,6 +2412,7 @@ sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, &gr, NULL};
     uint64_t    n = 0, nrep = 0;
+    if (vgroups) sink.vgroups = &vg;
     if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
     sre_hip_tally_info_t res;
     memset(&res, 0, sizeof(res));
@@ -2398,6 +2453,17 @@ sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
             }
             SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, gr.k, sc->d_fblk, sc->d_tslot, cnt, d_counts, counts_cap,
                                                reinterpret_cast<int64_t *>(d_keyid), keyid_cap, stream));
+            if (vgroups && sums_cap != 0) {
+                /* (without counts and key ids the ranks above launched nothing: the key numbers are still needed) */
+                if (counts_cap == 0 && keyid_cap == 0) {
+                    SRE_HIP_TRY(sre_launch_tally_numbers(sc->d_fval, sc->d_fstart, n, gr.k, sc->d_fblk, sc->d_tslot, cnt, stream));
+                }
+                const uint64_t rows = sums_cap < res.nkeys ? sums_cap : res.nkeys;
+                const uint32_t copies = tally_sum_copies(rows, vg.k);
+                if (copies > 1 && lines_grow(&sc->d_vcopy, &sc->vcopy_cap, copies * rows * vg.k * sizeof(sre_ls_agg_t)) != 0) return -1;
+                SRE_HIP_TRY(sre_launch_tally_sums(d_buf, sc->d_vval, sc->d_vstart, n, vg.k, sc->d_tslot, cnt, rows, d_sums,
+                                                  sc->d_vcopy, copies, stream));
+            }
             SRE_HIP_TRY(hipStreamSynchronize(stream));
         }
     }
@@ -2405,6 +2471,48 @@ sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
     return rc;
 hip_failed:
     return -1;
+}
+
+extern "C" SRE_API int
+sre_hip_tally_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups, int fsep,
+    int flags, size_t max_keys, void *d_out, size_t out_cap, uint64_t *d_counts, size_t counts_cap, sre_int_t *d_keyid,
+    size_t keyid_cap, sre_int_t *d_index, size_t index_cap, sre_hip_tally_info_t *info, void *hip_stream)
+{
+    return tally_call(sc, d_buf, len, delim, groups, ngroups, NULL, 0, fsep, flags, max_keys, d_out, out_cap, d_counts, counts_cap,
+                      NULL, 0, d_keyid, keyid_cap, d_index, index_cap, info, hip_stream);
+}
+
+extern "C" SRE_API int
+sre_hip_tally_sums_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+    const int *vgroups, size_t nvgroups, int fsep, int flags, size_t max_keys, void *d_out, size_t out_cap, uint64_t *d_counts,
+    size_t counts_cap, sre_hip_tally_sum_t *d_sums, size_t sums_cap, sre_int_t *d_keyid, size_t keyid_cap, sre_int_t *d_index,
+    size_t index_cap, sre_hip_tally_info_t *info, void *hip_stream)
+{
+    static_assert(sizeof(sre_hip_tally_sum_t) == sizeof(sre_ls_agg_t) && SRE_HIP_TALLY_MAX_VALUES == SRE_LS_MAX_VALUES,
+                  "sre_lines_sums.h mirrors the public aggregate");
+    if (vgroups == NULL || nvgroups < 1 || nvgroups > SRE_HIP_TALLY_MAX_VALUES || (sums_cap != 0 && d_sums == NULL)
+        || (reinterpret_cast<uintptr_t>(d_sums) & 7u) != 0)
+    {
+        return -1;
+    }
+    return tally_call(sc, d_buf, len, delim, groups, ngroups, vgroups, nvgroups, fsep, flags, max_keys, d_out, out_cap, d_counts,
+                      counts_cap, d_sums, sums_cap, d_keyid, keyid_cap, d_index, index_cap, info, hip_stream);
+}
+
+/* the number rule of the tally's sums on the host (sre_lines_sums.h) */
+namespace {
+struct HostText {
+    const uint8_t *p;
+    uint8_t byte(uint64_t at) const { return p[at]; }
+};
+}  // namespace
+
+extern "C" SRE_API int
+sre_hip_tally_number(const void *text, size_t len, int64_t *value)
+{
+    if (value == NULL || (len != 0 && text == NULL)) return 0;
+    const HostText t = {static_cast<const uint8_t *>(text)};
+    return sre_ls_number(t, 0, len, value) ? 1 : 0;
 }
 
 /* The template of the line substitute: the pieces in order, the literal bytes of all literal pieces back to back in

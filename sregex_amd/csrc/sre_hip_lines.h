@@ -220,6 +220,20 @@ hipError_t sre_launch_tally_insert(const void *d_buf, uint64_t *d_val, const uin
 hipError_t sre_launch_tally_ranks(const uint64_t *d_off, const uint64_t *d_start, uint64_t n, uint32_t k, const uint64_t *d_blk,
     const uint32_t *d_lslot, uint64_t *d_cnt, uint64_t *d_counts, uint64_t counts_cap, int64_t *d_keyid, uint64_t keyid_cap,
     hipStream_t stream);
+/* ---- the tally's sums (sre_hip_lines_tally.hip, sre_lines_sums.h) ---- */
+/* the first kernel of sre_launch_tally_ranks alone, for a call that asks for neither counts nor key ids: d_cnt[slot]
+ * becomes the number of the slot's key */
+hipError_t sre_launch_tally_numbers(const uint64_t *d_off, const uint64_t *d_start, uint64_t n, uint32_t k, const uint64_t *d_blk,
+    const uint32_t *d_lslot, uint64_t *d_cnt, hipStream_t stream);
+/* behind either: rows 0 .. rows of d_sums (sre_hip_tally_sum_t, v aggregates a row, 8-byte aligned) are set to
+ * {0, INT64_MAX, INT64_MIN, 0}; then, a lane per line, the numbers of the line's v value fields (d_vval / d_vstart: the
+ * entry table of sre_launch_extract_select over the value groups, n * v entries) join the aggregates of row
+ * d_cnt[d_lslot[line]] when that is below rows.  A wave sends one add, minimum, maximum and add per key and column.
+ * With copies > 1 (sre_ls_copies) all of this happens in d_copies, copies x rows x v aggregates, wave w in copy
+ * w % copies, and a last kernel merges the copies into d_sums */
+hipError_t sre_launch_tally_sums(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, uint32_t v,
+    const uint32_t *d_lslot, const uint64_t *d_cnt, uint64_t rows, void *d_sums, void *d_copies, uint32_t copies,
+    hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,14 @@
  *              count's place;
  *   keyid      a lane per line: the number found through the line's slot.
  *
+ * The tally with sums (sre_hip_tally_sums_lines, DESIGN.md §4.11.8, rules in sre_lines_sums.h) adds behind the ranks
+ *   sums       a lane per line: the key number through the slot, the line's numbers through the value table; the wave
+ *              groups its lanes by key number, merges the members' numbers across the lanes and sends one add, minimum,
+ *              maximum and add per key and column of the wave, to the wave's COPY of the rows (a hot row would otherwise
+ *              take the atomics of every wave on one cache line).  Every access to the aggregates is an atomic at agent
+ *              scope; the copies were set to the identity by a kernel in front, and a kernel behind merges them into the
+ *              caller's rows.
+ *
  * Inside the insert every access to the table, the counts and the three info words is an atomic at agent scope: the
  * L2s of the eight XCDs do not see one another's plain stores within a kernel.  The later kernels read all of it with
  * plain loads, behind the kernel boundary.  No workgroup waits for another.  Plain C++ and vector memory operations only.
@@ -22,6 +30,7 @@
 #include <sregex/sregex.h>
 #include "sre_hip_lines.h"
 #include "sre_lines_tally.h"
+#include "sre_lines_sums.h"
 #include "sre_hip_lines_block.h"
 
 namespace {
@@ -150,6 +159,113 @@ sre_k_tally_keyid(const uint32_t *__restrict__ lslot, const uint64_t *__restrict
     keyid[i] = slot == SRE_LT_NONE ? -1 : (int64_t) cnt[slot];
 }
 
+/* ---- the sums (sre_lines_sums.h) ---- */
+
+/* the value table as the sums kernel reads it (written by earlier kernels or copies: plain loads) */
+struct SumVals {
+    const uint8_t  *buf;
+    const uint64_t *vval, *vstart;
+    uint32_t        v;
+    __device__ inline uint64_t val(uint64_t line, uint32_t c) const { return vval[line * v + c]; }
+    __device__ inline uint64_t raw(uint64_t line, uint32_t c) const { return vstart[line * v + c]; }
+    __device__ inline uint8_t  byte(uint64_t at) const { return buf[at]; }
+};
+
+struct SumMem {
+    sre_ls_agg_t *sums;
+    __device__ inline void add_sum(uint64_t idx, int64_t v)
+    {
+        (void) __hip_atomic_fetch_add(reinterpret_cast<uint64_t *>(&sums[idx].sum), (uint64_t) v, LT_RELAXED_AGENT);
+    }
+    __device__ inline void min(uint64_t idx, int64_t v) { (void) __hip_atomic_fetch_min(&sums[idx].min, v, LT_RELAXED_AGENT); }
+    __device__ inline void max(uint64_t idx, int64_t v) { (void) __hip_atomic_fetch_max(&sums[idx].max, v, LT_RELAXED_AGENT); }
+    __device__ inline void add_n(uint64_t idx, uint64_t v) { (void) __hip_atomic_fetch_add(&sums[idx].n, v, LT_RELAXED_AGENT); }
+};
+
+__device__ inline uint64_t
+wave_get(uint64_t v, uint32_t lane)
+{
+    return (uint64_t) __shfl((unsigned long long) v, (int) lane, 64);
+}
+
+/* every lane gets the merge of all 64 lanes' aggregates */
+__device__ inline sre_ls_agg_t
+wave_merge(sre_ls_agg_t g)
+{
+    for (int d = 1; d < 64; d <<= 1) {
+        sre_ls_agg_t o;
+        o.sum = (int64_t) __shfl_xor((long long) g.sum, d, 64);
+        o.min = (int64_t) __shfl_xor((long long) g.min, d, 64);
+        o.max = (int64_t) __shfl_xor((long long) g.max, d, 64);
+        o.n = (uint64_t) __shfl_xor((unsigned long long) g.n, d, 64);
+        g = sre_ls_merge(g, o);
+    }
+    return g;
+}
+
+/* lane per aggregate */
+__global__ __launch_bounds__(256) void
+sre_k_tally_sums_init(sre_ls_agg_t *__restrict__ sums, uint64_t count)
+{
+    const uint64_t x = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (x < count) sums[x] = sre_ls_identity();
+}
+
+/* lane per aggregate, behind the sums: the caller's aggregate is the merge of its copies (plain loads and a plain store,
+ * behind the kernel boundary) */
+__global__ __launch_bounds__(256) void
+sre_k_tally_sums_merge(const sre_ls_agg_t *__restrict__ copy, uint32_t copies, uint64_t count, sre_ls_agg_t *__restrict__ sums)
+{
+    const uint64_t x = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (x >= count) return;
+    sre_ls_agg_t a = sre_ls_identity();
+    for (uint32_t c = 0; c < copies; c++) a = sre_ls_merge(a, copy[(uint64_t) c * count + x]);
+    sums[x] = a;
+}
+
+/* lane per line, behind the ranks: cnt[slot] is the key number.  tests/lines_sums_sim.cpp re-types this kernel's grouping
+ * loop, its alone / shared split and its merge lane by lane; only sre_lines_sums.h is common text, so a change here has to
+ * be made there too, or the model's atomic counts no longer speak for the kernel */
+__global__ __launch_bounds__(SRE_LS_THREADS) void
+sre_k_tally_sums(const uint8_t *__restrict__ buf, const uint64_t *__restrict__ vval, const uint64_t *__restrict__ vstart,
+                 uint64_t n, uint32_t v, const uint32_t *__restrict__ lslot, const uint64_t *__restrict__ cnt, uint64_t rows,
+                 uint32_t copies, sre_ls_agg_t *sums)
+{
+    const uint64_t i = (uint64_t) blockIdx.x * SRE_LS_THREADS + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const SumVals  vals = {buf, vval, vstart, v};
+    /* the wave's copy of the rows */
+    SumMem         mem = {sums + (uint64_t) sre_ls_copy_of(i / 64u, copies) * rows * v};
+    const uint32_t slot = i < n ? lslot[i] : SRE_LT_NONE;
+    const uint64_t key = slot != SRE_LT_NONE ? cnt[slot] : 0;
+    const bool     part = sre_ls_takes_part(slot, key, rows);
+    /* the wave's groups: a turn per distinct key number of its lanes; every member keeps the group's ballot */
+    uint64_t rem = __ballot(part), members = 0;
+    while (rem) {
+        const uint32_t lead = sre_lr_leader(rem);
+        const uint64_t lk = wave_get(key, lead);
+        const bool     mine = ((rem >> lane) & 1u) != 0 && key == lk;
+        const uint64_t m = __ballot(mine);
+        if (mine) members = m;
+        rem &= ~m;
+    }
+    const bool     alone = part && sre_lr_popc(members) == 1;
+    /* the leaders of the groups of more than one lane */
+    const uint64_t shared = __ballot(part && !alone && sre_lr_leader(members) == lane);
+    for (uint32_t c = 0; c < v; c++) {
+        const sre_ls_agg_t a = part ? sre_ls_line(vals, i, c) : sre_ls_identity();
+        const uint64_t     idx = sre_ls_index(key, v, c);
+        if (alone) sre_ls_flush(mem, idx, a);
+        for (uint64_t todo = shared; todo; todo &= todo - 1) {
+            const uint32_t lead = sre_lr_leader(todo);
+            const bool     in = ((wave_get(members, lead) >> lane) & 1u) != 0;
+            if (__ballot(in && a.n != 0) == 0) continue;            /* no number in the group: nothing is sent */
+            const sre_ls_agg_t g = wave_merge(in ? a : sre_ls_identity());
+            if (lane == lead) sre_ls_flush(mem, idx, g);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" hipError_t
@@ -190,6 +306,43 @@ sre_launch_tally_ranks(const uint64_t *d_off, const uint64_t *d_start, uint64_t 
     if (keyid_cap != 0) {
         const uint64_t m = keyid_cap < n ? keyid_cap : n;
         hipLaunchKernelGGL(sre_k_tally_keyid, dim3((uint32_t) ((m + 255) / 256)), dim3(256), 0, stream, d_lslot, d_cnt, m, d_keyid);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_tally_numbers(const uint64_t *d_off, const uint64_t *d_start, uint64_t n, uint32_t k, const uint64_t *d_blk,
+                         const uint32_t *d_lslot, uint64_t *d_cnt, hipStream_t stream)
+{
+    if (n == 0 || k == 0) return hipErrorInvalidValue;
+    const uint64_t nent = n * k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    if (nblk > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_tally_ranks, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_start, nent, (uint64_t) k,
+                       d_blk + nblk, d_lslot, d_cnt, static_cast<uint64_t *>(nullptr), (uint64_t) 0);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_tally_sums(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, uint32_t v,
+                      const uint32_t *d_lslot, const uint64_t *d_cnt, uint64_t rows, void *d_sums, void *d_copies, uint32_t copies,
+                      hipStream_t stream)
+{
+    if (n == 0 || v == 0 || v > SRE_LS_MAX_VALUES || rows > SRE_LT_MAX_KEYS || copies == 0 || copies > SRE_LS_MAX_COPIES
+        || (copies > 1 && d_copies == NULL))
+    {
+        return hipErrorInvalidValue;
+    }
+    if (rows == 0) return hipSuccess;
+    const uint64_t nwg = (n + SRE_LS_THREADS - 1) / SRE_LS_THREADS, count = rows * v, all = count * copies;
+    if (nwg > 0x7FFFFFFFull || (all + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    sre_ls_agg_t *sums = static_cast<sre_ls_agg_t *>(d_sums);
+    sre_ls_agg_t *to = copies > 1 ? static_cast<sre_ls_agg_t *>(d_copies) : sums;
+    hipLaunchKernelGGL(sre_k_tally_sums_init, dim3((uint32_t) ((all + 255) / 256)), dim3(256), 0, stream, to, all);
+    hipLaunchKernelGGL(sre_k_tally_sums, dim3((uint32_t) nwg), dim3(SRE_LS_THREADS), 0, stream, static_cast<const uint8_t *>(d_buf),
+                       d_vval, d_vstart, n, v, d_lslot, d_cnt, rows, copies, to);
+    if (copies > 1) {
+        hipLaunchKernelGGL(sre_k_tally_sums_merge, dim3((uint32_t) ((count + 255) / 256)), dim3(256), 0, stream, to, copies, count,
+                           sums);
     }
     return hipGetLastError();
 }
