@@ -26,11 +26,13 @@
 #include "sre_lines_sums.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <vector>
 
 /* speculative fix-up rounds before a FIRST / Thompson scan computes exact entry states */
@@ -1459,14 +1461,32 @@ hip_failed:
     return -1;
 }
 
+/* a host read of the device words of a line-mode call, queued: the run of sre_lines_info_t that holds every word named,
+ * whatever the order of the struct, so a word added or moved changes how much is copied and never which words arrive */
+typedef uint64_t sre_lines_info_t::*LinfoWord;
+#define LINFO(word) (&sre_lines_info_t::word)
+
+static hipError_t
+linfo_read(sre_hip_scanner_t *sc, hipStream_t stream, std::initializer_list<LinfoWord> words)
+{
+    const char *base = reinterpret_cast<const char *>(sc->h_linfo);
+    size_t      lo = sizeof(sre_lines_info_t), hi = 0;
+    for (LinfoWord w : words) {
+        const size_t at = (size_t) (reinterpret_cast<const char *>(&(sc->h_linfo->*w)) - base);
+        lo = at < lo ? at : lo;
+        hi = at + sizeof(uint64_t) > hi ? at + sizeof(uint64_t) : hi;
+    }
+    return hipMemcpyAsync(reinterpret_cast<char *>(sc->h_linfo) + lo, reinterpret_cast<const char *>(sc->d_linfo) + lo, hi - lo,
+                          hipMemcpyDeviceToHost, stream);
+}
+
 /* line mode: the batch's status words reduced on the device to h_linfo->pending (streams not
  * done) and h_linfo->maps (streams with need_maps); the host reads 16 bytes */
 static int
 lines_status_counters(sre_hip_scanner_t *sc, size_t n, hipStream_t stream)
 {
     SRE_HIP_TRY(sre_launch_lines_settle(sc->d_status, (uint32_t) n, sc->d_linfo, stream));
-    SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->pending, &sc->d_linfo->pending, 2 * sizeof(uint64_t),
-                               hipMemcpyDeviceToHost, stream));
+    SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(pending), LINFO(maps)}));
     SRE_HIP_TRY(hipStreamSynchronize(stream));
     return 0;
 hip_failed:
@@ -1696,55 +1716,106 @@ hip_failed:
     return -1;
 }
 
-/* the line filter's sink (sre_hip_filter_lines): with one, a batch ends with the select pass into d_val in place of
- * the compaction of its rows, and no row goes to the host (out / cap are NULL / 0 then) */
+/* a sink of a line-mode call: with one, a batch ends with the sink's select pass into the scanner's table (d_fval, one
+ * word per entry, and d_fstart) in place of the compaction, and no row goes to the host (out / cap are NULL / 0 then) */
 struct LinesSink {
-    int       mode;     /* 0: the lines with a match, 1: the lines without one, 2: every line */
-    uint64_t *d_val;    /* one word per line of the call */
-    /* the line extract (sre_hip_extract_lines): with groups, the select pass is the extract's over the entries
-     * line * k + field, d_val has one word per entry and d_start the entries' source offsets; mode is 0 or 2 */
+    int        delim;
+    void      *d_out;       /* the caller's output: out_cap bytes that do not overlap the buffer */
+    size_t     out_cap;
+    sre_int_t *d_index;     /* ... and room for index_cap index rows */
+    size_t     index_cap;
+    int        mode;        /* the row rule (sre_sel_row): 0 the lines with a match, 1 the lines without one, 2 every line */
+    /* the extract and the tally: the entries line * k + field, fsep between the fields of a row; mode is 0 or 2 */
     const sre_extract_groups_t *groups;
-    uint64_t                   *d_start;
-    /* the line substitute (sre_hip_substitute_lines): with pieces, the select pass is the substitute's over the entries
-     * line * (np + 2) + piece, into d_val and d_start as above; mode is 0 or 2 */
+    int                         fsep;
+    /* the substitute: the entries line * (np + 2) + piece; mode is 0 or 2 */
     const sre_subst_pieces_t   *pieces;
-    /* the line route (sre_hip_route_lines): with a map, the select pass writes the route's keys into d_val, one word
-     * per line; h_map / d_map: the nreg + 1 buckets of the call on the host and on the device; mode is unused */
-    const int32_t              *h_map, *d_map;
+    /* the route: a key per line by the scanner's map of nreg + 1 buckets (h_rmap / d_rmap); mode is unused */
+    bool                        route;
     uint32_t                    nreg;
-    /* the tally's sums (sre_hip_tally_sums_lines): with value groups (and groups), the extract's select pass runs a
-     * second time over the entries line * v + column into d_vval and d_vstart; the key table is untouched by it */
+    /* the tally's sums: the extract's select pass runs a second time over the entries line * v + column of the value
+     * groups into d_vval and d_vstart; the key table is untouched by it */
     const sre_extract_groups_t *vgroups;
-    uint64_t                   *d_vval, *d_vstart;
+    /* the filter with context: index rows of five words; d_cbits marks the context-only lines (NULL: no line is one) */
+    bool                        context;
+    const uint64_t             *d_cbits;
 };
 
+/* the arguments every sink call shares: false unless they are in range, the pointers stand for their sizes and the output
+ * does not overlap the buffer; else the sink that describes them (of the caller's checked flags, the row rule) */
+static bool
+sink_open(LinesSink *sink, const sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, void *d_out,
+          size_t out_cap, sre_int_t *d_index, size_t index_cap)
+{
+    if (sc == NULL || delim < 0 || delim > 255 || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL)
+        || (len != 0 && d_buf == NULL))
+    {
+        return false;
+    }
+    if (len != 0 && out_cap != 0) {
+        /* the output may not overlap the buffer */
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (o < b + len && b < o + out_cap) return false;
+    }
+    *sink = LinesSink();
+    sink->delim = sink->fsep = delim;
+    sink->mode = (flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0;
+    sink->d_out = d_out;
+    sink->out_cap = out_cap;
+    sink->d_index = d_index;
+    sink->index_cap = index_cap;
+    return true;
+}
+
+/* the sinks that read the first match's record refuse every other mode, by name */
+static bool
+sink_first_match(const sre_hip_scanner_t *sc, const char *call, const char *reads)
+{
+    if (sc->mode == SRE_HIP_PIKE_FIRST) return true;
+    fprintf(stderr, "[sregex-hip] %s: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's %s)\n", call, reads);
+    return false;
+}
+
+/* a list of capture groups packed for the select pass; false: one of them is not a group of the program */
+static bool
+sink_groups(const sre_hip_scanner_t *sc, const int *groups, size_t ngroups, sre_extract_groups_t *gr)
+{
+    memset(gr, 0, sizeof(*gr));
+    gr->k = (uint32_t) ngroups;
+    for (size_t f = 0; f < ngroups; f++) {
+        /* ovec_slots = 2 * (max_ncaps + 1) */
+        if (groups[f] < 0 || groups[f] > 0xFFFF || 2 * (size_t) groups[f] + 1 >= (size_t) sc->ovec_slots) return false;
+        gr->g[f] = (uint16_t) groups[f];
+    }
+    return true;
+}
+
 /* entries per line of the sink's table */
-static uint64_t
+static uint32_t
 sink_entries(const LinesSink *sink)
 {
     return sink->pieces ? sink->pieces->np + 2 : sink->groups ? sink->groups->k : 1;
 }
 
-static bool
-sink_selects(const LinesSink *sink, sre_int_t rc)
-{
-    return sink->mode == 2 || (rc != SRE_DECLINED) != (sink->mode == 1);
-}
-
 /* the select pass of a device batch (lines i0 .. d_linfo->i1, at most nmax) from its records */
-static hipError_t
-sink_select(sre_hip_scanner_t *sc, const LinesSink *sink, size_t slots, uint64_t nmax, uint64_t i0, hipStream_t stream)
+static int
+sink_select(sre_hip_scanner_t *sc, const LinesSink *sink, uint32_t slots, uint64_t nmax, uint64_t i0, hipStream_t stream)
 {
-    if (sink->pieces) {
-        return sre_launch_subst_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->pieces, sc->d_ends,
-                                       sc->d_linfo, sink->d_val, sink->d_start, stream);
+    const int64_t          *recs = sc->d_records;
+    const uint64_t         *ends = sc->d_ends;
+    const sre_lines_info_t *li = sc->d_linfo;
+    uint64_t               *val = sc->d_fval, *start = sc->d_fstart;
+    const int               all = sink->mode == 2;
+    if (sink->route) SRE_HIP_TRY(sre_launch_route_select(recs, slots, nmax, i0, sink->nreg, sc->d_rmap, ends, li, val, stream));
+    else if (sink->pieces) SRE_HIP_TRY(sre_launch_subst_select(recs, slots, nmax, i0, all, sink->pieces, ends, li, val, start, stream));
+    else if (sink->groups) SRE_HIP_TRY(sre_launch_extract_select(recs, slots, nmax, i0, all, sink->groups, ends, li, val, start, stream));
+    else SRE_HIP_TRY(sre_launch_filter_select(recs, slots, nmax, i0, sink->mode, ends, li, val, stream));
+    if (sink->vgroups) {
+        SRE_HIP_TRY(sre_launch_extract_select(recs, slots, nmax, i0, all, sink->vgroups, ends, li, sc->d_vval, sc->d_vstart, stream));
     }
-    if (sink->groups) {
-        return sre_launch_extract_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->groups, sc->d_ends,
-                                         sc->d_linfo, sink->d_val, sink->d_start, stream);
-    }
-    return sre_launch_filter_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode, sc->d_ends, sc->d_linfo, sink->d_val,
-                                    stream);
+    return 0;
+hip_failed:
+    return -1;
 }
 
 /* what a line-mode call sums over its batches (lines_call publishes it) */
@@ -1772,19 +1843,12 @@ static int
 lines_device_batch_end(sre_hip_scanner_t *sc, LinesTotals *tot, const LinesSink *sink, uint64_t nmax, uint64_t i0, int all,
                        uint64_t rcap, hipStream_t stream)
 {
-    const size_t slots = 2 + (size_t) sc->ovec_slots;
-    if (sink && sink->h_map) {
-        SRE_HIP_TRY(sre_launch_route_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->nreg, sink->d_map, sc->d_ends,
-                                            sc->d_linfo, sink->d_val, stream));
-    } else if (sink) {
-        SRE_HIP_TRY(sink_select(sc, sink, slots, nmax, i0, stream));
-        if (sink->vgroups) {
-            SRE_HIP_TRY(sre_launch_extract_select(sc->d_records, (uint32_t) slots, nmax, i0, sink->mode == 2, sink->vgroups,
-                                                  sc->d_ends, sc->d_linfo, sink->d_vval, sink->d_vstart, stream));
-        }
+    const uint32_t slots = 2 + sc->ovec_slots;
+    if (sink) {
+        if (sink_select(sc, sink, slots, nmax, i0, stream) != 0) return -1;
     } else {
-        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, (uint32_t) slots, nmax, i0, all, sc->d_ends, sc->d_lblk,
-                                             sc->d_linfo, sc->d_rows, rcap, stream));
+        SRE_HIP_TRY(sre_launch_lines_compact(sc->d_records, slots, nmax, i0, all, sc->d_ends, sc->d_lblk, sc->d_linfo, sc->d_rows,
+                                             rcap, stream));
     }
     tot->fixups += sc->fixup_rounds;
     tot->exact += sc->exact_passes;
@@ -1835,7 +1899,7 @@ lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all,
         SRE_HIP_TRY(sre_launch_lines_geometry(d_buf, sc->d_ends, n, i0, nmax, SRE_LINES_WALK_MAX, seg_fixed, resident,
                                               scan_seg_cap(sc), reinterpret_cast<const uint8_t **>(sc->d_ptrs), sc->d_lens,
                                               sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(i1), LINFO(seg), LINFO(nsegs)}));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
         const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
         call_begin(sc);         /* (to the diagnostics a batch is a call: tot sums them) */
@@ -1916,7 +1980,7 @@ lines_scan_nfa(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, sr
         SRE_HIP_TRY(sre_launch_lines_geometry_nfa(d_buf, sc->d_ends, n, i0, nmax, short_lim, SRE_LINES_NFA_WORK_MAX, seg_cost,
                                                   seg_fixed, resident, scan_seg_cap(sc), reinterpret_cast<const uint8_t **>(sc->d_ptrs),
                                                   sc->d_lens, sc->d_seg_first, sc->d_lblk, sc->d_linfo, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->i1, &sc->d_linfo->i1, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(i1), LINFO(seg), LINFO(nsegs)}));
         SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->nshort, &sc->d_linfo->nshort, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
         const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
@@ -1975,9 +2039,7 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
     std::vector<const void *> ptrs;
     std::vector<size_t>       lens;
     std::vector<sre_int_t>    recs;
-    std::vector<uint64_t>     vals;             /* with a sink: the batch's per-line values, uploaded */
-    std::vector<uint64_t>     starts;           /* ... of the line extract: and the per-entry source offsets */
-    std::vector<uint64_t>     vvals, vstarts;   /* ... of the tally's sums: and the same of the value table */
+    std::vector<uint64_t>     vals, starts;     /* with a sink: the words of the batch's entries, uploaded */
     uint64_t                  nrep = 0;
     for (uint64_t i0 = 0; i0 < n;) {
         const uint64_t nb = bmax < n - i0 ? bmax : n - i0;
@@ -2003,85 +2065,34 @@ lines_scan_host(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all, s
         tot->lineage += sc->lineage_passes;
         const double ms = sre_hip_scanner_last_kernel_ms(sc);
         tot->kms = (ms < 0 || tot->kms < 0) ? -1.0 : tot->kms + ms;
-        if (sink && sink->pieces) {
-            /* what sre_k_subst_select writes, from the records the host holds */
-            const sre_subst_pieces_t *pc = sink->pieces;
-            const uint32_t            P = pc->np + 2;
-            vals.resize(nb * P);
-            starts.resize(nb * P);
-            for (uint64_t j = 0; j < nb; j++) {
+        /* with a sink, what its select pass writes, by the rules the kernels compile: the sink's table, then the sums' */
+        for (int pass = 0; sink && pass < (sink->vgroups ? 2 : 1); pass++) {
+            const sre_subst_pieces_t   *pc = pass ? NULL : sink->pieces;
+            const sre_extract_groups_t *gr = pass ? sink->vgroups : sink->groups;
+            const uint32_t              k = pc ? pc->np + 2 : gr ? gr->k : 1;
+            const int                   smode = sink->mode, all_rows = smode == 2;
+            vals.resize(nb * k);
+            starts.resize(nb * k);
+            for (uint64_t e = 0; e < nb * k; e++) {
+                const uint64_t   j = e / k, st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf), len = lens[j];
+                const uint32_t   f = (uint32_t) (e % k);
                 const sre_int_t *rec = recs.data() + j * slots;
-                const bool       hit = rec[0] != SRE_DECLINED, sel = hit || sink->mode == 2;
-                const uint64_t   st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf), len = lens[j];
-                const sre_int_t  m0 = hit ? rec[2] : -1, m1 = hit ? rec[3] : -1;
-                const bool       ok = m0 >= 0 && m1 >= m0 && (uint64_t) m1 <= len;
-                uint64_t        *v = vals.data() + j * P, *w = starts.data() + j * P;
-                v[0] = ok ? (uint64_t) m0 : len;
-                w[0] = st | SRE_LG_ENTRY_FIRST | (ok ? 0 : SRE_LG_ENTRY_UNSET);
-                for (uint32_t q = 0; q < pc->np; q++) {
-                    if (pc->g[q] < 0) {
-                        v[1 + q] = ok ? pc->len[q] : 0;
-                        w[1 + q] = (uint64_t) pc->off[q] | SRE_LG_ENTRY_LITERAL;
-                    } else {
-                        const sre_int_t a = ok ? rec[2 + 2 * pc->g[q]] : -1, b = ok ? rec[3 + 2 * pc->g[q]] : -1;
-                        const bool      set = a >= 0 && b >= a && (uint64_t) b <= len;
-                        v[1 + q] = set ? (uint64_t) (b - a) : 0;
-                        w[1 + q] = set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET;
-                    }
-                }
-                v[P - 1] = (ok ? len - (uint64_t) m1 : 0) + 1;
-                w[P - 1] = (ok ? st + (uint64_t) m1 : st + len) | SRE_LG_ENTRY_LAST;
-                for (uint32_t f = 0; !sel && f < P; f++) v[f] = 0;
+                if (pc) sre_sel_subst_entry(rec, SRE_DECLINED, all_rows, st, len, f, pc, &vals[e], &starts[e]);
+                else if (gr) sre_sel_extract_entry(rec, SRE_DECLINED, all_rows, st, len, f, k, gr->g[f], &vals[e], &starts[e]);
+                else if (sink->route) vals[e] = sre_lr_key(sre_lr_bucket(rec[0], SRE_DECLINED, sink->nreg, sc->h_rmap), len);
+                else vals[e] = sre_sel_row(rec, SRE_DECLINED, smode) ? len + 1 : 0;
             }
-            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0 * P, vals.data(), nb * P * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            SRE_HIP_TRY(hipMemcpyAsync(sink->d_start + i0 * P, starts.data(), nb * P * sizeof(uint64_t), hipMemcpyHostToDevice,
-                                       stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-        } else if (sink && sink->groups) {
-            /* what sre_k_extract_select writes, from the records the host holds: the entry table of the groups, and for
-             * the tally's sums the value table of the value groups */
-            for (int pass = 0; pass < (sink->vgroups ? 2 : 1); pass++) {
-                const sre_extract_groups_t *gr = pass ? sink->vgroups : sink->groups;
-                std::vector<uint64_t>      &ev = pass ? vvals : vals, &es = pass ? vstarts : starts;
-                const uint32_t              k = gr->k;
-                ev.resize(nb * k);
-                es.resize(nb * k);
-                for (uint64_t j = 0; j < nb; j++) {
-                    const sre_int_t *rec = recs.data() + j * slots;
-                    const bool       hit = rec[0] != SRE_DECLINED;
-                    const uint64_t   st = (uint64_t) (static_cast<const uint8_t *>(ptrs[j]) - buf);
-                    for (uint32_t f = 0; f < k; f++) {
-                        const uint32_t  g = gr->g[f];
-                        const sre_int_t a = hit ? rec[2 + 2 * g] : -1, b = hit ? rec[3 + 2 * g] : -1;
-                        const bool      set = a >= 0 && b >= a && (uint64_t) b <= lens[j];
-                        ev[j * k + f] = (hit || sink->mode == 2) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
-                        es[j * k + f] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
-                                        | (f + 1 == k ? SRE_LG_ENTRY_LAST : 0);
-                    }
-                }
-                SRE_HIP_TRY(hipMemcpyAsync((pass ? sink->d_vval : sink->d_val) + i0 * k, ev.data(), nb * k * sizeof(uint64_t),
-                                           hipMemcpyHostToDevice, stream));
-                SRE_HIP_TRY(hipMemcpyAsync((pass ? sink->d_vstart : sink->d_start) + i0 * k, es.data(), nb * k * sizeof(uint64_t),
+            SRE_HIP_TRY(hipMemcpyAsync((pass ? sc->d_vval : sc->d_fval) + i0 * k, vals.data(), nb * k * sizeof(uint64_t),
+                                       hipMemcpyHostToDevice, stream));
+            if (pc || gr) {
+                SRE_HIP_TRY(hipMemcpyAsync((pass ? sc->d_vstart : sc->d_fstart) + i0 * k, starts.data(), nb * k * sizeof(uint64_t),
                                            hipMemcpyHostToDevice, stream));
             }
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-        } else if (sink && sink->h_map) {
-            /* what sre_k_route_select writes, from the records the host holds */
-            vals.resize(nb);
-            for (uint64_t j = 0; j < nb; j++) {
-                vals[j] = sre_lr_key(sre_lr_bucket(recs[j * slots], SRE_DECLINED, sink->nreg, sink->h_map), (uint64_t) lens[j]);
-            }
-            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0, vals.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-        } else if (sink) {
-            vals.resize(nb);
-            for (uint64_t j = 0; j < nb; j++) vals[j] = sink_selects(sink, recs[j * slots]) ? (uint64_t) lens[j] + 1 : 0;
-            SRE_HIP_TRY(hipMemcpyAsync(sink->d_val + i0, vals.data(), nb * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));      /* (the next pass fills the vectors again) */
         }
         for (uint64_t j = 0; !sink && j < nb; j++) {
             const sre_int_t *rec = recs.data() + j * slots;
-            if (!all && rec[0] == SRE_DECLINED) continue;
+            if (!sre_sel_row(rec, SRE_DECLINED, all ? 2 : 0)) continue;
             if (nrep < cap) {
                 sre_int_t *row = out + nrep * width;
                 row[0] = (sre_int_t) (i0 + j);
@@ -2104,7 +2115,7 @@ hip_failed:
  * call's lines first.  The call replaces the scanner's last one; its diagnostics describe the whole call. */
 static int
 lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int all, sre_int_t *out, size_t cap,
-           LinesSink *sink, uint64_t *pn, uint64_t *pnrep, hipStream_t stream)
+           const LinesSink *sink, uint64_t *pn, uint64_t *pnrep, hipStream_t stream)
 {
     uint64_t    n = 0, nrep = 0;
     int         rc = -1;
@@ -2122,17 +2133,13 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
         if (sink) {
             const uint64_t k = sink_entries(sink);
             if (lines_grow(&sc->d_fval, &sc->fval_cap, (n * k + 1) * sizeof(uint64_t)) != 0) goto hip_failed;
-            sink->d_val = sc->d_fval;
             if (sink->groups || sink->pieces) {
                 if (lines_grow(&sc->d_fstart, &sc->fstart_cap, n * k * sizeof(uint64_t)) != 0) goto hip_failed;
-                sink->d_start = sc->d_fstart;
             }
             if (sink->vgroups) {
                 const uint64_t v = sink->vgroups->k;
                 if (lines_grow(&sc->d_vval, &sc->vval_cap, n * v * sizeof(uint64_t)) != 0) goto hip_failed;
                 if (lines_grow(&sc->d_vstart, &sc->vstart_cap, n * v * sizeof(uint64_t)) != 0) goto hip_failed;
-                sink->d_vval = sc->d_vval;
-                sink->d_vstart = sc->d_vstart;
             }
         }
         rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink)
@@ -2176,44 +2183,73 @@ sre_hip_scan_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     return 0;
 }
 
-/* The line filter (DESIGN.md §4.11.2): the line-mode call with a sink, then on the device the scan of the per-line
- * values to the offset table, the cut at out_cap, one read of four words, the gather and the index rows. */
-extern "C" SRE_API int
-sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, void *d_out,
-    size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream)
+/* The tail of the sinks that scan an entry table (a word per line, fields or pieces), behind the line-mode call, in three
+ * steps; a call may queue passes of its own between them.  First the scan to the offset table and the cut at out_cap. */
+static int
+sink_offsets(sre_hip_scanner_t *sc, const LinesSink *sink, uint64_t n, hipStream_t stream)
 {
-    const int known = SRE_HIP_LINES_ALL | SRE_HIP_LINES_INVERT;
-    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~known) != 0 || (flags & known) == known
-        || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
-    {
-        return -1;
-    }
-    if (len != 0 && out_cap != 0) {
-        /* the output may not overlap the buffer */
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (o < b + len && b < o + out_cap) return -1;
-    }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0, NULL, NULL, NULL};
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    const uint32_t k = sink_entries(sink);
+    const uint64_t nblk = (n * k + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+    SRE_HIP_TRY(sink->pieces   ? sre_launch_subst_offsets(sc->d_fval, n, k, sc->d_fblk, sink->out_cap, sc->d_linfo, stream)
+                : sink->groups ? sre_launch_extract_offsets(sc->d_fval, n, k, sc->d_fblk, sink->out_cap, sc->d_linfo, stream)
+                               : sre_launch_filter_offsets(sc->d_fval, n, sc->d_fblk, sink->out_cap, sc->d_linfo, stream));
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* ... then the one read of the call (the scan's four words and `more` of the call's own) into the fields every info has */
+template <class Info, class... More>
+static int
+sink_read(sre_hip_scanner_t *sc, const LinesSink *sink, uint64_t n, Info *res, hipStream_t stream, More... more)
+{
+    SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(fsel), LINFO(fneed), LINFO(fwritten), LINFO(fbytes), more...}));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    res->nlines = (size_t) n;
+    res->nselected = (size_t) sc->h_linfo->fsel;
+    res->need_bytes = (size_t) sc->h_linfo->fneed;
+    res->nwritten = (size_t) sc->h_linfo->fwritten;
+    res->out_bytes = (size_t) sc->h_linfo->fbytes;
+    return res->out_bytes > sink->out_cap ? -1 : 0;     /* (cannot happen: the cut is made against out_cap) */
+hip_failed:
+    return -1;
+}
+
+/* ... then the gather of the out_bytes bytes and the index rows of the written lines, queued */
+static int
+sink_write(sre_hip_scanner_t *sc, const LinesSink *sink, const void *d_buf, uint64_t n, uint64_t out_bytes, uint64_t nwritten,
+           hipStream_t stream)
+{
+    const uint32_t          k = sink_entries(sink), delim = (uint32_t) sink->delim, fsep = (uint32_t) sink->fsep;
+    const uint64_t         *off = sc->d_fval, *start = sc->d_fstart, *ends = sc->d_ends, *blk = sc->d_fblk, cap = sink->index_cap;
+    const sre_lines_info_t *li = sc->d_linfo;
+    int64_t                *rows = sink->d_index;
+    if (sink->pieces) SRE_HIP_TRY(sre_launch_subst_gather(d_buf, sink->d_out, off, start, sc->d_lit, n * k, out_bytes, delim, stream));
+    else if (sink->groups) SRE_HIP_TRY(sre_launch_extract_gather(d_buf, sink->d_out, off, start, n * k, out_bytes, delim, fsep, stream));
+    else SRE_HIP_TRY(sre_launch_lines_gather(d_buf, sink->d_out, off, ends, n, out_bytes, delim, stream));
+    if (nwritten == 0) return 0;
+    if (sink->pieces) SRE_HIP_TRY(sre_launch_subst_index(off, start, ends, n, k, blk, li, cap, rows, stream));
+    else if (sink->groups) SRE_HIP_TRY(sre_launch_extract_index(off, start, ends, n, k, blk, li, cap, rows, stream));
+    else if (sink->context) SRE_HIP_TRY(sre_launch_context_index(off, ends, n, blk, sink->d_cbits, li, cap, rows, stream));
+    else SRE_HIP_TRY(sre_launch_filter_index(off, ends, n, blk, li, cap, rows, stream));
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* the three steps back to back and the wait for them: the whole tail of the filter, the extract and the substitute */
+static int
+sink_finish(sre_hip_scanner_t *sc, const LinesSink *sink, const void *d_buf, uint64_t n, sre_hip_filter_info_t *info,
+            hipStream_t stream)
+{
     sre_hip_filter_info_t res;
     memset(&res, 0, sizeof(res));
     if (n != 0) {
-        const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
-        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_fval, n, sc->d_fblk, out_cap, sc->d_linfo, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        res.nlines = (size_t) n;
-        res.nselected = (size_t) sc->h_linfo->fsel;
-        res.need_bytes = (size_t) sc->h_linfo->fneed;
-        res.nwritten = (size_t) sc->h_linfo->fwritten;
-        res.out_bytes = (size_t) sc->h_linfo->fbytes;
-        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
-        SRE_HIP_TRY(sre_launch_lines_gather(d_buf, d_out, sc->d_fval, sc->d_ends, n, res.out_bytes, (uint32_t) delim, stream));
-        if (res.nwritten != 0) {
-            SRE_HIP_TRY(sre_launch_filter_index(sc->d_fval, sc->d_ends, n, sc->d_fblk, sc->d_linfo, index_cap, d_index, stream));
+        if (sink_offsets(sc, sink, n, stream) != 0 || sink_read(sc, sink, n, &res, stream) != 0
+            || sink_write(sc, sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0)
+        {
+            return -1;
         }
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -2221,6 +2257,22 @@ sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
     return 0;
 hip_failed:
     return -1;
+}
+
+/* The line filter (DESIGN.md §4.11.2): the line-mode call with a sink, then on the device the scan of the per-line
+ * values to the offset table, the cut at out_cap, one read of four words, the gather and the index rows. */
+extern "C" SRE_API int
+sre_hip_filter_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, void *d_out,
+    size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream)
+{
+    const int known = SRE_HIP_LINES_ALL | SRE_HIP_LINES_INVERT;
+    LinesSink sink;
+    if ((flags & ~known) != 0 || (flags & known) == known) return -1;
+    if (!sink_open(&sink, sc, d_buf, len, delim, flags, d_out, out_cap, d_index, index_cap)) return -1;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    return sink_finish(sc, &sink, d_buf, n, info, stream);
 }
 
 /* The line filter with context lines: sre_hip_filter_lines with one more device pass between the
@@ -2234,49 +2286,33 @@ sre_hip_filter_lines_context(sre_hip_scanner_t *sc, const void *d_buf, size_t le
 {
     const int  known = SRE_HIP_LINES_ALL | SRE_HIP_LINES_INVERT;
     const bool context = before != 0 || after != 0;
-    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~known) != 0 || (flags & known) == known
-        || ((flags & SRE_HIP_LINES_ALL) && context) || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL)
-        || (len != 0 && d_buf == NULL))
+    LinesSink  sink;
+    if ((flags & ~known) != 0 || (flags & known) == known || ((flags & SRE_HIP_LINES_ALL) && context)
+        || !sink_open(&sink, sc, d_buf, len, delim, flags, d_out, out_cap, d_index, index_cap))
     {
         return -1;
     }
-    if (len != 0 && out_cap != 0) {
-        /* the output may not overlap the buffer */
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (o < b + len && b < o + out_cap) return -1;
-    }
+    sink.context = true;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : (flags & SRE_HIP_LINES_INVERT) ? 1 : 0, NULL, NULL, NULL};
     uint64_t    n = 0, nrep = 0;
     if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
     sre_hip_context_info_t res;
     memset(&res, 0, sizeof(res));
     if (n != 0) {
         const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
         if (lines_grow(&sc->d_cblk, &sc->cblk_cap, 4 * nblk * sizeof(uint64_t)) != 0) return -1;
         if (context) {
             if (lines_grow(&sc->d_cbits, &sc->cbits_cap, (n + 63) / 64 * sizeof(uint64_t)) != 0) return -1;
             SRE_HIP_TRY(sre_launch_context_select(sc->d_fval, sc->d_ends, n, before, after, sc->d_cbits, sc->d_cblk, sc->d_linfo,
                                                   stream));
+            sink.d_cbits = sc->d_cbits;
         }
-        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_fval, n, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
         if (!context) SRE_HIP_TRY(sre_launch_context_runs(sc->d_fval, n, sc->d_cblk, sc->d_linfo, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        res.nlines = (size_t) n;
-        res.nselected = (size_t) sc->h_linfo->fsel;
+        if (sink_read(sc, &sink, n, &res, stream, LINFO(cmatched), LINFO(cgroups)) != 0) return -1;
         res.nmatched = context ? (size_t) sc->h_linfo->cmatched : res.nselected;
         res.ngroups = (size_t) sc->h_linfo->cgroups;
-        res.need_bytes = (size_t) sc->h_linfo->fneed;
-        res.nwritten = (size_t) sc->h_linfo->fwritten;
-        res.out_bytes = (size_t) sc->h_linfo->fbytes;
-        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
-        SRE_HIP_TRY(sre_launch_lines_gather(d_buf, d_out, sc->d_fval, sc->d_ends, n, res.out_bytes, (uint32_t) delim, stream));
-        if (res.nwritten != 0) {
-            SRE_HIP_TRY(sre_launch_context_index(sc->d_fval, sc->d_ends, n, sc->d_fblk, context ? sc->d_cbits : NULL, sc->d_linfo,
-                                                 index_cap, d_index, stream));
-        }
+        if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
     if (info) *info = res;
@@ -2292,59 +2328,20 @@ sre_hip_extract_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int 
     int fsep, int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info,
     void *hip_stream)
 {
-    if (sc == NULL || delim < 0 || delim > 255 || fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0
-        || groups == NULL || ngroups < 1 || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (out_cap != 0 && d_out == NULL)
-        || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    if (fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1
+        || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || !sink_open(&sink, sc, d_buf, len, delim, flags, d_out, out_cap, d_index, index_cap))
     {
         return -1;
     }
-    if (sc->mode != SRE_HIP_PIKE_FIRST) {
-        fprintf(stderr, "[sregex-hip] line extract: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
-        return -1;
-    }
-    sre_extract_groups_t gr;
-    memset(&gr, 0, sizeof(gr));
-    gr.k = (uint32_t) ngroups;
-    for (size_t f = 0; f < ngroups; f++) {
-        /* ovec_slots = 2 * (max_ncaps + 1) */
-        if (groups[f] < 0 || groups[f] > 0xFFFF || 2 * (size_t) groups[f] + 1 >= (size_t) sc->ovec_slots) return -1;
-        gr.g[f] = (uint16_t) groups[f];
-    }
-    if (len != 0 && out_cap != 0) {
-        /* the output may not overlap the buffer */
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (o < b + len && b < o + out_cap) return -1;
-    }
+    if (!sink_first_match(sc, "line extract", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
+    sink.groups = &gr;
+    sink.fsep = fsep;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, &gr, NULL};
     uint64_t    n = 0, nrep = 0;
     if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
-    sre_hip_filter_info_t res;
-    memset(&res, 0, sizeof(res));
-    if (n != 0) {
-        const uint64_t nent = n * gr.k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
-        SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_fval, n, gr.k, sc->d_fblk, out_cap, sc->d_linfo, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        res.nlines = (size_t) n;
-        res.nselected = (size_t) sc->h_linfo->fsel;
-        res.need_bytes = (size_t) sc->h_linfo->fneed;
-        res.nwritten = (size_t) sc->h_linfo->fwritten;
-        res.out_bytes = (size_t) sc->h_linfo->fbytes;
-        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
-        SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, nent, res.out_bytes, (uint32_t) delim,
-                                              (uint32_t) fsep, stream));
-        if (res.nwritten != 0) {
-            SRE_HIP_TRY(sre_launch_extract_index(sc->d_fval, sc->d_fstart, sc->d_ends, n, gr.k, sc->d_fblk, sc->d_linfo, index_cap,
-                                                 d_index, stream));
-        }
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-    }
-    if (info) *info = res;
-    return 0;
-hip_failed:
-    return -1;
+    return sink_finish(sc, &sink, d_buf, n, info, stream);
 }
 
 /* the hash bits the tally's table index keeps: SRE_HIP_TALLY_HASH_BITS (test knob, read on every call; 0 .. 64), else all */
@@ -2379,78 +2376,52 @@ tally_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, cons
     sre_hip_tally_sum_t *d_sums, size_t sums_cap, sre_int_t *d_keyid, size_t keyid_cap, sre_int_t *d_index, size_t index_cap,
     sre_hip_tally_info_t *info, void *hip_stream)
 {
-    if (sc == NULL || delim < 0 || delim > 255 || fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0
-        || groups == NULL || ngroups < 1 || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (out_cap != 0 && d_out == NULL)
-        || (index_cap != 0 && d_index == NULL) || (counts_cap != 0 && d_counts == NULL) || (keyid_cap != 0 && d_keyid == NULL)
-        || (len != 0 && d_buf == NULL) || max_keys < 1 || max_keys > SRE_LT_MAX_KEYS)
+    LinesSink            sink;
+    sre_extract_groups_t gr, vg;
+    if (fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1
+        || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (counts_cap != 0 && d_counts == NULL) || (keyid_cap != 0 && d_keyid == NULL)
+        || max_keys < 1 || max_keys > SRE_LT_MAX_KEYS)
     {
         return -1;
     }
-    if (sc->mode != SRE_HIP_PIKE_FIRST) {
-        fprintf(stderr, "[sregex-hip] line tally: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
+    if (!sink_open(&sink, sc, d_buf, len, delim, flags, d_out, out_cap, d_index, index_cap)) return -1;
+    if (!sink_first_match(sc, "line tally", "captures") || !sink_groups(sc, groups, ngroups, &gr)
+        || !sink_groups(sc, vgroups, nvgroups, &vg))
+    {
         return -1;
     }
-    sre_extract_groups_t gr, vg;
-    memset(&gr, 0, sizeof(gr));
-    gr.k = (uint32_t) ngroups;
-    for (size_t f = 0; f < ngroups; f++) {
-        /* ovec_slots = 2 * (max_ncaps + 1) */
-        if (groups[f] < 0 || groups[f] > 0xFFFF || 2 * (size_t) groups[f] + 1 >= (size_t) sc->ovec_slots) return -1;
-        gr.g[f] = (uint16_t) groups[f];
-    }
-    memset(&vg, 0, sizeof(vg));
-    vg.k = (uint32_t) nvgroups;
-    for (size_t c = 0; c < nvgroups; c++) {
-        if (vgroups[c] < 0 || vgroups[c] > 0xFFFF || 2 * (size_t) vgroups[c] + 1 >= (size_t) sc->ovec_slots) return -1;
-        vg.g[c] = (uint16_t) vgroups[c];
-    }
-    if (len != 0 && out_cap != 0) {
-        /* the output may not overlap the buffer */
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (o < b + len && b < o + out_cap) return -1;
-    }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    LinesSink   sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, &gr, NULL};
-    uint64_t    n = 0, nrep = 0;
+    sink.groups = &gr;
+    sink.fsep = fsep;
     if (vgroups) sink.vgroups = &vg;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
     if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
     sre_hip_tally_info_t res;
     memset(&res, 0, sizeof(res));
     int rc = 0;
     if (n != 0) {
-        const uint64_t nent = n * gr.k, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
         const uint64_t nslots = sre_lt_nslots(max_keys);
-        uint64_t      *tab, *cnt;
-        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
         if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
         if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
-        tab = sc->d_ttab;
-        cnt = sc->d_ttab + nslots;
+        uint64_t *const tab = sc->d_ttab, *const cnt = sc->d_ttab + nslots;
         SRE_HIP_TRY(hipMemsetAsync(tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
         SRE_HIP_TRY(hipMemsetAsync(cnt, 0, nslots * sizeof(uint64_t), stream));
+        static_assert(offsetof(sre_lines_info_t, tclaims) == offsetof(sre_lines_info_t, tsel) + sizeof(uint64_t)
+                          && offsetof(sre_lines_info_t, tover) == offsetof(sre_lines_info_t, tsel) + 2 * sizeof(uint64_t),
+                      "tsel, tclaims, tover are zeroed as one run");
         SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
         SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, gr.k, nslots, max_keys, tally_hash_mask(), tab, cnt,
                                             sc->d_tslot, sc->d_linfo, stream));
-        SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_fval, n, gr.k, sc->d_fblk, out_cap, sc->d_linfo, stream));
-        /* fsel, fneed, fwritten, fbytes, (cmatched, cgroups,) tsel, tclaims, tover */
-        SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 9 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        res.nlines = (size_t) n;
-        res.nselected = (size_t) sc->h_linfo->tsel;
+        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
+        if (sink_read(sc, &sink, n, &res, stream, LINFO(tsel), LINFO(tclaims), LINFO(tover)) != 0) return -1;
         if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
+            memset(&res, 0, sizeof(res));       /* (nothing is written: only the two counts of lines stand) */
             rc = SRE_HIP_TALLY_OVERFLOW;
         } else {
-            res.nkeys = (size_t) sc->h_linfo->fsel;
-            res.need_bytes = (size_t) sc->h_linfo->fneed;
-            res.nwritten = (size_t) sc->h_linfo->fwritten;
-            res.out_bytes = (size_t) sc->h_linfo->fbytes;
-            if (res.out_bytes > out_cap || res.nkeys != sc->h_linfo->tclaims) return -1;    /* (cannot happen) */
-            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, nent, res.out_bytes, (uint32_t) delim,
-                                                  (uint32_t) fsep, stream));
-            if (res.nwritten != 0) {
-                SRE_HIP_TRY(sre_launch_extract_index(sc->d_fval, sc->d_fstart, sc->d_ends, n, gr.k, sc->d_fblk, sc->d_linfo,
-                                                     index_cap, d_index, stream));
-            }
+            /* the table selected the first line of every key: what the scan counted are the keys */
+            res.nkeys = res.nselected;
+            if (res.nkeys != sc->h_linfo->tclaims) return -1;    /* (cannot happen) */
+            if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
             SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, gr.k, sc->d_fblk, sc->d_tslot, cnt, d_counts, counts_cap,
                                                reinterpret_cast<int64_t *>(d_keyid), keyid_cap, stream));
             if (vgroups && sums_cap != 0) {
@@ -2466,6 +2437,8 @@ tally_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, cons
             }
             SRE_HIP_TRY(hipStreamSynchronize(stream));
         }
+        res.nlines = (size_t) n;
+        res.nselected = (size_t) sc->h_linfo->tsel;
     }
     if (info) *info = res;
     return rc;
@@ -2591,15 +2564,13 @@ extern "C" SRE_API int
 sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const void *tmpl, size_t tmpl_len,
     int flags, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info, void *hip_stream)
 {
-    if (sc == NULL || delim < 0 || delim > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || (tmpl_len != 0 && tmpl == NULL)
-        || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
+    LinesSink sink;
+    if ((flags & ~SRE_HIP_LINES_ALL) != 0 || (tmpl_len != 0 && tmpl == NULL)
+        || !sink_open(&sink, sc, d_buf, len, delim, flags, d_out, out_cap, d_index, index_cap))
     {
         return -1;
     }
-    if (sc->mode != SRE_HIP_PIKE_FIRST) {
-        fprintf(stderr, "[sregex-hip] line substitute: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's captures)\n");
-        return -1;
-    }
+    if (!sink_first_match(sc, "line substitute", "captures")) return -1;
     sre_subst_pieces_t pc;
     uint8_t            lit[SRE_SUBST_MAX_LITERAL];
     size_t             nlit = 0;
@@ -2607,11 +2578,6 @@ sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, i
     if (subst_parse(static_cast<const uint8_t *>(tmpl), tmpl_len, (int) sc->ovec_slots / 2 - 1, &pc, lit, &nlit) != 0) return -1;
     /* a literal delimiter would make two rows of one line */
     if (nlit != 0 && memchr(lit, delim, nlit) != NULL) return -1;
-    if (len != 0 && out_cap != 0) {
-        /* the output may not overlap the buffer */
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (o < b + len && b < o + out_cap) return -1;
-    }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     /* the literal block: allocated once, uploaded when the literals differ from the ones it holds */
     if (sc->d_lit == NULL) {
@@ -2630,38 +2596,14 @@ sre_hip_substitute_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, i
         sc->lit_valid = true;
     }
     {
-        const uint32_t P = pc.np + 2;
-        LinesSink      sink = {(flags & SRE_HIP_LINES_ALL) ? 2 : 0, NULL, NULL, NULL, &pc};
-        uint64_t       n = 0, nrep = 0;
+        uint64_t n = 0, nrep = 0;
+        sink.pieces = &pc;
         if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) {
             sc->lit_valid = false;      /* (the upload may not have run) */
             return -1;
         }
-        sre_hip_filter_info_t res;
-        memset(&res, 0, sizeof(res));
-        if (n != 0) {
-            const uint64_t nent = n * P, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-            if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
-            SRE_HIP_TRY(sre_launch_subst_offsets(sc->d_fval, n, P, sc->d_fblk, out_cap, sc->d_linfo, stream));
-            SRE_HIP_TRY(hipMemcpyAsync(&sc->h_linfo->fsel, &sc->d_linfo->fsel, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-            res.nlines = (size_t) n;
-            res.nselected = (size_t) sc->h_linfo->fsel;
-            res.need_bytes = (size_t) sc->h_linfo->fneed;
-            res.nwritten = (size_t) sc->h_linfo->fwritten;
-            res.out_bytes = (size_t) sc->h_linfo->fbytes;
-            if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
-            SRE_HIP_TRY(sre_launch_subst_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, sc->d_lit, nent, res.out_bytes,
-                                                (uint32_t) delim, stream));
-            if (res.nwritten != 0) {
-                SRE_HIP_TRY(sre_launch_subst_index(sc->d_fval, sc->d_fstart, sc->d_ends, n, P, sc->d_fblk, sc->d_linfo, index_cap,
-                                                   d_index, stream));
-            }
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-        }
-        if (info) *info = res;
+        return sink_finish(sc, &sink, d_buf, n, info, stream);
     }
-    return 0;
 hip_failed:
     return -1;
 }
@@ -2669,21 +2611,18 @@ hip_failed:
 /* The line route: the line-mode call with the route's sink (a key per line), then on the device the
  * per-(bucket, workgroup) counts and their scan, one read of the selected lines, the scatter into the compact table, the
  * filter's scan over it, the cut and the bucket totals, one read of 4 + 2 nbuckets words, the extract's gather over the
- * compact table and the index rows. */
+ * compact table and the index rows.  (Its table is compact and its result words are its own: it shares the sinks'
+ * argument checks and none of their tail.) */
 extern "C" SRE_API int
 sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *bucket_of, size_t nbuckets,
     void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_filter_info_t *info,
     sre_hip_route_bucket_t *buckets, void *hip_stream)
 {
-    if (sc == NULL || delim < 0 || delim > 255 || nbuckets < 1 || nbuckets > SRE_LR_MAX_BUCKETS
-        || (out_cap != 0 && d_out == NULL) || (index_cap != 0 && d_index == NULL) || (len != 0 && d_buf == NULL))
-    {
+    LinesSink sink;
+    if (nbuckets < 1 || nbuckets > SRE_LR_MAX_BUCKETS || !sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) {
         return -1;
     }
-    if (sc->mode != SRE_HIP_PIKE_FIRST) {
-        fprintf(stderr, "[sregex-hip] line route: the scanner's mode must be SRE_HIP_PIKE_FIRST (the first match's regex id)\n");
-        return -1;
-    }
+    if (!sink_first_match(sc, "line route", "regex id")) return -1;
     const uint32_t R = sc->prog->nregexes;
     if (bucket_of == NULL && nbuckets != R) return -1;
     std::vector<int32_t> map(R + 1);
@@ -2691,11 +2630,6 @@ sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
         const int b = bucket_of ? bucket_of[r] : (r < R ? (int) r : -1);
         if (b < -1 || b >= (int) nbuckets) return -1;
         map[r] = b;
-    }
-    if (len != 0 && out_cap != 0) {
-        /* the output may not overlap the buffer */
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (o < b + len && b < o + out_cap) return -1;
     }
     hipStream_t           stream = static_cast<hipStream_t>(hip_stream);
     const uint32_t        nb = (uint32_t) nbuckets;
@@ -2717,8 +2651,9 @@ sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
         sc->rmap_valid = true;
     }
     {
-        LinesSink sink = {0, NULL, NULL, NULL, NULL, sc->h_rmap, sc->d_rmap, R};
-        uint64_t  n = 0, nrep = 0;
+        uint64_t n = 0, nrep = 0;
+        sink.route = true;
+        sink.nreg = R;
         if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
         if (n != 0) {
             const uint64_t nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nb * nwg;

@@ -11,6 +11,7 @@
 #include "sre_hip_scan.h"
 #include "sre_hip_nfa.h"
 #include "sre_lines_nfa.h"
+#include "sre_lines_select.h"     /* sre_extract_groups_t, sre_subst_pieces_t and the select rules */
 
 /* split: a workgroup of SRE_LINES_THREADS lanes owns one tile of 16-byte aligned chunks, each lane
  * loads SRE_LINES_CHUNKS chunks of it (lane x, step k: chunk k * SRE_LINES_THREADS + x of the tile).
@@ -99,8 +100,7 @@ hipError_t sre_launch_lines_nfa(sre_lnfa_t tab, const void *d_buf, const uint64_
     uint32_t short_lim, int thompson, sre_nfa_status_t *d_status, int64_t *d_records, uint32_t ovec_slots,
     int64_t *d_lo, hipStream_t stream);
 /* ---- the line filter (sre_hip_lines_gather.hip) ---- */
-/* select pass of the batch (lines i0 .. info->i1, at most nmax): d_val[i] = len + 1 of a selected line, else 0;
- * mode 0: rc != SRE_DECLINED, 1: rc == SRE_DECLINED, 2: every line */
+/* select pass of the batch (lines i0 .. info->i1, at most nmax): d_val[i] = len + 1 of a row of sre_sel_row, else 0 */
 hipError_t sre_launch_filter_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int mode,
     const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val, hipStream_t stream);
 /* d_val[0 .. n) becomes the offset table off[0 .. n] in place (n + 1 words); d_blk: 2 x ceil(n / SRE_LINES_ITEMS)
@@ -130,15 +130,8 @@ hipError_t sre_launch_context_runs(const uint64_t *d_off, uint64_t n, uint64_t *
 hipError_t sre_launch_context_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
     const uint64_t *d_bits, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
 /* ---- the line extract (sre_hip_lines_gather.hip) ---- */
-#define SRE_EXTRACT_MAX_FIELDS 32u
-/* the chosen capture groups: field f of a row is group g[f] of the line's record */
-typedef struct {
-    uint32_t k;
-    uint16_t g[SRE_EXTRACT_MAX_FIELDS];
-} sre_extract_groups_t;
-/* select pass of the batch over its entries e = line * k + f: d_val[e] = field length + 1 for every field of a
- * selected line (rc != SRE_DECLINED, or every line with `all`), else 0; d_start[e] = the field's offset in the buffer
- * under the flag bits of sre_lines_gather.h.  A batch may have at most 2^32 - 1 entries */
+/* select pass of the batch over its entries e = line * k + f: d_val[e] and d_start[e] as sre_sel_extract_entry gives
+ * them.  A batch may have at most 2^32 - 1 entries */
 hipError_t sre_launch_extract_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int all,
     const sre_extract_groups_t *groups, const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val,
     uint64_t *d_start, hipStream_t stream);
@@ -155,20 +148,8 @@ hipError_t sre_launch_extract_index(const uint64_t *d_off, const uint64_t *d_sta
     uint32_t k, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
 /* ---- the line substitute (sre_hip_lines_gather.hip) ---- */
-#define SRE_SUBST_MAX_PIECES  30u
-#define SRE_SUBST_MAX_LITERAL 4096u
-/* the parsed template: piece q is capture group g[q] of the line's record, or with g[q] < 0 the len[q] bytes at off[q]
- * of the call's literal block */
-typedef struct {
-    uint32_t np;
-    int16_t  g[SRE_SUBST_MAX_PIECES];
-    uint16_t off[SRE_SUBST_MAX_PIECES];
-    uint16_t len[SRE_SUBST_MAX_PIECES];
-} sre_subst_pieces_t;
-/* select pass of the batch over its entries e = line * p + f, p = np + 2: d_val[e] = the bytes of the entry (the line's
- * text in front of the match, a piece, the text behind the match + 1 for the delimiter) for a selected line (rc !=
- * SRE_DECLINED, or every line with `all`: a line without a match is its own row), else 0; d_start[e] = where the
- * entry's text starts, under the flag bits of sre_lines_gather.h.  A batch may have at most 2^32 - 1 entries */
+/* select pass of the batch over its entries e = line * p + f, p = np + 2: d_val[e] and d_start[e] as
+ * sre_sel_subst_entry gives them.  A batch may have at most 2^32 - 1 entries */
 hipError_t sre_launch_subst_select(const int64_t *d_records, uint32_t slots, uint64_t nmax, uint64_t i0, int all,
     const sre_subst_pieces_t *pieces, const uint64_t *d_ends, const sre_lines_info_t *d_info, uint64_t *d_val,
     uint64_t *d_start, hipStream_t stream);

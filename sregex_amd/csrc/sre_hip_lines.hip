@@ -381,10 +381,11 @@ sre_k_lines_settle(const sre_stream_status_t *__restrict__ status, uint32_t n, s
 
 /* ---- compaction ---- */
 
+/* the row rule of line mode (sre_lines_select.h): the hits, or every line with `all` */
 __device__ inline uint32_t
 reported(const int64_t *records, uint32_t slots, uint64_t j, int all)
 {
-    return all || records[j * slots] != SRE_DECLINED;
+    return sre_sel_row(records + j * slots, SRE_DECLINED, all ? 2 : 0);
 }
 
 __global__ __launch_bounds__(256) void

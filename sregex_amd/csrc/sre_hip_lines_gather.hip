@@ -1,7 +1,8 @@
 /*
  * sre_hip_lines_gather.hip — the line filter on the device (sregex_hip.h sre_hip_filter_lines).
  *
- *   select     per batch: val[i] = len + 1 of a selected line, 0 of the others, from the batch's records;
+ *   select     per batch: val[i] = len + 1 of a selected line, 0 of the others, from the batch's records.  The kernels
+ *              only index: the rules are sre_lines_select.h's, which the host route and the CPU models compile too;
  *   scan       after the last batch: val becomes the offset table off[0 .. n] in place (per-workgroup sums, a
  *              single-workgroup scan of the sums, then the prefixes), the sums of the selected lines stay in
  *              blk for the index; `finish` cuts the output at whole lines that fit out_cap;
@@ -31,7 +32,7 @@ namespace {
 
 /* ---- select ---- */
 
-/* lane per line of the batch (lines i0 .. info->i1): mode 0 selects rc != SRE_DECLINED, 1 the others, 2 all */
+/* lane per line of the batch (lines i0 .. info->i1): the rows of sre_sel_row under mode 0 / 1 / 2 */
 __global__ __launch_bounds__(256) void
 sre_k_filter_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t i0, int mode,
                     const uint64_t *__restrict__ ends, const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ val)
@@ -39,17 +40,14 @@ sre_k_filter_select(const int64_t *__restrict__ records, uint32_t slots, uint64_
     const uint64_t nb = info->i1 - i0;
     const uint64_t j = (uint64_t) blockIdx.x * 256u + threadIdx.x;
     if (j >= nb) return;
-    const bool     hit = records[j * slots] != SRE_DECLINED;
-    const bool     sel = mode == 2 || hit != (mode == 1);
     const uint64_t i = i0 + j;
-    val[i] = sel ? ends[i] - line_start(ends, i) + 1 : 0;
+    val[i] = sre_sel_row(records + j * slots, SRE_DECLINED, mode) ? ends[i] - line_start(ends, i) + 1 : 0;
 }
 
 /* the line extract's: LANE PER ENTRY of the batch, entry x = j * K + f of line i0 + j.  The stores of val and start
  * are then consecutive words of consecutive lanes; the K lanes of a line read the same record, whose two ovector
  * words lie in the cache lines the neighbouring lanes read too (a lane per line would read the same records and
- * scatter 2 K stores at a stride of K words).  val = field length + 1 for every entry of a selected line, else 0;
- * start = the field's source offset (the line's start for an unset field) under the flags of sre_lines_gather.h */
+ * scatter 2 K stores at a stride of K words).  The two words are sre_sel_extract_entry's */
 __global__ __launch_bounds__(256) void
 sre_k_extract_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t i0, int all, sre_extract_groups_t gr,
                      const uint64_t *__restrict__ ends, const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ val,
@@ -59,24 +57,13 @@ sre_k_extract_select(const int64_t *__restrict__ records, uint32_t slots, uint64
     const uint64_t x = (uint64_t) blockIdx.x * 256u + threadIdx.x;
     if (x >= nb * gr.k) return;
     const uint32_t j = (uint32_t) x / gr.k, f = (uint32_t) x - j * gr.k;       /* (a batch has fewer than 2^32 entries) */
-    const int64_t *rec = records + (uint64_t) j * slots;
-    const bool     hit = rec[0] != SRE_DECLINED;
     const uint64_t i = i0 + j, st = line_start(ends, i), len = ends[i] - st;
-    const uint32_t g = gr.g[f];
-    const int64_t  a = hit ? rec[2 + 2 * g] : -1, b = hit ? rec[3 + 2 * g] : -1;
-    /* (a set group lies inside its line; anything else counts as unset and can never reach outside the buffer) */
-    const bool     set = a >= 0 && b >= a && (uint64_t) b <= len;
     const uint64_t e = (i0 * gr.k) + x;
-    val[e] = (hit || all) ? (set ? (uint64_t) (b - a) : 0) + 1 : 0;
-    start[e] = (set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET) | (f == 0 ? SRE_LG_ENTRY_FIRST : 0)
-               | (f + 1 == gr.k ? SRE_LG_ENTRY_LAST : 0);
+    sre_sel_extract_entry(records + (uint64_t) j * slots, SRE_DECLINED, all, st, len, f, gr.k, gr.g[f], val + e, start + e);
 }
 
-/* the line substitute's: LANE PER ENTRY of the batch, entry x = j * P + f of line i0 + j, P = pieces + 2.  f = 0 is the
- * line's text in front of the match [m0, m1) = group 0, f = 1 .. P - 2 the template's pieces (a literal: its length and
- * its offset in the literal block; a group: as the extract's field, without the byte behind it), f = P - 1 the text
- * behind the match and the delimiter.  A selected line without a match, or whose group 0 does not lie inside the line,
- * is copied whole: its text is the first entry, its pieces are empty.  Every entry of an unselected line is 0 */
+/* the line substitute's: LANE PER ENTRY of the batch, entry x = j * P + f of line i0 + j, P = pieces + 2; the two words
+ * are sre_sel_subst_entry's */
 __global__ __launch_bounds__(256) void
 sre_k_subst_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t i0, int all, sre_subst_pieces_t pc,
                    const uint64_t *__restrict__ ends, const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ val,
@@ -87,32 +74,9 @@ sre_k_subst_select(const int64_t *__restrict__ records, uint32_t slots, uint64_t
     const uint64_t x = (uint64_t) blockIdx.x * 256u + threadIdx.x;
     if (x >= nb * P) return;
     const uint32_t j = (uint32_t) x / P, f = (uint32_t) x - j * P;             /* (a batch has fewer than 2^32 entries) */
-    const int64_t *rec = records + (uint64_t) j * slots;
-    const bool     hit = rec[0] != SRE_DECLINED;
     const uint64_t i = i0 + j, st = line_start(ends, i), len = ends[i] - st;
-    const int64_t  m0 = hit ? rec[2] : -1, m1 = hit ? rec[3] : -1;
-    /* (nothing but a match that lies inside its line is ever turned into offsets) */
-    const bool     ok = m0 >= 0 && m1 >= m0 && (uint64_t) m1 <= len;
-    uint64_t       v, w;
-    if (f == 0) {
-        v = ok ? (uint64_t) m0 : len;
-        w = st | SRE_LG_ENTRY_FIRST | (ok ? 0 : SRE_LG_ENTRY_UNSET);
-    } else if (f + 1 == P) {
-        v = (ok ? len - (uint64_t) m1 : 0) + 1;
-        w = (ok ? st + (uint64_t) m1 : st + len) | SRE_LG_ENTRY_LAST;
-    } else if (pc.g[f - 1] < 0) {
-        v = ok ? pc.len[f - 1] : 0;
-        w = (uint64_t) pc.off[f - 1] | SRE_LG_ENTRY_LITERAL;
-    } else {
-        const uint32_t g = (uint32_t) pc.g[f - 1];
-        const int64_t  a = ok ? rec[2 + 2 * g] : -1, b = ok ? rec[3 + 2 * g] : -1;
-        const bool     set = a >= 0 && b >= a && (uint64_t) b <= len;
-        v = set ? (uint64_t) (b - a) : 0;
-        w = set ? st + (uint64_t) a : st | SRE_LG_ENTRY_UNSET;
-    }
     const uint64_t e = (i0 * P) + x;
-    val[e] = (hit || all) ? v : 0;
-    start[e] = w;
+    sre_sel_subst_entry(records + (uint64_t) j * slots, SRE_DECLINED, all, st, len, f, &pc, val + e, start + e);
 }
 
 /* ---- scan ---- */

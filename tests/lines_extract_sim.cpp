@@ -3,9 +3,11 @@
  * kernel compiles (sregex_amd/csrc/sre_lines_gather.h) over the ENTRY table (sre_lg_tab_fields), tile by tile with
  * the kernel's table slices and its LDS window rule, over host copies of the two 16-byte aligned extents.  Every
  * source byte read and every output byte written is counted, so tests/test_lines_extract_model.py can assert where
- * the kernel may touch memory.  The cut at a line boundary is the header's too.
+ * the kernel may touch memory.  The cut at a line boundary is the header's too.  The select rule that fills the entry
+ * table from the lines' records (sregex_amd/csrc/sre_lines_select.h) is exported as the kernel and the host route call it.
  */
 #include "sre_lines_gather.h"
+#include "sre_lines_select.h"
 #include <stdint.h>
 #include <string.h>
 #include <vector>
@@ -69,6 +71,19 @@ uint64_t lesim_flag_first(void) { return SRE_LG_ENTRY_FIRST; }
 
 /* the cut: the first of n lines of k fields whose row ends beyond out_cap */
 uint64_t lesim_cut(const uint64_t *off, uint64_t n, uint64_t k, uint64_t out_cap) { return sre_lg_row_cut(off, n, k, out_cap); }
+
+/* the select rule over n lines: line i has the record recs[i * slots ..] and the extent [st[i], st[i] + len[i]); field f of
+ * the k of a row is group groups[f].  val / start: n * k words, entry i * k + f as sre_k_extract_select writes it */
+void
+lesim_select(const int64_t *recs, uint32_t slots, uint64_t n, int64_t declined, int all, const uint64_t *st, const uint64_t *len,
+             const uint32_t *groups, uint32_t k, uint64_t *val, uint64_t *start)
+{
+    for (uint64_t i = 0; i < n; i++) {
+        for (uint32_t f = 0; f < k; f++) {
+            sre_sel_extract_entry(recs + i * slots, declined, all, st[i], len[i], f, k, groups[f], val + i * k + f, start + i * k + f);
+        }
+    }
+}
 
 /* the whole gather.  off[0 .. nent], starts[0 .. nent - 1] as the runtime holds them.  *windowed / *global = tiles
  * that took the LDS window / the global table.  Returns the accesses outside the extents. */

@@ -4,9 +4,12 @@
  * the kernel's table slices and its LDS window rule, over host copies of the three 16-byte aligned extents: the
  * source, the literal block and the output.  Every source and literal byte read and every output byte written is
  * counted, so tests/test_lines_subst_model.py can assert where the kernel may touch memory.  The cut at a line
- * boundary is the header's; the lines in front of it are counted as the kernels count them, by last entries.
+ * boundary is the header's; the lines in front of it are counted as the kernels count them, by last entries.  The select
+ * rule that fills the piece table from the lines' records (sregex_amd/csrc/sre_lines_select.h) is exported as the kernel
+ * and the host route call it.
  */
 #include "sre_lines_gather.h"
+#include "sre_lines_select.h"
 #include <stdint.h>
 #include <string.h>
 #include <vector>
@@ -85,6 +88,31 @@ lssim_count(const uint64_t *off, uint64_t p, uint64_t lines)
     uint64_t k = 0;
     for (uint64_t j = 0; j < lines * p; j++) k += (j % p == p - 1 && off[j + 1] > off[j]) ? 1 : 0;
     return k;
+}
+
+/* the select rule over n lines: line i has the record recs[i * slots ..] and the extent [st[i], st[i] + len[i]); piece q of
+ * the np of the template is group pg[q], or with pg[q] < 0 the plen[q] bytes at poff[q] of the literal block.  val /
+ * start: n * (np + 2) words, entry i * (np + 2) + f as sre_k_subst_select writes it.  -1: more pieces than a template has */
+int
+lssim_select(const int64_t *recs, uint32_t slots, uint64_t n, int64_t declined, int all, const uint64_t *st, const uint64_t *len,
+             const int32_t *pg, const uint32_t *poff, const uint32_t *plen, uint32_t np, uint64_t *val, uint64_t *start)
+{
+    sre_subst_pieces_t pc;
+    if (np > SRE_SUBST_MAX_PIECES) return -1;
+    memset(&pc, 0, sizeof(pc));
+    pc.np = np;
+    for (uint32_t q = 0; q < np; q++) {
+        pc.g[q] = (int16_t) pg[q];
+        pc.off[q] = (uint16_t) poff[q];
+        pc.len[q] = (uint16_t) plen[q];
+    }
+    const uint32_t P = np + 2;
+    for (uint64_t i = 0; i < n; i++) {
+        for (uint32_t f = 0; f < P; f++) {
+            sre_sel_subst_entry(recs + i * slots, declined, all, st[i], len[i], f, &pc, val + i * P + f, start + i * P + f);
+        }
+    }
+    return 0;
 }
 
 /* the whole gather.  off[0 .. nent], starts[0 .. nent - 1] as the runtime holds them.  *windowed / *global = tiles

@@ -14,6 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 _u64, _u32 = ctypes.c_uint64, ctypes.c_uint32
 _p64, _p32, _p8 = ctypes.POINTER(_u64), ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_uint8)
+_i64 = ctypes.c_int64
+_pi64 = ctypes.POINTER(_i64)
 FILL = 0xA5
 
 
@@ -23,7 +25,8 @@ def esim():
     os.makedirs(out, exist_ok=True)
     so = os.path.join(out, "liblinesextractsim.so")
     csrc = os.path.join(ROOT, "sregex_amd", "csrc")
-    deps = [os.path.join(HERE, "lines_extract_sim.cpp"), os.path.join(csrc, "sre_lines_gather.h")]
+    deps = [os.path.join(HERE, "lines_extract_sim.cpp"), os.path.join(csrc, "sre_lines_gather.h"),
+            os.path.join(csrc, "sre_lines_select.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
         subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", so, deps[0], "-I" + csrc])
     L = ctypes.CDLL(so)
@@ -35,6 +38,8 @@ def esim():
     L.lesim_gather.restype = _u64
     L.lesim_gather.argtypes = [_p64, _p64, _u64, _u64, _u32, _u32, _u32, _u32, ctypes.c_char_p, _u64, _p8, _u64, _p32, _p32,
                                _p64, _p64]
+    L.lesim_select.restype = None
+    L.lesim_select.argtypes = [_pi64, _u32, _u64, _i64, ctypes.c_int, _p64, _p64, _p32, _u32, _p64, _p64]
     return L
 
 
@@ -262,3 +267,77 @@ def test_random_tables(esim):
             spans.append(sp if rng.random() < p else None)
         run(esim, lines, spans, K, rng.randrange(16), rng.randrange(16), bool(k & 1),
             (None, lambda need, rows: rng.randrange(0, need + 2)))
+
+
+# ---- the select rule (sregex_amd/csrc/sre_lines_select.h): the entry table from the lines' records ----
+
+DECLINED, ERROR = -5, -1        # SRE_DECLINED, SRE_ERROR (include/sregex/sregex.h)
+
+
+def make_records(gspans, lens, G, rc=0):
+    """records of 2 + 2 (G + 1) words as the scanner leaves them: rc, a word no rule reads, the match (group 0) and
+    groups 1 .. G ((-1, -1): unset).  None: a line without a match, whose spans hold numbers that must not be read"""
+    recs = []
+    for sp, n in zip(gspans, lens):
+        if sp is None:
+            recs += [DECLINED, 77] + [0, 0] * (G + 1)
+        else:
+            recs += [rc, 77, 0, n] + [x for g in sp for x in (g if g is not None else (-1, -1))]
+    return recs, 4 + 2 * G
+
+
+def select_words(esim, recs, slots, st, lens, all_lines, groups):
+    n, K = len(st), len(groups)
+    val, start = (_u64 * (n * K))(), (_u64 * (n * K))()
+    esim.lesim_select((_i64 * len(recs))(*recs), slots, n, DECLINED, int(all_lines), (_u64 * n)(*st), (_u64 * n)(*lens),
+                      (_u32 * K)(*groups), K, val, start)
+    return list(val), list(start)
+
+
+@pytest.mark.parametrize("groups", [[2], [3, 1, 2]])
+def test_the_select_rule_writes_the_entry_table(esim, groups):
+    """K = 1 (FIRST and LAST on one entry) and K = 3: lines without a match, unset groups, empty groups at offset 0 and
+    at len, empty lines"""
+    rng = random.Random(46 + len(groups))
+    G = 3
+    lines = [b"", b"", b"abcdef", b"abcdef", b"xy", text(rng, 9)]
+    gspans = [[(0, 0)] * 3, None, [(0, 0), (6, 6), (2, 5)], [None, (1, 3), None], None, [None, None, None]]
+    for _ in range(6):
+        ln = text(rng, rng.randrange(0, 30))
+        sp = []
+        for _ in range(G):
+            a = rng.randrange(0, len(ln) + 1)
+            sp.append(None if rng.random() < 0.25 else (a, rng.randrange(a, len(ln) + 1)))
+        lines.append(ln)
+        gspans.append(sp if rng.random() < 0.7 else None)
+    lens = [len(ln) for ln in lines]
+    st = [sum(lens[:i]) + i for i in range(len(lines))]
+    recs, slots = make_records(gspans, lens, G)
+    spans = [None if sp is None else [sp[g - 1] for g in groups] for sp in gspans]
+    for all_lines in (False, True):
+        val, starts, _ = entry_table(esim, lines, spans, len(groups), all_lines)
+        assert select_words(esim, recs, slots, st, lens, all_lines, groups) == (val, starts), (groups, all_lines)
+
+
+def test_the_select_rule_on_hostile_records(esim):
+    """spans no scanner should leave, and an rc that is neither a regex id nor SRE_DECLINED: the literal words, and no
+    start word outside its line"""
+    LAST, UNSET, FIRST = esim.lesim_flag_last(), esim.lesim_flag_unset(), esim.lesim_flag_first()
+    n, both = 10, FIRST | LAST
+    # (rc, the span of group 1) -> (val, start - st) of the one entry
+    unset = (1, UNSET | both)
+    cases = [((0, (-3, 4)), unset), ((0, (5, 3)), unset), ((0, (2, n + 1)), unset), ((0, (2, 2 ** 62)), unset),
+             ((0, (-2 ** 63, 2 ** 63 - 1)), unset), ((0, (-1, -1)), unset), ((0, (n, n)), (1, n | both)),
+             ((0, (0, n)), (n + 1, both)), ((ERROR, (2, 5)), (4, 2 | both)), ((ERROR, (2, n + 1)), unset),
+             ((7, (n + 1, n + 1)), unset), ((DECLINED, (2, 5)), (0, UNSET | both))]
+    st = [100 + 40 * i for i in range(len(cases))]
+    recs = [x for (rc, sp), _ in cases for x in (rc, 77, 0, n) + sp]
+    for all_lines in (False, True):
+        val, start = select_words(esim, recs, 6, st, [n] * len(cases), all_lines, [1])
+        for i, ((rc, sp), (v, w)) in enumerate(cases):
+            want = (1 if all_lines and rc == DECLINED else v, st[i] + w)
+            assert (val[i], start[i]) == want, (rc, sp, all_lines, val[i], hex(start[i]))
+            assert st[i] <= start[i] & (FIRST - 1) <= st[i] + n
+    # two fields of one line: FIRST on the one, LAST on the other, each with its own verdict
+    val, start = select_words(esim, [0, 77, 0, n, 4, n + 1, 4, n], 8, [100], [n], False, [1, 2])
+    assert (val, start) == ([1, n - 4 + 1], [100 | UNSET | FIRST, 104 | LAST])

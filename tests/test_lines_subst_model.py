@@ -15,6 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 _u64, _u32 = ctypes.c_uint64, ctypes.c_uint32
 _p64, _p32, _p8 = ctypes.POINTER(_u64), ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_uint8)
+_i64 = ctypes.c_int64
+_pi64 = ctypes.POINTER(_i64)
 FILL = 0xA5
 
 
@@ -24,7 +26,8 @@ def ssim():
     os.makedirs(out, exist_ok=True)
     so = os.path.join(out, "liblinessubstsim.so")
     csrc = os.path.join(ROOT, "sregex_amd", "csrc")
-    deps = [os.path.join(HERE, "lines_subst_sim.cpp"), os.path.join(csrc, "sre_lines_gather.h")]
+    deps = [os.path.join(HERE, "lines_subst_sim.cpp"), os.path.join(csrc, "sre_lines_gather.h"),
+            os.path.join(csrc, "sre_lines_select.h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
         subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-Wall", "-shared", "-fPIC", "-o", so, deps[0], "-I" + csrc])
     L = ctypes.CDLL(so)
@@ -38,6 +41,9 @@ def ssim():
     L.lssim_gather.restype = _u64
     L.lssim_gather.argtypes = [_p64, _p64, _u64, _u64, _u32, _u32, _u32, ctypes.c_char_p, _u64, ctypes.c_char_p, _u64, _p8, _u64,
                                _p32, _p32, _p32, _p64, _p64]
+    L.lssim_select.restype = ctypes.c_int
+    L.lssim_select.argtypes = [_pi64, _u32, _u64, _i64, ctypes.c_int, _p64, _p64, ctypes.POINTER(ctypes.c_int32), _p32, _p32, _u32,
+                               _p64, _p64]
     return L
 
 
@@ -353,3 +359,70 @@ def test_random_tables(ssim):
             spans.append(sp if rng.random() < p else None)
         run(ssim, lines, spans, template, rng.randrange(16), rng.randrange(16), bool(k & 1),
             (None, lambda need, rows: rng.randrange(0, need + 2)))
+
+
+# ---- the select rule (sregex_amd/csrc/sre_lines_select.h): the piece table from the lines' records ----
+
+DECLINED, ERROR = -5, -1        # SRE_DECLINED, SRE_ERROR (include/sregex/sregex.h)
+
+
+def select_words(ssim, recs, slots, st, lens, all_lines, template):
+    """the compiled rule over records of `slots` words (rc, a word no rule reads, then the spans of groups 0, 1, ..)"""
+    pg, poff, plen, at = [], [], [], 0
+    for pc in template:
+        pg.append(-1 if isinstance(pc, bytes) else pc)
+        poff.append(at if isinstance(pc, bytes) else 0)
+        plen.append(len(pc) if isinstance(pc, bytes) else 0)
+        at += len(pc) if isinstance(pc, bytes) else 0
+    n, np_, P = len(st), len(template), len(template) + 2
+    val, start = (_u64 * (n * P))(), (_u64 * (n * P))()
+    assert ssim.lssim_select((_i64 * len(recs))(*recs), slots, n, DECLINED, int(all_lines), (_u64 * n)(*st), (_u64 * n)(*lens),
+                             (ctypes.c_int32 * max(np_, 1))(*pg), (_u32 * max(np_, 1))(*poff), (_u32 * max(np_, 1))(*plen), np_,
+                             val, start) == 0
+    return list(val), list(start)
+
+
+@pytest.mark.parametrize("template", [[], [b"<", 1, b"=", 2, b">"]])
+def test_the_select_rule_writes_the_piece_table(ssim, template):
+    """an empty template (P = 2) and one with literals, a set group and an unset group: lines without a match, empty
+    groups at offset 0 and at len, empty lines"""
+    rng = random.Random(70 + len(template))
+    lines = [b"", b"", b"abcdef", b"abcdef", b"xy", b"abcdef"]
+    spans = [[(0, 0), (0, 0), (0, 0)], None, [(0, 6), (0, 0), (6, 6)], [(2, 4), (2, 3), None], None, [(6, 6), None, None]]
+    for _ in range(6):
+        ln, sp = matched_line(rng, [rng.choice([None, 0, 1, 5]), rng.choice([None, 0, 2])])
+        lines.append(ln)
+        spans.append(sp if rng.random() < 0.7 else None)
+    lens = [len(ln) for ln in lines]
+    st = [sum(lens[:i]) + i for i in range(len(lines))]
+    recs = []
+    for sp in spans:
+        recs += [DECLINED, 77] + [0, 0] * 3 if sp is None else [0, 77] + [x for g in sp for x in (g if g is not None else (-1, -1))]
+    for all_lines in (False, True):
+        val, starts, _, _ = piece_table(ssim, lines, spans, template, all_lines)
+        assert select_words(ssim, recs, 8, st, lens, all_lines, template) == (val, starts), (template, all_lines)
+
+
+def test_the_select_rule_on_hostile_records(ssim):
+    """spans no scanner should leave, in match 0 (the line is copied whole, its pieces are empty) and in a group (the
+    piece is unset), and an rc that is neither a regex id nor SRE_DECLINED: the literal words, and no start word outside
+    its line or the literal block"""
+    LAST, UNSET, FIRST, LIT = ssim.lssim_flag_last(), ssim.lssim_flag_unset(), ssim.lssim_flag_first(), ssim.lssim_flag_literal()
+    n, template = 10, [b"ab", 1]
+    # (rc, match 0, group 1) -> the four (val, start - st) of the line; a literal's start is its offset in the block
+    whole = [(n, FIRST | UNSET), (0, LIT), (0, UNSET), (1, n | LAST)]
+    piece_unset = [(2, FIRST), (2, LIT), (0, UNSET), (n - 6 + 1, 6 | LAST)]
+    bad = [(-3, 4), (5, 3), (2, n + 1), (2, 2 ** 62), (-2 ** 63, 2 ** 63 - 1), (-1, -1)]
+    cases = [((0, m, (2, 3)), whole) for m in bad] + [((0, (2, 6), g), piece_unset) for g in bad]
+    cases += [((ERROR, (2, 6), (3, 5)), [(2, FIRST), (2, LIT), (2, 3), (5, 6 | LAST)]), ((ERROR, (2, n + 1), (3, 5)), whole),
+              ((0, (n, n), (n, n)), [(n, FIRST), (2, LIT), (0, n), (1, n | LAST)]),
+              ((0, (0, 0), (0, 0)), [(0, FIRST), (2, LIT), (0, 0), (n + 1, LAST)]), ((DECLINED, (2, 6), (3, 5)), whole)]
+    st = [100 + 40 * i for i in range(len(cases))]
+    recs = [x for (rc, m, g), _ in cases for x in (rc, 77) + m + g]
+    for all_lines in (False, True):
+        val, start = select_words(ssim, recs, 6, st, [n] * len(cases), all_lines, template)
+        for i, ((rc, m, g), words) in enumerate(cases):
+            for f, (v, w) in enumerate(words):
+                want = (0 if rc == DECLINED and not all_lines else v, w if w & LIT else st[i] + w)
+                assert (val[4 * i + f], start[4 * i + f]) == want, (rc, m, g, f, all_lines, val[4 * i + f], hex(start[4 * i + f]))
+                assert w & LIT or st[i] <= start[4 * i + f] & (LIT - 1) <= st[i] + n
