@@ -697,6 +697,109 @@ SRE_API int sre_hip_tally_sums_lines(sre_hip_scanner_t *sc, const void *d_buf, s
  * it; 0: not a number, *value is untouched */
 SRE_API int sre_hip_tally_number(const void *text, size_t len, int64_t *value);
 
+/* ---- key sets and the line lookup: select the lines whose captured key is in a device key set ---- */
+
+typedef struct sre_hip_keyset_s sre_hip_keyset_t;
+
+/*
+ * A key set: the distinct keys of a DICTIONARY, kept on the device for any number of lookups
+ * (`grep -F -f keys` on a field, `WHERE ip IN (...)`, awk's `NR==FNR{s[$1];next} $3 in s`).
+ *
+ * Row format.  d_rows is a device pointer at any alignment to len bytes in the row format that
+ * sre_hip_extract_lines and sre_hip_tally_lines write: field 0, fsep, .., field K - 1, delim, with
+ * K = nfields.  The rows are split by the split rule of line mode: a final row without delim is a
+ * row, and len == 0 is the empty set, which is valid.  A row must hold exactly nfields - 1 bytes
+ * equal to fsep; with nfields == 1 nothing is split and fsep is ignored.  When a row breaks that
+ * rule, create returns NULL with one diagnostic line on stderr that names the LOWEST such row.
+ *
+ * create returns NULL without touching the device when nfields < 1 or nfields >
+ * SRE_HIP_EXTRACT_MAX_FIELDS, when fsep or delim is outside 0 .. 255, or when fsep == delim with
+ * nfields > 1; and NULL behind the count of the rows when there are more than 2^30 of them.
+ *
+ * Ownership.  The set keeps its own copy of the rows: d_rows may be freed or overwritten as soon as
+ * create has returned.  create is synchronous on hip_stream.  The set is immutable afterwards;
+ * any number of scanners and streams of the same device may use it at once.  Its device memory
+ * (sre_hip_keyset_device_bytes: the copy, 16 bytes per field of every row, 8 bytes per slot) is
+ * freed by sre_hip_keyset_destroy; a NULL set is ignored there.
+ *
+ * Keys and ids.  The key of a row is the tuple of its field texts, compared as the tally compares
+ * keys: every length first, then the bytes, so ("ab", "c") and ("a", "bc") differ.  The ID of a
+ * key is the lowest row number that carries it; sre_hip_keyset_distinct is the number of keys,
+ * sre_hip_keyset_rows the number of rows.  The table has sre_hip_keyset_slots words, the power of
+ * two >= 2 * rows and at least 1024.
+ *
+ * sre_hip_keyset_hash is the set's hash of one row (its text WITHOUT the delimiter) on the host;
+ * it needs no device.  A row's home slot, where its search begins and from where it moves up one
+ * word at a time around the table's end, is hash & (slots - 1): a caller may shard keys by it.
+ * It returns 0 for arguments out of range and for a row that breaks the field rule.
+ * SRE_HIP_KEYSET_HASH_BITS=n (test knob, read at create) keeps the low n bits of the hash in
+ * front of the index; a lookup takes the mask from the set.
+ *
+ * Not offered: mutable sets (build a new one), a value column joined into the output, caseless
+ * keys, rows whose fields contain fsep.
+ */
+SRE_API sre_hip_keyset_t *sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields,
+    int fsep, int delim, void *hip_stream);
+SRE_API void sre_hip_keyset_destroy(sre_hip_keyset_t *ks);
+SRE_API size_t sre_hip_keyset_rows(const sre_hip_keyset_t *ks);
+SRE_API size_t sre_hip_keyset_distinct(const sre_hip_keyset_t *ks);
+SRE_API size_t sre_hip_keyset_fields(const sre_hip_keyset_t *ks);
+SRE_API size_t sre_hip_keyset_slots(const sre_hip_keyset_t *ks);
+SRE_API size_t sre_hip_keyset_device_bytes(const sre_hip_keyset_t *ks);
+SRE_API uint64_t sre_hip_keyset_hash(const void *row, size_t len, size_t nfields, int fsep);
+
+typedef struct {
+    size_t nlines;      /* lines of the buffer */
+    size_t nkeyed;      /* lines with a match, i.e. with a key */
+    size_t nmembers;    /* of those, lines whose key is in the set */
+    size_t nselected;   /* lines the flags select */
+    size_t need_bytes;  /* bytes all of them take */
+    size_t nwritten;    /* selected lines written (whole lines only) */
+    size_t out_bytes;
+} sre_hip_lookup_info_t;
+
+/*
+ * Line lookup: the lines of d_buf whose captured key is in the set (the semi-join), or with
+ * SRE_HIP_LINES_INVERT the lines with a key that is not (the anti-join).  The split of d_buf, the
+ * matching of every line, the routing to an engine, the batching, the diagnostics, the demand for
+ * an SRE_HIP_PIKE_FIRST scanner (Thompson and COUNT scanners return -1 with a diagnostic) and the
+ * range rule of groups are exactly those of sre_hip_extract_lines on the same (sc, d_buf, len,
+ * delim); the overlap check of d_out is the filter's.  ks == NULL and ngroups !=
+ * sre_hip_keyset_fields(ks) return -1.
+ *
+ * Selection.  A line is KEYED when it has a match; its key is the tuple of the texts of the capture
+ * groups `groups` of its first match, an unset group an empty field.  A keyed line is a MEMBER
+ * when that tuple equals the key of some row of the set.  flags == 0 selects the members,
+ * SRE_HIP_LINES_INVERT the keyed lines that are not members.  A line without a match has no key
+ * and is never selected.  Any other flag bit, SRE_HIP_LINES_ALL included, returns -1.
+ *
+ * Output, truncation, the sizing call and d_index are those of sre_hip_filter_lines byte for byte:
+ * the selected lines in line order, each followed by one delim, whole lines only, nothing at or
+ * beyond out_bytes touched, d_out == NULL with out_cap == 0 sizes the output, index rows of the
+ * filter's four words.
+ *
+ * d_keyid is an optional DEVICE array: d_keyid[i], i < min(keyid_cap, nlines), is the id of the
+ * line's key in the set (a row number of the dictionary) for a member, -1 for a keyed line that is
+ * not a member, -2 for a line without a key.  It does not depend on flags or out_cap; the
+ * dictionary row of written line r is d_keyid[index[r][0]].  info->nkeyed and info->nmembers are
+ * totals over the buffer whatever out_cap is.  len == 0 gives zeros and success; an empty set
+ * makes no line a member.
+ *
+ * The call is synchronous and all its work runs on hip_stream; the host waits exactly as often as
+ * in sre_hip_filter_lines.  The set is only read.  Beyond what sre_hip_filter_lines takes, a
+ * scanner keeps the 16 bytes per line and key group that sre_hip_tally_sums_lines keeps per value
+ * column (the same grow-only memory, freed with the scanner).  Not offered: routing by dictionary
+ * row (d_keyid plus the route's partition is the obvious follow-up), a value column joined into
+ * the output, every match of a line, caseless keys, Thompson and COUNT scanners, stream sets.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, const sre_hip_keyset_t *ks, int flags,
+    void *d_out, size_t out_cap,
+    sre_int_t *d_keyid, size_t keyid_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_lookup_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

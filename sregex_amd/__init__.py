@@ -103,6 +103,16 @@ API = {
                                                 ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _sz, _vp, _sz, _vp, _sz,
                                                 _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_tally_number": (ctypes.c_int, [ctypes.c_char_p, _sz, ctypes.POINTER(ctypes.c_int64)]),
+    "sre_hip_keyset_create": (_vp, [_vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]),
+    "sre_hip_keyset_destroy": (None, [_vp]),
+    "sre_hip_keyset_rows": (_sz, [_vp]),
+    "sre_hip_keyset_distinct": (_sz, [_vp]),
+    "sre_hip_keyset_fields": (_sz, [_vp]),
+    "sre_hip_keyset_slots": (_sz, [_vp]),
+    "sre_hip_keyset_device_bytes": (_sz, [_vp]),
+    "sre_hip_keyset_hash": (ctypes.c_uint64, [ctypes.c_char_p, _sz, _sz, ctypes.c_int]),
+    "sre_hip_lookup_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int, _vp,
+                                            _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -185,6 +195,60 @@ def tally_number(text):
     if load_library().sre_hip_tally_number(text, len(text), ctypes.byref(value)) != 1:
         return None
     return value.value
+
+
+def keyset_hash(row, nfields=1, fsep=0x09):
+    """sre_hip_keyset_hash: the hash a KeySet of nfields fields gives the row `row` (bytes, without its delimiter); the
+    row's home slot in a set is keyset_hash(row) & (set.slots - 1).  0 for a row that does not hold nfields fields.
+    Needs no device."""
+    row = bytes(row)
+    return load_library().sre_hip_keyset_hash(row, len(row), nfields, fsep)
+
+
+class KeySet:
+    """sre_hip_keyset_*: the distinct keys of a dictionary of rows (field 0, fsep, .., field K - 1, delim: what
+    Scanner.extract_lines and Scanner.tally_lines write) in the device buffer (ptr, length), kept on the device for
+    Scanner.lookup_lines.  The set copies the rows: the buffer may be freed once the constructor has returned.  A key's
+    id is the lowest row that carries it.  Raises ValueError when the arguments are out of range or a row does not hold
+    nfields fields."""
+
+    def __init__(self, ptr, length, nfields=1, fsep=0x09, delim=0x0A, hip_stream=None, lib=None):
+        self.lib = lib or load_library()
+        self.h = self.lib.sre_hip_keyset_create(ptr, length, nfields, fsep, delim, hip_stream)
+        if not self.h:
+            raise ValueError("sre_hip_keyset_create failed (arguments out of range, a row without %d fields, or no device)"
+                             % nfields)
+
+    def close(self):
+        if self.h:
+            self.lib.sre_hip_keyset_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def rows(self):
+        return self.lib.sre_hip_keyset_rows(self.h)
+
+    @property
+    def distinct(self):
+        return self.lib.sre_hip_keyset_distinct(self.h)
+
+    @property
+    def fields(self):
+        return self.lib.sre_hip_keyset_fields(self.h)
+
+    @property
+    def slots(self):
+        return self.lib.sre_hip_keyset_slots(self.h)
+
+    @property
+    def device_bytes(self):
+        return self.lib.sre_hip_keyset_device_bytes(self.h)
 
 
 def _capture_stdout(fn):
@@ -588,6 +652,24 @@ class Scanner:
             raise RuntimeError("sre_hip_tally_sums_lines failed")
         return res
 
+    def lookup_lines(self, ptr, length, out_ptr, out_cap, groups, keyset, delim=0x0A, invert=False, keyid_ptr=None, keyid_cap=0,
+                     index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_lookup_lines: the matching lines of the device buffer (ptr, length) whose key, the tuple of the texts of
+        the capture groups `groups` of the first match, is in the KeySet `keyset` (with invert: is not in it), each
+        followed by one delimiter, compacted in order into the device buffer (out_ptr, out_cap) as filter_lines writes
+        them.  keyid_ptr: an optional device array of keyid_cap int64, per line the id of its key in the set (a row of the
+        dictionary), -1 for a key the set does not hold, -2 for a line without a match; index_ptr: the filter's index
+        rows.  The scanner's mode must be HIP_PIKE_FIRST.  Returns LookupInfo(nlines, nkeyed, nmembers, nselected,
+        need_bytes, nwritten, out_bytes)."""
+        groups = list(groups)
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        info = (_sz * 7)()
+        if self.lib.sre_hip_lookup_lines(self.h, ptr, length, delim, arr, len(groups), keyset.h if keyset is not None else None,
+                                         HIP_LINES_INVERT if invert else 0, out_ptr, out_cap, keyid_ptr, keyid_cap, index_ptr,
+                                         index_cap, info, hip_stream) != 0:
+            raise RuntimeError("sre_hip_lookup_lines failed")
+        return LookupInfo(*info)
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -607,6 +689,7 @@ FilterInfo = collections.namedtuple("FilterInfo", "nlines nselected need_bytes n
 RouteBucket = collections.namedtuple("RouteBucket", "nlines offset bytes")
 ContextInfo = collections.namedtuple("ContextInfo", "nlines nmatched nselected ngroups need_bytes nwritten out_bytes")
 TallyInfo = collections.namedtuple("TallyInfo", "nlines nselected nkeys need_bytes nwritten out_bytes")
+LookupInfo = collections.namedtuple("LookupInfo", "nlines nkeyed nmembers nselected need_bytes nwritten out_bytes")
 
 
 class TallyInfoStruct(ctypes.Structure):

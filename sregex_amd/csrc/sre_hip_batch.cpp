@@ -24,6 +24,7 @@
 #include "sre_lines_route.h"
 #include "sre_lines_tally.h"
 #include "sre_lines_sums.h"
+#include "sre_lines_keyset.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
 #include <stddef.h>
@@ -2492,6 +2493,180 @@ sre_hip_tally_number(const void *text, size_t len, int64_t *value)
  * lit (SRE_SUBST_MAX_LITERAL bytes).  $digits and ${digits} are groups, $$ is one '$', every other byte is literal and
  * adjacent literals are one piece.  -1: a '$' in front of anything else, a group above max_group, too many pieces or
  * literal bytes */
+/* ---- the key set and the line lookup (rules in sre_lines_keyset.h) ---- */
+
+struct sre_hip_keyset_s {
+    uint8_t  *d_rows;       /* the set's copy of the dictionary */
+    uint64_t *d_fstart;     /* rows x k field offsets into it */
+    uint64_t *d_flen;       /* ... and lengths */
+    uint64_t *d_tab;        /* nslots words: SRE_LT_EMPTY or the lowest row of the slot's key */
+    uint64_t  rows, distinct, nslots, hash_mask;
+    uint32_t  k;
+    size_t    bytes;        /* device memory held */
+};
+
+/* the hash bits the set's table index keeps: SRE_HIP_KEYSET_HASH_BITS (test knob, read at create; 0 .. 64), else all */
+static uint64_t
+keyset_hash_mask(void)
+{
+    const char *e = getenv("SRE_HIP_KEYSET_HASH_BITS");
+    if (e == NULL || *e == 0) return ~(uint64_t) 0;
+    return sre_lt_hash_mask(atoi(e));
+}
+
+extern "C" SRE_API void
+sre_hip_keyset_destroy(sre_hip_keyset_t *ks)
+{
+    if (ks == NULL) return;
+    if (ks->d_rows) (void) hipFree(ks->d_rows);
+    if (ks->d_fstart) (void) hipFree(ks->d_fstart);
+    if (ks->d_flen) (void) hipFree(ks->d_flen);
+    if (ks->d_tab) (void) hipFree(ks->d_tab);
+    free(ks);
+}
+
+extern "C" SRE_API sre_hip_keyset_t *
+sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields, int fsep, int delim, void *hip_stream)
+{
+    if (nfields < 1 || nfields > SRE_HIP_EXTRACT_MAX_FIELDS || fsep < 0 || fsep > 255 || delim < 0 || delim > 255
+        || (nfields > 1 && fsep == delim) || (len != 0 && d_rows == NULL))
+    {
+        return NULL;
+    }
+    hipStream_t       stream = static_cast<hipStream_t>(hip_stream);
+    sre_hip_keyset_t *ks = static_cast<sre_hip_keyset_t *>(calloc(1, sizeof(*ks)));
+    /* what only the build needs: the split's words and tile counts, the row ends, and two words of its own */
+    struct Words {
+        sre_lines_info_t li;
+        uint64_t         bad, distinct;
+    };
+    Words          *d_w = NULL;
+    uint64_t       *d_tiles = NULL, *d_ends = NULL;
+    uint64_t        h[2] = {0, 0};
+    const uint64_t  ntiles = (len + SRE_LINES_TILE_BYTES - 1) / SRE_LINES_TILE_BYTES;
+    size_t          nent = 0;
+    if (ks == NULL) return NULL;
+    ks->k = (uint32_t) nfields;
+    ks->hash_mask = keyset_hash_mask();
+    ks->nslots = sre_lk_nslots(0);
+    if (len != 0) {
+        /* (16 bytes behind the copy: the split loads whole aligned chunks) */
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_rows), len + 16));
+        SRE_HIP_TRY(hipMemcpyAsync(ks->d_rows, d_rows, len, hipMemcpyDeviceToDevice, stream));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_w), sizeof(Words)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_tiles), ntiles * sizeof(uint64_t)));
+        SRE_HIP_TRY(sre_launch_lines_count(ks->d_rows, len, (uint32_t) delim, d_tiles, &d_w->li, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&h[0], &d_w->li.nlines, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        ks->rows = h[0];
+        if (ks->rows > SRE_LK_MAX_ROWS) {
+            fprintf(stderr, "[sregex-hip] key set: %llu rows, at most 2^30\n", (unsigned long long) ks->rows);
+            goto hip_failed;
+        }
+        nent = (size_t) ks->rows * ks->k;
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_ends), ks->rows * sizeof(uint64_t)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_fstart), nent * sizeof(uint64_t)));
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_flen), nent * sizeof(uint64_t)));
+        SRE_HIP_TRY(sre_launch_lines_write(ks->d_rows, len, (uint32_t) delim, d_tiles, d_ends, stream));
+        SRE_HIP_TRY(hipMemsetAsync(&d_w->bad, 0xFF, sizeof(uint64_t), stream));         /* SRE_LK_NO_ROW */
+        SRE_HIP_TRY(hipMemsetAsync(&d_w->distinct, 0, sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_keyset_fields(ks->d_rows, d_ends, ks->rows, ks->k, (uint32_t) fsep, ks->d_fstart, ks->d_flen, &d_w->bad,
+                                             stream));
+        /* (the insert reads the fields of every row: it is queued only when every row has them) */
+        SRE_HIP_TRY(hipMemcpyAsync(&h[0], &d_w->bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        if (h[0] != SRE_LK_NO_ROW) {
+            fprintf(stderr, "[sregex-hip] key set: row %llu does not hold %u fields\n", (unsigned long long) h[0], ks->k);
+            goto hip_failed;
+        }
+        ks->nslots = sre_lk_nslots(ks->rows);
+    }
+    SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_tab), ks->nslots * sizeof(uint64_t)));
+    SRE_HIP_TRY(hipMemsetAsync(ks->d_tab, 0xFF, ks->nslots * sizeof(uint64_t), stream));        /* SRE_LT_EMPTY */
+    if (ks->rows != 0) {
+        SRE_HIP_TRY(sre_launch_keyset_insert(ks->d_rows, ks->d_fstart, ks->d_flen, ks->rows, ks->k, ks->nslots, ks->hash_mask,
+                                             ks->d_tab, &d_w->distinct, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(&h[1], &d_w->distinct, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    }
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    ks->distinct = h[1];
+    ks->bytes = (len ? len + 16 : 0) + 2 * nent * sizeof(uint64_t) + ks->nslots * sizeof(uint64_t);
+    if (d_w) (void) hipFree(d_w);
+    if (d_tiles) (void) hipFree(d_tiles);
+    if (d_ends) (void) hipFree(d_ends);
+    return ks;
+hip_failed:
+    (void) hipStreamSynchronize(stream);
+    if (d_w) (void) hipFree(d_w);
+    if (d_tiles) (void) hipFree(d_tiles);
+    if (d_ends) (void) hipFree(d_ends);
+    sre_hip_keyset_destroy(ks);
+    return NULL;
+}
+
+extern "C" SRE_API size_t sre_hip_keyset_rows(const sre_hip_keyset_t *ks) { return ks ? (size_t) ks->rows : 0; }
+extern "C" SRE_API size_t sre_hip_keyset_distinct(const sre_hip_keyset_t *ks) { return ks ? (size_t) ks->distinct : 0; }
+extern "C" SRE_API size_t sre_hip_keyset_fields(const sre_hip_keyset_t *ks) { return ks ? ks->k : 0; }
+extern "C" SRE_API size_t sre_hip_keyset_slots(const sre_hip_keyset_t *ks) { return ks ? (size_t) ks->nslots : 0; }
+extern "C" SRE_API size_t sre_hip_keyset_device_bytes(const sre_hip_keyset_t *ks) { return ks ? ks->bytes : 0; }
+
+/* the set's hash on the host: the row's fields by the field rule, then the tally's hash over them */
+extern "C" SRE_API uint64_t
+sre_hip_keyset_hash(const void *row, size_t len, size_t nfields, int fsep)
+{
+    if (nfields < 1 || nfields > SRE_HIP_EXTRACT_MAX_FIELDS || fsep < 0 || fsep > 255 || (len != 0 && row == NULL)) return 0;
+    uint64_t               fstart[SRE_HIP_EXTRACT_MAX_FIELDS], flen[SRE_HIP_EXTRACT_MAX_FIELDS];
+    const HostText         t = {static_cast<const uint8_t *>(row)};
+    const sre_lk_dict_keys keys = {t.p, fstart, flen, (uint32_t) nfields};
+    if (!sre_lk_row_fields(t, 0, len, (uint32_t) nfields, (uint32_t) fsep, fstart, flen)) return 0;
+    return sre_lt_hash(keys, 0);
+}
+
+/* The line lookup: the filter's call in mode 0 with the key groups as its value groups, so that every
+ * route leaves the per-line values and the key table; then on the device the probe of every keyed line in the set's table,
+ * which writes the key ids and clears the values of the lines the selection rule drops; then the filter's scan, cut, one
+ * read (its four words and the lookup's two), gather and index. */
+extern "C" SRE_API int
+sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+    const sre_hip_keyset_t *ks, int flags, void *d_out, size_t out_cap, sre_int_t *d_keyid, size_t keyid_cap, sre_int_t *d_index,
+    size_t index_cap, sre_hip_lookup_info_t *info, void *hip_stream)
+{
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    if (ks == NULL || (flags & ~SRE_HIP_LINES_INVERT) != 0 || groups == NULL || ngroups < 1 || ngroups != ks->k
+        || (keyid_cap != 0 && d_keyid == NULL))
+    {
+        return -1;
+    }
+    /* (the sink's row rule is the filter's mode 0 whatever the flags are: the probe applies them) */
+    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
+    if (!sink_first_match(sc, "line lookup", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
+    sink.vgroups = &gr;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_lookup_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        static_assert(offsetof(sre_lines_info_t, knmembers) == offsetof(sre_lines_info_t, knkeyed) + sizeof(uint64_t),
+                      "knkeyed, knmembers are zeroed as one run");
+        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_keyset_probe(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen, ks->d_tab,
+                                            ks->nslots, ks->hash_mask, (flags & SRE_HIP_LINES_INVERT) != 0, sc->d_fval,
+                                            reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream));
+        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
+        if (sink_read(sc, &sink, n, &res, stream, LINFO(knkeyed), LINFO(knmembers)) != 0) return -1;
+        res.nkeyed = (size_t) sc->h_linfo->knkeyed;
+        res.nmembers = (size_t) sc->h_linfo->knmembers;
+        if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
 static int
 subst_parse(const uint8_t *t, size_t n, int max_group, sre_subst_pieces_t *pc, uint8_t *lit, size_t *lit_len)
 {

@@ -54,6 +54,9 @@ typedef struct {
     uint64_t tsel;          /* lines that have a key */
     uint64_t tclaims;       /* slots of the table claimed */
     uint64_t tover;         /* not 0: more than max_keys distinct keys, or the table is full */
+    /* the line lookup (sre_hip_lookup_lines): two more words, read with the four (zeroed in front of the probe) */
+    uint64_t knkeyed;       /* lines that have a key */
+    uint64_t knmembers;     /* of those, lines whose key is in the set */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -214,6 +217,26 @@ hipError_t sre_launch_tally_numbers(const uint64_t *d_off, const uint64_t *d_sta
  * w % copies, and a last kernel merges the copies into d_sums */
 hipError_t sre_launch_tally_sums(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, uint32_t v,
     const uint32_t *d_lslot, const uint64_t *d_cnt, uint64_t rows, void *d_sums, void *d_copies, uint32_t copies,
+    hipStream_t stream);
+/* ---- the key set and the line lookup (sre_hip_lines_keyset.hip, sre_lines_keyset.h) ---- */
+/* behind the split of the dictionary d_rows (d_ends: its `rows` row ends), a lane per row: the fields of row r by the
+ * field rule into entries r * k + f of d_fstart / d_flen; *d_bad (all ones before) = the lowest row that does not hold
+ * exactly k - 1 bytes fsep */
+hipError_t sre_launch_keyset_fields(const void *d_rows, const uint64_t *d_ends, uint64_t rows, uint32_t k, uint32_t fsep,
+    uint64_t *d_fstart, uint64_t *d_flen, uint64_t *d_bad, hipStream_t stream);
+/* the tally's insert over the dictionary's keys, a lane per row: d_tab (nslots words, all SRE_LT_EMPTY before, nslots a
+ * power of two >= 2 x rows) ends with the lowest row of every key in the key's one slot; *d_distinct (zero before) += the
+ * claims, one add per workgroup */
+hipError_t sre_launch_keyset_insert(const void *d_rows, const uint64_t *d_fstart, const uint64_t *d_flen, uint64_t rows,
+    uint32_t k, uint64_t nslots, uint64_t hash_mask, uint64_t *d_tab, uint64_t *d_distinct, hipStream_t stream);
+/* between the last select pass and sre_launch_filter_offsets, a lane per line: the key of a line with one (d_vval[line * k]
+ * != 0; d_vval / d_vstart: the entry table of sre_launch_extract_select over the key groups) is looked up in the set's
+ * finished table with plain loads; d_keyid[i], i < min(keyid_cap, n), = the row number of the key, -1 without one in the
+ * set, -2 for a line without a key; d_fval[i] stays for a selected line (a member, with invert a keyed line that is not one)
+ * and becomes 0 for every other; info->knkeyed, knmembers (zero before), one add per workgroup each */
+hipError_t sre_launch_keyset_probe(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, uint32_t k,
+    const void *d_rows, const uint64_t *d_fstart, const uint64_t *d_flen, const uint64_t *d_tab, uint64_t nslots,
+    uint64_t hash_mask, int invert, uint64_t *d_fval, int64_t *d_keyid, uint64_t keyid_cap, sre_lines_info_t *d_info,
     hipStream_t stream);
 #ifdef __cplusplus
 }
