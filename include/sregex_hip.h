@@ -735,11 +735,28 @@ typedef struct sre_hip_keyset_s sre_hip_keyset_t;
  * SRE_HIP_KEYSET_HASH_BITS=n (test knob, read at create) keeps the low n bits of the hash in
  * front of the index; a lookup takes the mask from the set.
  *
- * Not offered: mutable sets (build a new one), a value column joined into the output, caseless
- * keys, rows whose fields contain fsep.
+ * Key maps.  sre_hip_keyset_create_map builds a set whose rows carry VALUE COLUMNS behind the key:
+ * a row holds nfields fields under the same field rule (exactly nfields - 1 bytes equal to fsep, the
+ * diagnostic names the lowest bad row), the first nkeys fields are the key, the other nfields -
+ * nkeys fields are value columns 0 .., which sre_hip_join_lines appends to the lines that carry the
+ * key.  It returns NULL without touching the device unless 1 <= nkeys <= nfields <=
+ * SRE_HIP_EXTRACT_MAX_FIELDS, and for everything create refuses.  sre_hip_keyset_create(..,
+ * nfields, ..) is create_map with nkeys == nfields.  sre_hip_keyset_fields is the number of KEY
+ * fields and sre_hip_keyset_values the number of value columns (0 for a plain set), so a map is a
+ * valid argument of sre_hip_lookup_lines; sre_hip_keyset_hash is given the key fields only.  The
+ * id of a key is still the lowest row that carries it, and the VALUES of a key are the values of
+ * that row: the first row wins and later rows of the same key are ignored.  (awk's m[$1]=$2 keeps
+ * the LAST row; sort the dictionary the other way round for that.)  A map remembers its delim and
+ * keeps 16 more bytes per value column of every row, which device_bytes counts.
+ *
+ * Not offered: mutable sets (build a new one), last-row-wins, caseless keys, rows whose fields
+ * contain fsep.
  */
 SRE_API sre_hip_keyset_t *sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields,
     int fsep, int delim, void *hip_stream);
+SRE_API sre_hip_keyset_t *sre_hip_keyset_create_map(const void *d_rows, size_t len, size_t nfields,
+    size_t nkeys, int fsep, int delim, void *hip_stream);
+SRE_API size_t sre_hip_keyset_values(const sre_hip_keyset_t *ks);   /* nfields - nkeys; 0 for a plain set */
 SRE_API void sre_hip_keyset_destroy(sre_hip_keyset_t *ks);
 SRE_API size_t sre_hip_keyset_rows(const sre_hip_keyset_t *ks);
 SRE_API size_t sre_hip_keyset_distinct(const sre_hip_keyset_t *ks);
@@ -789,12 +806,67 @@ typedef struct {
  * in sre_hip_filter_lines.  The set is only read.  Beyond what sre_hip_filter_lines takes, a
  * scanner keeps the 16 bytes per line and key group that sre_hip_tally_sums_lines keeps per value
  * column (the same grow-only memory, freed with the scanner).  Not offered: routing by dictionary
- * row (d_keyid plus the route's partition is the obvious follow-up), a value column joined into
- * the output, every match of a line, caseless keys, Thompson and COUNT scanners, stream sets.
+ * row (d_keyid plus the route's partition is the obvious follow-up), every match of a line,
+ * caseless keys, Thompson and COUNT scanners, stream sets.  The dictionary's value columns joined
+ * into the output are sre_hip_join_lines.
  * Returns 0 on success, -1 on bad arguments or failure.
  */
 SRE_API int sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
     const int *groups, size_t ngroups, const sre_hip_keyset_t *ks, int flags,
+    void *d_out, size_t out_cap,
+    sre_int_t *d_keyid, size_t keyid_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_lookup_info_t *info, void *hip_stream);
+
+/* ---- the line join: append a key map's value columns to each matching line ---- */
+
+enum { SRE_HIP_JOIN_MAX_VALUES = 31 };
+
+/*
+ * Line join: every line of d_buf whose captured key is in the key map ks, with the chosen value
+ * columns of the key's dictionary row behind it (the equi-join: awk's
+ * `NR==FNR{m[$1]=$2;next} ($3 in m){print $0, m[$3]}`, SQL's JOIN); with SRE_HIP_LINES_ALL every
+ * line, the ones without a dictionary row with empty values (LEFT JOIN).
+ *
+ * On the same (sc, d_buf, len, delim, groups, ngroups, ks) the split, the matching, the routing to
+ * an engine, the batching, the diagnostics, the demand for an SRE_HIP_PIKE_FIRST scanner, the range
+ * rule of groups, ngroups == sre_hip_keyset_fields(ks), the overlap check, d_keyid (-1 not a
+ * member, -2 no key; independent of flags and out_cap), info->nkeyed, info->nmembers and the number
+ * of host waits are exactly those of sre_hip_lookup_lines.
+ *
+ * Returns -1 as well: for ks == NULL or a set without value columns; for nvcols < 1, nvcols >
+ * SRE_HIP_JOIN_MAX_VALUES, vcols == NULL or a column outside [0, sre_hip_keyset_values(ks)); for
+ * jsep outside 0 .. 255 or equal to delim; for a delim that is not the one the map was created
+ * with (a value could hold the call's delimiter, and a row would no longer be one line); for any
+ * flag bit other than SRE_HIP_LINES_ALL.  vcols may be in any order and may repeat.
+ *
+ * Selection.  flags == 0 selects the members (the inner join).  SRE_HIP_LINES_ALL selects every
+ * line (the left outer join): a line that is not a member or has no key gets every value field
+ * empty, so row i of the output is line i of the input.  SRE_HIP_LINES_INVERT is not offered: the
+ * anti-join has no values and is sre_hip_lookup_lines.
+ *
+ * Output.  One row per selected line, in line order:
+ *     line bytes, jsep, value vcols[0], jsep, .., value vcols[V - 1], delim
+ * Nothing is escaped.  need_bytes is the sum over the selected lines of len + 1 + the sum of (value
+ * length + 1).  Truncation and the sizing call are the extract's: whole rows only, nothing at or
+ * beyond out_bytes is touched, nothing in front of d_out.
+ *
+ * Index.  A row has 5 + 2 * nvcols words: [0] line, [1] start, [2] len, [3] the row's offset in
+ * d_out, [4] the dictionary row, or -1 / -2 as in d_keyid, then per value column [the offset of the
+ * value in d_out, its length], or [-1, -1] for a row without a dictionary row.
+ *
+ * len == 0 gives zeros and success.  With flags == 0 an empty map selects nothing, with
+ * SRE_HIP_LINES_ALL every line with empty value fields.
+ *
+ * Memory.  Beyond what sre_hip_lookup_lines takes, a scanner keeps 16 bytes per line and entry of
+ * the join's table, 1 + nvcols entries a line (the extract's grow-only table), and 8 bytes per
+ * line for the index's key ids.  The map is only read.  Not offered: a default text for missing
+ * values, last-row-wins, joining extracted fields instead of the whole line, INVERT, caseless keys.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_join_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, const sre_hip_keyset_t *ks,
+    const int *vcols, size_t nvcols, int jsep, int flags,
     void *d_out, size_t out_cap,
     sre_int_t *d_keyid, size_t keyid_cap,
     sre_int_t *d_index, size_t index_cap,

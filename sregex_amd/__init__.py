@@ -29,6 +29,7 @@ HIP_LINES_ALL = 1
 HIP_LINES_INVERT = 2
 HIP_EXTRACT_MAX_FIELDS = 32
 HIP_SUBST_MAX_PIECES = 30
+HIP_JOIN_MAX_VALUES = 31
 HIP_SUBST_MAX_LITERAL = 4096
 HIP_ROUTE_MAX_BUCKETS = 256
 HIP_TALLY_OVERFLOW = 1
@@ -104,6 +105,8 @@ API = {
                                                 _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_tally_number": (ctypes.c_int, [ctypes.c_char_p, _sz, ctypes.POINTER(ctypes.c_int64)]),
     "sre_hip_keyset_create": (_vp, [_vp, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]),
+    "sre_hip_keyset_create_map": (_vp, [_vp, _sz, _sz, _sz, ctypes.c_int, ctypes.c_int, _vp]),
+    "sre_hip_keyset_values": (_sz, [_vp]),
     "sre_hip_keyset_destroy": (None, [_vp]),
     "sre_hip_keyset_rows": (_sz, [_vp]),
     "sre_hip_keyset_distinct": (_sz, [_vp]),
@@ -113,6 +116,9 @@ API = {
     "sre_hip_keyset_hash": (ctypes.c_uint64, [ctypes.c_char_p, _sz, _sz, ctypes.c_int]),
     "sre_hip_lookup_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int, _vp,
                                             _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_join_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp,
+                                          ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _sz,
+                                          _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -209,15 +215,20 @@ class KeySet:
     """sre_hip_keyset_*: the distinct keys of a dictionary of rows (field 0, fsep, .., field K - 1, delim: what
     Scanner.extract_lines and Scanner.tally_lines write) in the device buffer (ptr, length), kept on the device for
     Scanner.lookup_lines.  The set copies the rows: the buffer may be freed once the constructor has returned.  A key's
-    id is the lowest row that carries it.  Raises ValueError when the arguments are out of range or a row does not hold
-    nfields fields."""
+    id is the lowest row that carries it.  With nkeys (sre_hip_keyset_create_map) the set is a key MAP: the first nkeys
+    of a row's nfields fields are its key, the others the value columns Scanner.join_lines appends to a line; the values
+    of a key are those of the lowest row that carries it.  Raises ValueError when the arguments are out of range or a
+    row does not hold nfields fields."""
 
-    def __init__(self, ptr, length, nfields=1, fsep=0x09, delim=0x0A, hip_stream=None, lib=None):
+    def __init__(self, ptr, length, nfields=1, fsep=0x09, delim=0x0A, hip_stream=None, lib=None, nkeys=None):
         self.lib = lib or load_library()
-        self.h = self.lib.sre_hip_keyset_create(ptr, length, nfields, fsep, delim, hip_stream)
+        if nkeys is None:
+            self.h = self.lib.sre_hip_keyset_create(ptr, length, nfields, fsep, delim, hip_stream)
+        else:
+            self.h = self.lib.sre_hip_keyset_create_map(ptr, length, nfields, nkeys, fsep, delim, hip_stream)
         if not self.h:
-            raise ValueError("sre_hip_keyset_create failed (arguments out of range, a row without %d fields, or no device)"
-                             % nfields)
+            raise ValueError("sre_hip_keyset_create%s failed (arguments out of range, a row without %d fields, or no device)"
+                             % ("" if nkeys is None else "_map", nfields))
 
     def close(self):
         if self.h:
@@ -241,6 +252,11 @@ class KeySet:
     @property
     def fields(self):
         return self.lib.sre_hip_keyset_fields(self.h)
+
+    @property
+    def values(self):
+        """value columns of a key map; 0 for a plain set"""
+        return self.lib.sre_hip_keyset_values(self.h)
 
     @property
     def slots(self):
@@ -668,6 +684,25 @@ class Scanner:
                                          HIP_LINES_INVERT if invert else 0, out_ptr, out_cap, keyid_ptr, keyid_cap, index_ptr,
                                          index_cap, info, hip_stream) != 0:
             raise RuntimeError("sre_hip_lookup_lines failed")
+        return LookupInfo(*info)
+
+    def join_lines(self, ptr, length, out_ptr, out_cap, groups, keyset, vcols, jsep=0x09, delim=0x0A, all_lines=False,
+                   keyid_ptr=None, keyid_cap=0, index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_join_lines: the lines of the device buffer (ptr, length) whose key (lookup_lines) is in the key map
+        `keyset`, each followed by jsep and the value columns `vcols` of the key's dictionary row, jsep between them, and
+        one delimiter, compacted in order into the device buffer (out_ptr, out_cap); with all_lines every line, the ones
+        without a dictionary row with empty values.  keyid_ptr: as in lookup_lines; index_ptr: an optional device array of
+        index_cap rows of 5 + 2 * len(vcols) int64: line, start, len, the row's output offset, the dictionary row (-1, -2
+        as in keyid), then per column the value's output offset and length, (-1, -1) without a dictionary row.  The
+        scanner's mode must be HIP_PIKE_FIRST and delim the map's.  Returns LookupInfo."""
+        groups, vcols = list(groups), list(vcols)
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        cols = (ctypes.c_int * max(len(vcols), 1))(*vcols)
+        info = (_sz * 7)()
+        if self.lib.sre_hip_join_lines(self.h, ptr, length, delim, arr, len(groups), keyset.h if keyset is not None else None,
+                                       cols, len(vcols), jsep, HIP_LINES_ALL if all_lines else 0, out_ptr, out_cap, keyid_ptr,
+                                       keyid_cap, index_ptr, index_cap, info, hip_stream) != 0:
+            raise RuntimeError("sre_hip_join_lines failed")
         return LookupInfo(*info)
 
     @property

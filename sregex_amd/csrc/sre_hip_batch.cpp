@@ -25,6 +25,7 @@
 #include "sre_lines_tally.h"
 #include "sre_lines_sums.h"
 #include "sre_lines_keyset.h"
+#include "sre_lines_join.h"
 #include "sre_hip_streams.h"
 #include "sre_streams_nfa.h"
 #include <stddef.h>
@@ -179,6 +180,10 @@ struct sre_hip_scanner_s {
     size_t                    vstart_cap;
     sre_ls_agg_t             *d_vcopy;          /* the copies of the aggregates the waves send to: at most SRE_LS_COPY_BYTES */
     size_t                    vcopy_cap;
+    /* the line join (sre_hip_join_lines): the entry table is the extract's (d_fval, d_fstart, d_fblk), sized by lines x
+     * (1 + columns), the key table the lookup's (d_vval, d_vstart); it adds */
+    int64_t                  *d_jkey;           /* the key id of every line, for the index */
+    size_t                    jkey_cap;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -255,6 +260,7 @@ scanner_release(void *data)
     if (sc->d_vval) (void) hipFree(sc->d_vval);
     if (sc->d_vstart) (void) hipFree(sc->d_vstart);
     if (sc->d_vcopy) (void) hipFree(sc->d_vcopy);
+    if (sc->d_jkey) (void) hipFree(sc->d_jkey);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -1740,6 +1746,11 @@ struct LinesSink {
     /* the filter with context: index rows of five words; d_cbits marks the context-only lines (NULL: no line is one) */
     bool                        context;
     const uint64_t             *d_cbits;
+    /* the join: the batches end with the filter's select pass (mode 0) and the key groups' (vgroups) as the lookup's do; the
+     * table has `join` = 1 + columns entries per line, which the join pass behind the call fills, jsep between the fields
+     * of a row (fsep); its values come from d_dict, the map's copy of its dictionary */
+    uint32_t                    join;
+    const void                 *d_dict;
 };
 
 /* the arguments every sink call shares: false unless they are in range, the pointers stand for their sizes and the output
@@ -1795,7 +1806,7 @@ sink_groups(const sre_hip_scanner_t *sc, const int *groups, size_t ngroups, sre_
 static uint32_t
 sink_entries(const LinesSink *sink)
 {
-    return sink->pieces ? sink->pieces->np + 2 : sink->groups ? sink->groups->k : 1;
+    return sink->pieces ? sink->pieces->np + 2 : sink->groups ? sink->groups->k : sink->join ? sink->join : 1;
 }
 
 /* the select pass of a device batch (lines i0 .. d_linfo->i1, at most nmax) from its records */
@@ -2134,7 +2145,7 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
         if (sink) {
             const uint64_t k = sink_entries(sink);
             if (lines_grow(&sc->d_fval, &sc->fval_cap, (n * k + 1) * sizeof(uint64_t)) != 0) goto hip_failed;
-            if (sink->groups || sink->pieces) {
+            if (sink->groups || sink->pieces || sink->join) {
                 if (lines_grow(&sc->d_fstart, &sc->fstart_cap, n * k * sizeof(uint64_t)) != 0) goto hip_failed;
             }
             if (sink->vgroups) {
@@ -2142,6 +2153,7 @@ lines_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int 
                 if (lines_grow(&sc->d_vval, &sc->vval_cap, n * v * sizeof(uint64_t)) != 0) goto hip_failed;
                 if (lines_grow(&sc->d_vstart, &sc->vstart_cap, n * v * sizeof(uint64_t)) != 0) goto hip_failed;
             }
+            if (sink->join && lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) goto hip_failed;
         }
         rc = route == 1   ? lines_scan_device(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink)
              : route == 2 ? lines_scan_nfa(sc, d_buf, n, all, out, cap, &nrep, stream, &tot, sink)
@@ -2193,7 +2205,8 @@ sink_offsets(sre_hip_scanner_t *sc, const LinesSink *sink, uint64_t n, hipStream
     const uint64_t nblk = (n * k + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
     if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
     SRE_HIP_TRY(sink->pieces   ? sre_launch_subst_offsets(sc->d_fval, n, k, sc->d_fblk, sink->out_cap, sc->d_linfo, stream)
-                : sink->groups ? sre_launch_extract_offsets(sc->d_fval, n, k, sc->d_fblk, sink->out_cap, sc->d_linfo, stream)
+                : sink->groups || sink->join
+                    ? sre_launch_extract_offsets(sc->d_fval, n, k, sc->d_fblk, sink->out_cap, sc->d_linfo, stream)
                                : sre_launch_filter_offsets(sc->d_fval, n, sc->d_fblk, sink->out_cap, sc->d_linfo, stream));
     return 0;
 hip_failed:
@@ -2228,10 +2241,12 @@ sink_write(sre_hip_scanner_t *sc, const LinesSink *sink, const void *d_buf, uint
     int64_t                *rows = sink->d_index;
     if (sink->pieces) SRE_HIP_TRY(sre_launch_subst_gather(d_buf, sink->d_out, off, start, sc->d_lit, n * k, out_bytes, delim, stream));
     else if (sink->groups) SRE_HIP_TRY(sre_launch_extract_gather(d_buf, sink->d_out, off, start, n * k, out_bytes, delim, fsep, stream));
+    else if (sink->join) SRE_HIP_TRY(sre_launch_join_gather(d_buf, sink->d_out, off, start, sink->d_dict, n * k, out_bytes, delim, fsep, stream));
     else SRE_HIP_TRY(sre_launch_lines_gather(d_buf, sink->d_out, off, ends, n, out_bytes, delim, stream));
     if (nwritten == 0) return 0;
     if (sink->pieces) SRE_HIP_TRY(sre_launch_subst_index(off, start, ends, n, k, blk, li, cap, rows, stream));
     else if (sink->groups) SRE_HIP_TRY(sre_launch_extract_index(off, start, ends, n, k, blk, li, cap, rows, stream));
+    else if (sink->join) SRE_HIP_TRY(sre_launch_join_index(off, start, ends, sc->d_jkey, n, k, blk, li, cap, rows, stream));
     else if (sink->context) SRE_HIP_TRY(sre_launch_context_index(off, ends, n, blk, sink->d_cbits, li, cap, rows, stream));
     else SRE_HIP_TRY(sre_launch_filter_index(off, ends, n, blk, li, cap, rows, stream));
     return 0;
@@ -2500,8 +2515,12 @@ struct sre_hip_keyset_s {
     uint64_t *d_fstart;     /* rows x k field offsets into it */
     uint64_t *d_flen;       /* ... and lengths */
     uint64_t *d_tab;        /* nslots words: SRE_LT_EMPTY or the lowest row of the slot's key */
+    uint64_t *d_vstart;     /* a map's: rows x v value-column offsets into the copy */
+    uint64_t *d_vlen;       /* ... and lengths */
     uint64_t  rows, distinct, nslots, hash_mask;
-    uint32_t  k;
+    uint32_t  k;            /* key fields of a row */
+    uint32_t  v;            /* value columns behind them; 0: a plain set */
+    int       delim;
     size_t    bytes;        /* device memory held */
 };
 
@@ -2522,14 +2541,18 @@ sre_hip_keyset_destroy(sre_hip_keyset_t *ks)
     if (ks->d_fstart) (void) hipFree(ks->d_fstart);
     if (ks->d_flen) (void) hipFree(ks->d_flen);
     if (ks->d_tab) (void) hipFree(ks->d_tab);
+    if (ks->d_vstart) (void) hipFree(ks->d_vstart);
+    if (ks->d_vlen) (void) hipFree(ks->d_vlen);
     free(ks);
 }
 
+/* A key map: a key set whose rows carry nfields - nkeys value columns behind the nkeys key fields.
+ * The plain set is the map without columns: the same passes, and its rows go through the same fields kernel as before. */
 extern "C" SRE_API sre_hip_keyset_t *
-sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields, int fsep, int delim, void *hip_stream)
+sre_hip_keyset_create_map(const void *d_rows, size_t len, size_t nfields, size_t nkeys, int fsep, int delim, void *hip_stream)
 {
-    if (nfields < 1 || nfields > SRE_HIP_EXTRACT_MAX_FIELDS || fsep < 0 || fsep > 255 || delim < 0 || delim > 255
-        || (nfields > 1 && fsep == delim) || (len != 0 && d_rows == NULL))
+    if (nfields < 1 || nfields > SRE_HIP_EXTRACT_MAX_FIELDS || nkeys < 1 || nkeys > nfields || fsep < 0 || fsep > 255 || delim < 0
+        || delim > 255 || (nfields > 1 && fsep == delim) || (len != 0 && d_rows == NULL))
     {
         return NULL;
     }
@@ -2544,9 +2567,11 @@ sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields, int fsep, 
     uint64_t       *d_tiles = NULL, *d_ends = NULL;
     uint64_t        h[2] = {0, 0};
     const uint64_t  ntiles = (len + SRE_LINES_TILE_BYTES - 1) / SRE_LINES_TILE_BYTES;
-    size_t          nent = 0;
+    size_t          nent = 0, nvent = 0;
     if (ks == NULL) return NULL;
-    ks->k = (uint32_t) nfields;
+    ks->k = (uint32_t) nkeys;
+    ks->v = (uint32_t) (nfields - nkeys);
+    ks->delim = delim;
     ks->hash_mask = keyset_hash_mask();
     ks->nslots = sre_lk_nslots(0);
     if (len != 0) {
@@ -2567,16 +2592,26 @@ sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields, int fsep, 
         SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_ends), ks->rows * sizeof(uint64_t)));
         SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_fstart), nent * sizeof(uint64_t)));
         SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_flen), nent * sizeof(uint64_t)));
+        if (ks->v) {
+            nvent = (size_t) ks->rows * ks->v;
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_vstart), nvent * sizeof(uint64_t)));
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ks->d_vlen), nvent * sizeof(uint64_t)));
+        }
         SRE_HIP_TRY(sre_launch_lines_write(ks->d_rows, len, (uint32_t) delim, d_tiles, d_ends, stream));
         SRE_HIP_TRY(hipMemsetAsync(&d_w->bad, 0xFF, sizeof(uint64_t), stream));         /* SRE_LK_NO_ROW */
         SRE_HIP_TRY(hipMemsetAsync(&d_w->distinct, 0, sizeof(uint64_t), stream));
-        SRE_HIP_TRY(sre_launch_keyset_fields(ks->d_rows, d_ends, ks->rows, ks->k, (uint32_t) fsep, ks->d_fstart, ks->d_flen, &d_w->bad,
-                                             stream));
+        if (ks->v) {
+            SRE_HIP_TRY(sre_launch_keymap_fields(ks->d_rows, d_ends, ks->rows, (uint32_t) nfields, ks->k, (uint32_t) fsep, ks->d_fstart,
+                                                 ks->d_flen, ks->d_vstart, ks->d_vlen, &d_w->bad, stream));
+        } else {
+            SRE_HIP_TRY(sre_launch_keyset_fields(ks->d_rows, d_ends, ks->rows, ks->k, (uint32_t) fsep, ks->d_fstart, ks->d_flen,
+                                                 &d_w->bad, stream));
+        }
         /* (the insert reads the fields of every row: it is queued only when every row has them) */
         SRE_HIP_TRY(hipMemcpyAsync(&h[0], &d_w->bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
         if (h[0] != SRE_LK_NO_ROW) {
-            fprintf(stderr, "[sregex-hip] key set: row %llu does not hold %u fields\n", (unsigned long long) h[0], ks->k);
+            fprintf(stderr, "[sregex-hip] key set: row %llu does not hold %u fields\n", (unsigned long long) h[0], (unsigned) nfields);
             goto hip_failed;
         }
         ks->nslots = sre_lk_nslots(ks->rows);
@@ -2590,7 +2625,7 @@ sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields, int fsep, 
     }
     SRE_HIP_TRY(hipStreamSynchronize(stream));
     ks->distinct = h[1];
-    ks->bytes = (len ? len + 16 : 0) + 2 * nent * sizeof(uint64_t) + ks->nslots * sizeof(uint64_t);
+    ks->bytes = (len ? len + 16 : 0) + 2 * (nent + nvent) * sizeof(uint64_t) + ks->nslots * sizeof(uint64_t);
     if (d_w) (void) hipFree(d_w);
     if (d_tiles) (void) hipFree(d_tiles);
     if (d_ends) (void) hipFree(d_ends);
@@ -2604,6 +2639,13 @@ hip_failed:
     return NULL;
 }
 
+extern "C" SRE_API sre_hip_keyset_t *
+sre_hip_keyset_create(const void *d_rows, size_t len, size_t nfields, int fsep, int delim, void *hip_stream)
+{
+    return sre_hip_keyset_create_map(d_rows, len, nfields, nfields, fsep, delim, hip_stream);
+}
+
+extern "C" SRE_API size_t sre_hip_keyset_values(const sre_hip_keyset_t *ks) { return ks ? ks->v : 0; }
 extern "C" SRE_API size_t sre_hip_keyset_rows(const sre_hip_keyset_t *ks) { return ks ? (size_t) ks->rows : 0; }
 extern "C" SRE_API size_t sre_hip_keyset_distinct(const sre_hip_keyset_t *ks) { return ks ? (size_t) ks->distinct : 0; }
 extern "C" SRE_API size_t sre_hip_keyset_fields(const sre_hip_keyset_t *ks) { return ks ? ks->k : 0; }
@@ -2654,6 +2696,63 @@ sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
         SRE_HIP_TRY(sre_launch_keyset_probe(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen, ks->d_tab,
                                             ks->nslots, ks->hash_mask, (flags & SRE_HIP_LINES_INVERT) != 0, sc->d_fval,
                                             reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream));
+        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
+        if (sink_read(sc, &sink, n, &res, stream, LINFO(knkeyed), LINFO(knmembers)) != 0) return -1;
+        res.nkeyed = (size_t) sc->h_linfo->knkeyed;
+        res.nmembers = (size_t) sc->h_linfo->knmembers;
+        if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The line join: the lookup's call, key groups and host waits; in the probe's place the join pass, which
+ * walks the same table and fills the table of 1 + nvcols entries per line; then the extract's scan and cut over that table,
+ * the one read, the gather with the map's copy of the dictionary as its second extent, and the index. */
+extern "C" SRE_API int
+sre_hip_join_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+    const sre_hip_keyset_t *ks, const int *vcols, size_t nvcols, int jsep, int flags, void *d_out, size_t out_cap, sre_int_t *d_keyid,
+    size_t keyid_cap, sre_int_t *d_index, size_t index_cap, sre_hip_lookup_info_t *info, void *hip_stream)
+{
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    sre_lj_cols_t        cols;
+    static_assert(SRE_HIP_JOIN_MAX_VALUES == SRE_LJ_MAX_VALUES && 1 + SRE_LJ_MAX_VALUES <= SRE_EXTRACT_MAX_FIELDS,
+                  "a row of the join table is a row of the extract's");
+    if (ks == NULL || ks->v == 0 || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1 || ngroups != ks->k
+        || vcols == NULL || nvcols < 1 || nvcols > SRE_HIP_JOIN_MAX_VALUES || jsep < 0 || jsep > 255 || jsep == delim
+        || delim != ks->delim || (keyid_cap != 0 && d_keyid == NULL))
+    {
+        return -1;
+    }
+    memset(&cols, 0, sizeof(cols));
+    cols.n = (uint32_t) nvcols;
+    for (size_t x = 0; x < nvcols; x++) {
+        if (vcols[x] < 0 || (size_t) vcols[x] >= ks->v) return -1;
+        cols.col[x] = (uint8_t) vcols[x];
+    }
+    /* (the sink's row rule is the filter's mode 0 whatever the flags are, so that the key table says which lines are keyed:
+     * the join pass applies the flags) */
+    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
+    if (!sink_first_match(sc, "line join", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
+    sink.vgroups = &gr;
+    sink.join = 1 + cols.n;
+    sink.fsep = jsep;
+    sink.d_dict = ks->d_rows;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_lookup_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_keyset_join(d_buf, sc->d_vval, sc->d_vstart, sc->d_ends, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen,
+                                           ks->d_vstart, ks->d_vlen, ks->v, ks->d_tab, ks->nslots, ks->hash_mask, &cols,
+                                           (flags & SRE_HIP_LINES_ALL) != 0, sc->d_fval, sc->d_fstart, sc->d_jkey,
+                                           reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream));
         if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
         if (sink_read(sc, &sink, n, &res, stream, LINFO(knkeyed), LINFO(knmembers)) != 0) return -1;
         res.nkeyed = (size_t) sc->h_linfo->knkeyed;

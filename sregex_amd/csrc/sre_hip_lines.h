@@ -12,6 +12,7 @@
 #include "sre_hip_nfa.h"
 #include "sre_lines_nfa.h"
 #include "sre_lines_select.h"     /* sre_extract_groups_t, sre_subst_pieces_t and the select rules */
+#include "sre_lines_join.h"       /* sre_lj_cols_t */
 
 /* split: a workgroup of SRE_LINES_THREADS lanes owns one tile of 16-byte aligned chunks, each lane
  * loads SRE_LINES_CHUNKS chunks of it (lane x, step k: chunk k * SRE_LINES_THREADS + x of the tile).
@@ -237,6 +238,29 @@ hipError_t sre_launch_keyset_insert(const void *d_rows, const uint64_t *d_fstart
 hipError_t sre_launch_keyset_probe(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, uint32_t k,
     const void *d_rows, const uint64_t *d_fstart, const uint64_t *d_flen, const uint64_t *d_tab, uint64_t nslots,
     uint64_t hash_mask, int invert, uint64_t *d_fval, int64_t *d_keyid, uint64_t keyid_cap, sre_lines_info_t *d_info,
+    hipStream_t stream);
+/* ---- the key map and the line join (sre_lines_join.h) ---- */
+/* sre_launch_keyset_fields for a map of nfields fields a row, the first k its key: the key fields into entries r * k + f of
+ * d_fstart / d_flen, the value columns into entries r * (nfields - k) + c of d_vstart / d_vlen; k < nfields */
+hipError_t sre_launch_keymap_fields(const void *d_rows, const uint64_t *d_ends, uint64_t rows, uint32_t nfields, uint32_t k,
+    uint32_t fsep, uint64_t *d_fstart, uint64_t *d_flen, uint64_t *d_vstart, uint64_t *d_vlen, uint64_t *d_bad, hipStream_t stream);
+/* in the place of sre_launch_keyset_probe, a lane per line: the same walk, d_keyid and counts; d_own[i], every i < n, is the
+ * key id too; d_val / d_start get the P = 1 + cols->n entries of every line as sre_lj_entries gives them (n * P words; the
+ * line from d_ends, the values from the map's d_mstart / d_mlen of nvalues columns a row).  `all`: the left outer join */
+hipError_t sre_launch_keyset_join(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, const uint64_t *d_ends,
+    uint64_t n, uint32_t k, const void *d_rows, const uint64_t *d_fstart, const uint64_t *d_flen, const uint64_t *d_mstart,
+    const uint64_t *d_mlen, uint32_t nvalues, const uint64_t *d_tab, uint64_t nslots, uint64_t hash_mask, const sre_lj_cols_t *cols,
+    int all, uint64_t *d_val, uint64_t *d_start, int64_t *d_own, int64_t *d_keyid, uint64_t keyid_cap, sre_lines_info_t *d_info,
+    hipStream_t stream);
+/* the gather over the join table (behind sre_launch_extract_offsets with k = P): output bytes [0, out_bytes) of the rows to
+ * d_out.  d_dict: the map's copy of the dictionary, 16-byte aligned with 16 bytes allocated behind its text (NULL: the
+ * empty map) */
+hipError_t sre_launch_join_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_start,
+    const void *d_dict, uint64_t nentries, uint64_t out_bytes, uint32_t delim, uint32_t jsep, hipStream_t stream);
+/* rows [line, start, len, output offset, key id, (output offset of the value, its length) x (p - 1)] of the first
+ * min(index_cap, info->fwritten) written rows; a line without a dictionary row has (-1, -1) */
+hipError_t sre_launch_join_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, const int64_t *d_keyid,
+    uint64_t n, uint32_t p, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
 #ifdef __cplusplus
 }

@@ -20,6 +20,11 @@
  * a selected line may be empty there, so its sums, finish and index count LINES by their last entries, which always
  * take a byte; the gather is the same chunk walk over sre_lg_tab_pieces with the literal block as a second source.
  *
+ * The line join (sre_hip_join_lines) fills its table of entries e = line * P + f, the line and P - 1
+ * values of its dictionary row, in a pass of its own (sre_hip_lines_keyset.hip); every entry of a selected line takes a
+ * byte, so the extract's scan and finish run over it as they are, the gather is the same chunk walk over sre_lg_tab_join
+ * with the key map's copy of the dictionary as the second source, and the index rows have 5 + 2 (P - 1) words.
+ *
  * No workgroup waits for another.  Plain C++ and vector memory operations only.
  */
 #include <sregex/sregex.h>
@@ -356,6 +361,12 @@ window_start(const sre_lg_tab_pieces &tab, uint64_t i)
     return tab.raw(i);
 }
 
+__device__ inline uint64_t
+window_start(const sre_lg_tab_join &tab, uint64_t i)
+{
+    return tab.raw(i);
+}
+
 /* one tile of the output over the table `tab` (global memory), WTab its window type */
 template <class GTab, class WTab, class Mem>
 __device__ inline void
@@ -421,6 +432,23 @@ sre_k_subst_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, c
     mem.dst = dst;
     mem.lit = lit;
     gather_body<sre_lg_tab_pieces, sre_lg_tab_pieces>(tab, off, g, mem, w_off, w_start, slice);
+}
+
+/* the line join's (sre_hip_join_lines): g.nlines counts the entries of the join table, g.fsep is the
+ * join separator, lit is the key map's copy of the dictionary: hipMalloc aligns it, and it is allocated 16 bytes beyond its
+ * text.  An unaligned 16-byte load of it holds 16 bytes of one value; an aligned block holds at least one byte of a value,
+ * so it starts below the text's end and ends inside those 16 bytes */
+__global__ __launch_bounds__(SRE_LG_THREADS) void
+sre_k_join_gather(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const uint64_t *__restrict__ off,
+                  const uint64_t *__restrict__ starts, const uint8_t *__restrict__ lit, sre_lg_geom_t g)
+{
+    __shared__ uint64_t w_off[SRE_LG_WINDOW + 1], w_start[SRE_LG_WINDOW], slice[2];
+    const sre_lg_tab_join tab = {off, starts, 0};
+    SubstMem              mem;
+    mem.src = src;
+    mem.dst = dst;
+    mem.lit = lit;
+    gather_body<sre_lg_tab_join, sre_lg_tab_join>(tab, off, g, mem, w_off, w_start, slice);
 }
 
 /* ---- index ---- */
@@ -491,6 +519,47 @@ sre_k_extract_index(const uint64_t *__restrict__ off, const uint64_t *__restrict
                 const bool     unset = (w & SRE_LG_ENTRY_UNSET) != 0;
                 row[4 + 2 * x] = unset ? -1 : (int64_t) (w & SRE_LG_ENTRY_START);
                 row[5 + 2 * x] = unset ? -1 : (int64_t) (off[e + x + 1] - off[e + x] - 1);
+            }
+        }
+        r++;
+    }
+}
+
+/* the line join's rows, 5 + 2 (p - 1) words, as sre_k_extract_index finds and ranks them over the p entries of a line:
+ * [4] is the line's key id (a dictionary row, -1, -2), then per value column its offset in the OUTPUT and its length, or
+ * (-1, -1) for a line without a dictionary row */
+__global__ __launch_bounds__(256) void
+sre_k_join_index(const uint64_t *__restrict__ off, const uint64_t *__restrict__ starts, const uint64_t *__restrict__ ends,
+                 const int64_t *__restrict__ keyid, uint64_t nent, uint64_t p, const uint64_t *__restrict__ blkc,
+                 const sre_lines_info_t *__restrict__ info, uint64_t index_cap, int64_t *__restrict__ rows)
+{
+    __shared__ uint64_t wsum[4];
+    const uint64_t      limit = index_cap < info->fwritten ? index_cap : info->fwritten;
+    if (blkc[blockIdx.x] >= limit * p) return;      /* (the whole workgroup) */
+    const uint64_t q0 = (uint64_t) blockIdx.x * SRE_LINES_ITEMS + 4u * threadIdx.x;
+    uint32_t       f[4];
+    uint64_t       s = 0;
+    for (uint32_t q = 0; q < 4; q++) {
+        f[q] = q0 + q < nent && off[q0 + q + 1] > off[q0 + q];
+        s += f[q];
+    }
+    uint64_t total;
+    uint64_t r = blkc[blockIdx.x] + block_excl_scan<256>(s, wsum, total);
+    for (uint32_t q = 0; q < 4; q++) {
+        if (!f[q]) continue;
+        const uint64_t e = q0 + q;
+        if ((starts[e] & SRE_LG_ENTRY_FIRST) && r / p < limit) {
+            const uint64_t i = e / p, st = line_start(ends, i);
+            int64_t       *row = rows + (r / p) * (3 + 2 * p);
+            row[0] = (int64_t) i;
+            row[1] = (int64_t) st;
+            row[2] = (int64_t) (ends[i] - st);
+            row[3] = (int64_t) off[e];
+            row[4] = keyid[i];
+            for (uint64_t x = 1; x < p; x++) {
+                const bool unset = (starts[e + x] & SRE_LG_ENTRY_UNSET) != 0;
+                row[3 + 2 * x] = unset ? -1 : (int64_t) off[e + x];
+                row[4 + 2 * x] = unset ? -1 : (int64_t) (off[e + x + 1] - off[e + x] - 1);
             }
         }
         r++;
@@ -716,6 +785,43 @@ sre_launch_subst_index(const uint64_t *d_off, const uint64_t *d_start, const uin
     if (n == 0 || index_cap == 0) return hipSuccess;
     const uint64_t nent = n * p, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
     hipLaunchKernelGGL(sre_k_subst_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_start, d_ends, nent,
+                       (uint64_t) p, d_blk + nblk, d_info, index_cap, d_index);
+    return hipGetLastError();
+}
+
+/* ---- the line join ---- */
+
+extern "C" hipError_t
+sre_launch_join_gather(const void *d_buf, void *d_out, const uint64_t *d_off, const uint64_t *d_start, const void *d_dict,
+                       uint64_t nentries, uint64_t out_bytes, uint32_t delim, uint32_t jsep, hipStream_t stream)
+{
+    if (out_bytes == 0) return hipSuccess;
+    /* (d_dict == NULL: the empty map, no entry of the table is a value) */
+    if ((reinterpret_cast<uintptr_t>(d_dict) & 15u) != 0) return hipErrorInvalidValue;
+    sre_lg_geom_t g;
+    g.nlines = nentries;
+    g.out_bytes = out_bytes;
+    g.src_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_buf) & 15u);
+    g.dst_head = (uint32_t) (reinterpret_cast<uintptr_t>(d_out) & 15u);
+    g.delim = delim;
+    g.fsep = jsep;
+    const uint64_t ntiles = (sre_lg_nchunks(g) + SRE_LG_TILE_CHUNKS - 1) / SRE_LG_TILE_CHUNKS;
+    if (ntiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_join_gather, dim3((uint32_t) ntiles), dim3(SRE_LG_THREADS), 0, stream,
+                       static_cast<const uint8_t *>(d_buf) - g.src_head, static_cast<uint8_t *>(d_out) - g.dst_head, d_off,
+                       d_start, static_cast<const uint8_t *>(d_dict), g);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_join_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, const int64_t *d_keyid, uint64_t n,
+                      uint32_t p, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
+                      hipStream_t stream)
+{
+    if (n == 0 || index_cap == 0) return hipSuccess;
+    if (p < 2) return hipErrorInvalidValue;
+    const uint64_t nent = n * p, nblk = (nent + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    hipLaunchKernelGGL(sre_k_join_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_off, d_start, d_ends, d_keyid, nent,
                        (uint64_t) p, d_blk + nblk, d_info, index_cap, d_index);
     return hipGetLastError();
 }

@@ -24,6 +24,11 @@
  * row abut: only the last entry of a line has a byte behind it (the delimiter), the text of every other entry runs to
  * off[e + 1]; an entry may take no byte at all and is then never visited.  The text of a literal piece comes from the
  * call's LITERAL BLOCK, a second 16-byte aligned extent (sre_lg_tab_pieces).
+ *
+ * Line join (sre_hip_join_lines) gathers over a table of entries e = line * P + f: the line's text,
+ * then P - 1 values of the line's dictionary row.  Every entry has a byte behind it as the extract's fields have (the
+ * join separator, or the delimiter behind the last), and the text of a value comes from the key map's copy of its
+ * dictionary, the second extent in the literal block's place (sre_lg_tab_join).
  */
 #ifndef SRE_LINES_GATHER_H
 #define SRE_LINES_GATHER_H
@@ -174,6 +179,32 @@ struct sre_lg_tab_pieces {
         else sink.text((uint64_t) head + (w & SRE_LG_PIECE_START) + at, d, cnt);
     }
     template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t, uint32_t d) const { sink.delim(d); }
+};
+
+/* the entry table of the line join (sre_hip_join_lines, sre_lines_join.h), whole (base 0, global memory) or a window of it
+ * (LDS): entries e = line * P + f, f = 0 the line's text from the source (FIRST), f = 1 .. P - 1 a value from the key
+ * map's copy of the dictionary (LITERAL: the offset is one into that copy, the call's second extent) or nothing at all
+ * (UNSET: a line without a dictionary row).  Every entry trails a byte as the extract's fields do: the delimiter behind
+ * the LAST entry, the join separator (the geometry's fsep) behind every other */
+struct sre_lg_tab_join {
+    const uint64_t *offs;
+    const uint64_t *starts;
+    uint64_t        base;
+    SRE_LG_MEMBER uint64_t off(uint64_t e) const { return offs[e - base]; }
+    SRE_LG_MEMBER uint64_t raw(uint64_t e) const { return starts[e - base]; }
+    SRE_LG_MEMBER uint64_t start(uint64_t e) const { return starts[e - base] & SRE_LG_PIECE_START; }
+    SRE_LG_MEMBER bool     trails(uint64_t) const { return true; }
+    template <class Sink> SRE_LG_MEMBER void text(Sink &sink, uint64_t e, uint64_t at, uint32_t head, uint32_t d, uint32_t cnt) const
+    {
+        const uint64_t w = starts[e - base];
+        if (w & SRE_LG_ENTRY_LITERAL) sink.literal((w & SRE_LG_PIECE_START) + at, d, cnt);
+        else sink.text((uint64_t) head + (w & SRE_LG_PIECE_START) + at, d, cnt);
+    }
+    template <class Sink> SRE_LG_MEMBER void end(Sink &sink, uint64_t e, uint32_t d) const
+    {
+        if (starts[e - base] & SRE_LG_ENTRY_LAST) sink.delim(d);
+        else sink.sep(d);
+    }
 };
 
 /* the last i of [lo, hi] with off(i) <= o; the caller knows off(lo) <= o */
