@@ -805,10 +805,10 @@ typedef struct {
  * The call is synchronous and all its work runs on hip_stream; the host waits exactly as often as
  * in sre_hip_filter_lines.  The set is only read.  Beyond what sre_hip_filter_lines takes, a
  * scanner keeps the 16 bytes per line and key group that sre_hip_tally_sums_lines keeps per value
- * column (the same grow-only memory, freed with the scanner).  Not offered: routing by dictionary
- * row (d_keyid plus the route's partition is the obvious follow-up), every match of a line,
+ * column (the same grow-only memory, freed with the scanner).  Not offered: every match of a line,
  * caseless keys, Thompson and COUNT scanners, stream sets.  The dictionary's value columns joined
- * into the output are sre_hip_join_lines.
+ * into the output are sre_hip_join_lines; the lines grouped by their dictionary row are
+ * sre_hip_route_lines_by_key.
  * Returns 0 on success, -1 on bad arguments or failure.
  */
 SRE_API int sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
@@ -871,6 +871,93 @@ SRE_API int sre_hip_join_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t 
     sre_int_t *d_keyid, size_t keyid_cap,
     sre_int_t *d_index, size_t index_cap,
     sre_hip_lookup_info_t *info, void *hip_stream);
+
+/* ---- the line route by key: group lines by the dictionary row of their key ---- */
+
+typedef struct {
+    size_t nlines, nkeyed, nmembers;   /* as sre_hip_lookup_info_t */
+    size_t nselected;                  /* lines the flags select */
+    size_t nbuckets;                   /* NON-EMPTY buckets among them */
+    size_t need_bytes, nwritten, out_bytes;
+} sre_hip_route_key_info_t;
+
+/*
+ * Line route by key: the lines of d_buf grouped by the dictionary row of their captured key, in
+ * ONE output buffer (awk's `{ print > $3 }`, GROUP BY with the rows kept, the `sort -s -k` in
+ * front of any per-key processing).
+ *
+ * On the same (sc, d_buf, len, delim, groups, ngroups, ks) the split, the matching, the routing to
+ * an engine, the batching, the diagnostics, the demand for an SRE_HIP_PIKE_FIRST scanner (Thompson
+ * and COUNT scanners return -1 with a diagnostic), the range rule of groups, ngroups ==
+ * sre_hip_keyset_fields(ks), the overlap check, d_keyid (-1 for a keyed line that is not a member,
+ * -2 for a line without a key; independent of flags and out_cap), info->nkeyed and info->nmembers
+ * are exactly those of sre_hip_lookup_lines.  A key map is a valid set; its value columns are
+ * ignored.
+ *
+ * Selection and order.  flags == 0 selects the members; SRE_HIP_LINES_ALL selects every line, so
+ * the output is a permutation of the input's lines.  Any other bit returns -1, SRE_HIP_LINES_INVERT
+ * included: there is nothing to group by then, that is sre_hip_lookup_lines.  The output is
+ * bucket-major.  The buckets are the dictionary ids in ascending order (an id is the lowest row
+ * that carries the key, so the rows of sre_hip_tally_lines used as the dictionary give
+ * first-appearance order); with ALL the bucket of the keyed lines that are not members (id -1)
+ * follows the last dictionary bucket and the bucket of the lines without a key (id -2) comes
+ * last.  Inside a bucket the lines are in line order.  Each line is its bytes plus ONE delim, as
+ * sre_hip_route_lines writes them: the output and every bucket's slice of it are line buffers.
+ *
+ * Truncation, the sizing call and the guards are those of sre_hip_route_lines: whole lines only,
+ * in output order; nothing at or beyond out_bytes is touched and nothing in front of d_out; d_out
+ * == NULL with out_cap == 0 sizes the output.
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten) rows
+ * in output order it receives 5 sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the line in d_out   [4] the dictionary id, or -1 / -2 as in d_keyid.
+ *
+ * Bucket table.  d_buckets is an optional DEVICE array (per-bucket totals cannot travel to the
+ * host when the set has a million rows): for each of the first min(buckets_cap, nbuckets)
+ * NON-EMPTY buckets in output order it receives 5 sre_int_t,
+ *   [0] id (-1 / -2 for the two rest buckets)   [1] rank of its first line among the selected lines
+ *   [2] its lines   [3] its offset in the full output   [4] its bytes.
+ * The table and info->nbuckets are totals over the buffer whatever out_cap is.  A key of the set
+ * that no line carries has no row.  A NULL pointer with a cap other than 0 returns -1, for d_out,
+ * d_keyid, d_index and d_buckets alike.
+ *
+ * len == 0 gives zeros and success.  An empty set selects nothing with flags == 0 and gives the one
+ * or two rest buckets with SRE_HIP_LINES_ALL.
+ *
+ * Limits.  A sort item packs the id and the line number into one 64-bit word, 32 bits for the line:
+ * a buffer may hold at most 2^32 - 1 lines, a larger one returns -1 with one diagnostic line.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  Up to the probe the host waits as
+ * often as in sre_hip_lookup_lines; behind it as often as in sre_hip_route_lines: one word that
+ * sizes the compact table, one read of 7 result words, then the end.  That does not depend on the
+ * lines, the set or the number of passes; nothing per line or per bucket travels to the host.  The
+ * partition is a radix sort of one 8-bit digit of the id per pass: 1 pass up to 256 ids, 2 up to
+ * 65536, 3 up to 2^24, 4 beyond.  SRE_HIP_ROUTE_KEY_DIGIT_BITS=n, 1 <= n <= 8, is a test knob read
+ * on every call that forces narrower digits and so more passes; anything else means 8.
+ * SRE_HIP_ROUTE_KEY_RANK=turns is a measurement knob, read on every call as well: the rank of a
+ * line inside a wave by one ballot per distinct digit, the rule of sre_hip_route_lines, in place
+ * of one ballot per digit bit.  The results are identical.
+ *
+ * Memory.  Beyond what sre_hip_lookup_lines takes, a scanner keeps of the largest call 8 bytes per
+ * line (the key ids, shared with sre_hip_join_lines), 2 KiB per 1024 lines (the counts of a pass,
+ * shared with sre_hip_route_lines), and per selected line 16 bytes for the two item arrays, 16
+ * for the compact table and 8 for the head ranks (the last 24 shared with sre_hip_route_lines);
+ * all grow-only device memory, freed with the scanner.  The set is only read.
+ *
+ * Not offered: a separate output pointer per bucket; grouping by the buffer's own keys in one call
+ * (tally, build a set from the tally's rows, then route by it: that matches the lines twice);
+ * ordering the buckets by anything but the dictionary id; INVERT, caseless keys, every match of a
+ * line; Thompson and COUNT scanners, stream sets.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, const sre_hip_keyset_t *ks, int flags,
+    void *d_out, size_t out_cap,
+    sre_int_t *d_keyid, size_t keyid_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_int_t *d_buckets, size_t buckets_cap,
+    sre_hip_route_key_info_t *info, void *hip_stream);
 
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 

@@ -119,6 +119,8 @@ API = {
     "sre_hip_join_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp,
                                           ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _sz,
                                           _vp, _vp]),
+    "sre_hip_route_lines_by_key": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int,
+                                                  _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -705,6 +707,26 @@ class Scanner:
             raise RuntimeError("sre_hip_join_lines failed")
         return LookupInfo(*info)
 
+    def route_lines_by_key(self, ptr, length, out_ptr, out_cap, groups, keyset, delim=0x0A, all_lines=False, keyid_ptr=None,
+                           keyid_cap=0, index_ptr=None, index_cap=0, buckets_ptr=None, buckets_cap=0, hip_stream=None):
+        """sre_hip_route_lines_by_key: the lines of the device buffer (ptr, length) whose key (lookup_lines) is in the KeySet
+        `keyset`, grouped by the key's dictionary row: the device buffer (out_ptr, out_cap) receives the lines of the lowest
+        row first, in line order, then the next row's, .., each followed by one delimiter.  With all_lines every line: the
+        keyed lines whose key the set does not hold (id -1) follow the last row's, the lines without a key (id -2) come
+        last.  keyid_ptr: as in lookup_lines; index_ptr: an optional device array of index_cap rows [line no, offset in the
+        buffer, length, offset in the output, id] in output order; buckets_ptr: an optional device array of buckets_cap
+        rows [id, rank of the first line, lines, offset in the full output, bytes], one per non-empty bucket in output
+        order, complete whatever out_cap is.  The scanner's mode must be HIP_PIKE_FIRST.  Returns RouteKeyInfo(nlines,
+        nkeyed, nmembers, nselected, nbuckets, need_bytes, nwritten, out_bytes)."""
+        groups = list(groups)
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        info = (_sz * 8)()
+        if self.lib.sre_hip_route_lines_by_key(self.h, ptr, length, delim, arr, len(groups), keyset.h if keyset is not None else None,
+                                               HIP_LINES_ALL if all_lines else 0, out_ptr, out_cap, keyid_ptr, keyid_cap, index_ptr,
+                                               index_cap, buckets_ptr, buckets_cap, info, hip_stream) != 0:
+            raise RuntimeError("sre_hip_route_lines_by_key failed")
+        return RouteKeyInfo(*info)
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -725,6 +747,7 @@ RouteBucket = collections.namedtuple("RouteBucket", "nlines offset bytes")
 ContextInfo = collections.namedtuple("ContextInfo", "nlines nmatched nselected ngroups need_bytes nwritten out_bytes")
 TallyInfo = collections.namedtuple("TallyInfo", "nlines nselected nkeys need_bytes nwritten out_bytes")
 LookupInfo = collections.namedtuple("LookupInfo", "nlines nkeyed nmembers nselected need_bytes nwritten out_bytes")
+RouteKeyInfo = collections.namedtuple("RouteKeyInfo", "nlines nkeyed nmembers nselected nbuckets need_bytes nwritten out_bytes")
 
 
 class TallyInfoStruct(ctypes.Structure):

@@ -22,6 +22,7 @@
 #include "sre_hip_lines.h"
 #include "sre_lines_gather.h"
 #include "sre_lines_route.h"
+#include "sre_lines_route_key.h"
 #include "sre_lines_tally.h"
 #include "sre_lines_sums.h"
 #include "sre_lines_keyset.h"
@@ -184,6 +185,12 @@ struct sre_hip_scanner_s {
      * (1 + columns), the key table the lookup's (d_vval, d_vstart); it adds */
     int64_t                  *d_jkey;           /* the key id of every line, for the index */
     size_t                    jkey_cap;
+    /* the line route by key (sre_hip_route_lines_by_key): the key table is the lookup's (d_vval, d_vstart), the key ids d_jkey's
+     * words, the counts of a pass d_rcnt's, the compact table the route's (d_fstart, d_rval), the head ranks d_rmeta's words,
+     * the scans' sums d_fblk's, the result words d_rres's; it adds */
+    uint64_t                 *d_kitem[2];       /* the items of the partition, pass by pass from one to the other: selected lines
+                                                   + 1 words each (the spare one ends as the scan of the head flags) */
+    size_t                    kitem_cap[2];
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -261,6 +268,8 @@ scanner_release(void *data)
     if (sc->d_vstart) (void) hipFree(sc->d_vstart);
     if (sc->d_vcopy) (void) hipFree(sc->d_vcopy);
     if (sc->d_jkey) (void) hipFree(sc->d_jkey);
+    if (sc->d_kitem[0]) (void) hipFree(sc->d_kitem[0]);
+    if (sc->d_kitem[1]) (void) hipFree(sc->d_kitem[1]);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -2986,6 +2995,142 @@ sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
             }
             SRE_HIP_TRY(hipStreamSynchronize(stream));
         }
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* the digit width of the route by key: SRE_HIP_ROUTE_KEY_DIGIT_BITS (test knob, read on every call; 1 .. 8), else 8 */
+static uint32_t
+route_key_digit_bits(void)
+{
+    const char *e = getenv("SRE_HIP_ROUTE_KEY_DIGIT_BITS");
+    return sre_lrk_digit_bits(e && *e ? atol(e) : 0);
+}
+
+/* ... and its rank rule inside a slot: SRE_HIP_ROUTE_KEY_RANK=turns (measurement knob, read on every call) takes the route's
+ * wave rule, anything else the ballots per digit bit; the results are the same */
+static int
+route_key_rank_rule(void)
+{
+    const char *e = getenv("SRE_HIP_ROUTE_KEY_RANK");
+    return e && strcmp(e, "turns") == 0 ? SRE_LRK_RANK_TURNS : SRE_LRK_RANK_BITS;
+}
+
+/* The line route by key: the lookup's call and probe, the key ids into the scanner's own array; then the
+ * stable partition of the lines by their sort key, one count / scan / scatter per digit, with one read of the selected lines
+ * behind the first scan; then the compact table from the sorted items, the scans over its values and over the head flags,
+ * the bucket rows, the cut, one read of the result words, the extract's gather over the compact table and the index rows. */
+extern "C" SRE_API int
+sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+    const sre_hip_keyset_t *ks, int flags, void *d_out, size_t out_cap, sre_int_t *d_keyid, size_t keyid_cap, sre_int_t *d_index,
+    size_t index_cap, sre_int_t *d_buckets, size_t buckets_cap, sre_hip_route_key_info_t *info, void *hip_stream)
+{
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    if (ks == NULL || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1 || (keyid_cap != 0 && d_keyid == NULL)
+        || (buckets_cap != 0 && d_buckets == NULL))
+    {
+        return -1;
+    }
+    /* (the sink's row rule is the filter's mode 0 whatever the flags are, as in the lookup: the sort key applies them) */
+    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap) || ngroups != ks->k) return -1;
+    if (!sink_first_match(sc, "line route by key", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
+    sink.vgroups = &gr;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_route_key_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n > SRE_LRK_MAX_LINES) {
+        fprintf(stderr, "[sregex-hip] line route by key: %llu lines, at most 2^32 - 1\n", (unsigned long long) n);
+        return -1;
+    }
+    if (n != 0) {
+        const int      all = (flags & SRE_HIP_LINES_ALL) != 0, rule = route_key_rank_rule();
+        const uint64_t rows = ks->rows;
+        const uint32_t bits = route_key_digit_bits(), passes = sre_lrk_passes(sre_lrk_max_key(rows, all), bits);
+        const uint64_t nd = (uint64_t) 1 << bits, nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nd * nwg;
+        /* (the scans' sums: over the counts of a pass, then over at most n entries of the compact table) */
+        const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
+        static_assert(SRE_LRK_RES_WORDS <= SRE_LR_RES_WORDS + 2 * SRE_LR_MAX_BUCKETS, "the result words fit the route's");
+        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) return -1;
+        if (sc->d_rres == NULL) {
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
+            SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
+        }
+        /* the lookup's probe, the ids of all lines into the scanner's array; the caller's are a copy */
+        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_keyset_probe(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen, ks->d_tab,
+                                            ks->nslots, ks->hash_mask, 0, sc->d_fval, sc->d_jkey, n, sc->d_linfo, stream));
+        if (keyid_cap != 0) {
+            SRE_HIP_TRY(hipMemcpyAsync(d_keyid, sc->d_jkey, (keyid_cap < n ? keyid_cap : n) * sizeof(int64_t), hipMemcpyDeviceToDevice,
+                                       stream));
+        }
+        /* pass 0 over the lines; its total sizes the item arrays and the compact table */
+        SRE_HIP_TRY(sre_launch_route_key_count(sc->d_jkey, NULL, n, rows, all, 0, bits, rule, sc->d_rcnt, stream));
+        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, ncnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rcnt + ncnt, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t nsel = sc->h_rres[0];
+        if (nsel > n) return -1;        /* (cannot happen: every line is counted once) */
+        const uint64_t *hoff = NULL, *items = NULL;
+        if (nsel != 0) {
+            uint32_t cur = 0;
+            if (lines_grow(&sc->d_kitem[0], &sc->kitem_cap[0], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_kitem[1], &sc->kitem_cap[1], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_fstart, &sc->fstart_cap, nsel * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_rval, &sc->rval_cap, (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_rmeta, &sc->rmeta_cap, (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            SRE_HIP_TRY(sre_launch_route_key_scatter(sc->d_jkey, NULL, n, rows, all, 0, bits, rule, sc->d_rcnt, nsel, sc->d_kitem[0],
+                                                     stream));
+            /* the later passes over the nsel items, from one array to the other */
+            for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
+                const uint64_t pcnt = nd * ((nsel + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
+                SRE_HIP_TRY(sre_launch_route_key_count(NULL, sc->d_kitem[cur], nsel, rows, all, p, bits, rule, sc->d_rcnt, stream));
+                SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+                SRE_HIP_TRY(sre_launch_route_key_scatter(NULL, sc->d_kitem[cur], nsel, rows, all, p, bits, rule, sc->d_rcnt, nsel,
+                                                         sc->d_kitem[cur ^ 1u], stream));
+            }
+            /* the compact table and the head flags from the sorted items; the scan of the flags, then of the values (the
+             * second leaves the words of d_linfo as the cut at out_cap gives them) */
+            uint64_t *head = sc->d_kitem[cur ^ 1u];
+            items = sc->d_kitem[cur];
+            SRE_HIP_TRY(sre_launch_route_key_table(items, sc->d_ends, nsel, n, sc->d_fstart, sc->d_rval, head, stream));
+            SRE_HIP_TRY(sre_launch_filter_offsets(head, nsel, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+            SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rval, nsel, sc->d_fblk, out_cap, sc->d_linfo, stream));
+            SRE_HIP_TRY(sre_launch_route_key_buckets(items, head, sc->d_rmeta, sc->d_rval, nsel, rows, buckets_cap,
+                                                     reinterpret_cast<int64_t *>(d_buckets), stream));
+            hoff = head;
+        }
+        SRE_HIP_TRY(sre_launch_route_key_finish(sc->d_rval, hoff, nsel, out_cap, sc->d_linfo, sc->d_rres, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, SRE_LRK_RES_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nkeyed = (size_t) sc->h_rres[SRE_LRK_RES_NKEYED];
+        res.nmembers = (size_t) sc->h_rres[SRE_LRK_RES_NMEMBERS];
+        res.nselected = (size_t) sc->h_rres[SRE_LRK_RES_NSEL];
+        res.nbuckets = (size_t) sc->h_rres[SRE_LRK_RES_NBUCKETS];
+        res.need_bytes = (size_t) sc->h_rres[SRE_LRK_RES_NEED];
+        res.nwritten = (size_t) sc->h_rres[SRE_LRK_RES_WRITTEN];
+        res.out_bytes = (size_t) sc->h_rres[SRE_LRK_RES_BYTES];
+        if (res.out_bytes > out_cap || res.nselected != nsel || res.nwritten > nsel) return -1;     /* (cannot happen) */
+        if (res.out_bytes != 0) {
+            /* the compact table is an entry table with one entry a line: the extract's gather, unchanged */
+            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_fstart, nsel, res.out_bytes, (uint32_t) delim,
+                                                  (uint32_t) delim, stream));
+        }
+        if (res.nwritten != 0 && index_cap != 0) {
+            const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
+            SRE_HIP_TRY(sre_launch_route_key_index(items, sc->d_fstart, sc->d_rval, sc->d_rres, rows, nrows,
+                                                   index_cap, reinterpret_cast<int64_t *>(d_index), stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
     if (info) *info = res;
     return 0;

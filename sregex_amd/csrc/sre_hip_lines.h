@@ -262,6 +262,32 @@ hipError_t sre_launch_join_gather(const void *d_buf, void *d_out, const uint64_t
 hipError_t sre_launch_join_index(const uint64_t *d_off, const uint64_t *d_start, const uint64_t *d_ends, const int64_t *d_keyid,
     uint64_t n, uint32_t p, const uint64_t *d_blk, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
+/* ---- the line route by key (sre_hip_lines_route_key.hip, sre_lines_route_key.h) ---- */
+/* one digit pass of the stable partition, count then (behind sre_launch_filter_offsets over the nd * nwg counts, nd =
+ * 2^bits, nwg = ceil(n / SRE_LINES_ITEMS)) scatter.  Pass 0 (d_keyid != NULL, d_src unused): the n lines in line order, line
+ * i the item of sort key sre_lrk_sort_key(d_keyid[i], rows, all) or dropped.  A later pass (d_keyid == NULL): the n items
+ * of d_src.  d_cnt[d * nwg + w] = items of digit d of workgroup w; the scatter stores every item at its rank of d_dst, which
+ * holds `total` = d_first[nd * nwg] items.  rule: SRE_LRK_RANK_BITS or SRE_LRK_RANK_TURNS, with the same result */
+hipError_t sre_launch_route_key_count(const int64_t *d_keyid, const uint64_t *d_src, uint64_t n, uint64_t rows, int all,
+    uint32_t pass, uint32_t bits, int rule, uint64_t *d_cnt, hipStream_t stream);
+hipError_t sre_launch_route_key_scatter(const int64_t *d_keyid, const uint64_t *d_src, uint64_t n, uint64_t rows, int all,
+    uint32_t pass, uint32_t bits, int rule, const uint64_t *d_first, uint64_t total, uint64_t *d_dst, hipStream_t stream);
+/* the compact table from the nsel sorted items: d_cstart[r] the source offset of rank r's line under SRE_LG_ENTRY_LAST |
+ * FIRST, d_cval[r] = len + 1, d_head[r] = 1 where rank r is the first of its key, else 0 */
+hipError_t sre_launch_route_key_table(const uint64_t *d_items, const uint64_t *d_ends, uint64_t nsel, uint64_t nlines,
+    uint64_t *d_cstart, uint64_t *d_cval, uint64_t *d_head, hipStream_t stream);
+/* behind sre_launch_filter_offsets over d_head (d_hoff[0 .. nsel]) and over d_cval (d_coff[0 .. nsel]): d_hrank[b] = the rank
+ * of bucket b's first line, d_hrank[nbuckets] = nsel (nsel + 1 words), then rows [id, first rank, lines, output offset,
+ * bytes] of the first min(buckets_cap, nbuckets) buckets */
+hipError_t sre_launch_route_key_buckets(const uint64_t *d_items, const uint64_t *d_hoff, uint64_t *d_hrank, const uint64_t *d_coff,
+    uint64_t nsel, uint64_t rows, uint64_t buckets_cap, int64_t *d_buckets, hipStream_t stream);
+/* d_res[0 .. SRE_LRK_RES_WORDS): nsel, the bytes of all rows, the rows that fit out_cap whole, their bytes, the non-empty
+ * buckets, info->knkeyed, info->knmembers.  d_coff and d_hoff are not read when nsel == 0 */
+hipError_t sre_launch_route_key_finish(const uint64_t *d_coff, const uint64_t *d_hoff, uint64_t nsel, uint64_t out_cap,
+    const sre_lines_info_t *d_info, uint64_t *d_res, hipStream_t stream);
+/* rows [line, start, len, output offset, id or -1 / -2] of the first min(index_cap, d_res[2]) ranks; nrows: that number */
+hipError_t sre_launch_route_key_index(const uint64_t *d_items, const uint64_t *d_cstart, const uint64_t *d_coff,
+    const uint64_t *d_res, uint64_t rows, uint64_t nrows, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif
