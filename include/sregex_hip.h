@@ -959,6 +959,95 @@ SRE_API int sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf,
     sre_int_t *d_buckets, size_t buckets_cap,
     sre_hip_route_key_info_t *info, void *hip_stream);
 
+/* ---- the line sort: order lines by a numeric capture group, with top-k ---- */
+
+enum { SRE_HIP_SORT_DESC = 4 };   /* largest value first */
+
+typedef struct {
+    size_t  nlines;
+    size_t  nkeyed;      /* lines with a match */
+    size_t  nnumbered;   /* of those, lines whose sort field is a number */
+    size_t  nselected;   /* rows of the full output: min(limit, candidates), limit == 0: all */
+    size_t  need_bytes, nwritten, out_bytes;
+    size_t  passes;      /* digit passes the call made (0 when nothing was selected) */
+    int64_t vmin, vmax;  /* over the numbered lines; INT64_MAX / INT64_MIN when there is none */
+} sre_hip_sort_info_t;
+
+/*
+ * Line sort: the lines of d_buf ordered by the number in one capture group of their first match,
+ * optionally only the first `limit` of them (`sort -s -n -k`, `sort -s -rn | head`, ORDER BY v
+ * [DESC] LIMIT k: "the 100 slowest requests", "responses by size, largest first").
+ *
+ * On the same (sc, d_buf, len, delim) and groups = {group} the split, the matching, the routing to
+ * an engine, the batching, the diagnostics, the demand for an SRE_HIP_PIKE_FIRST scanner (Thompson
+ * and COUNT scanners return -1 with a diagnostic), the range rule of `group` and the overlap check
+ * of d_out are exactly those of sre_hip_lookup_lines.
+ *
+ * The value.  A line is NUMBERED when it has a match and the text of `group` in its first match
+ * is a number under the number rule of sre_hip_tally_sums_lines (sre_hip_tally_number tells the
+ * same on the host): "-0" is 0 and "007" is 7; an unset or empty group, "+1", "1 " and 19 digits
+ * are not numbers.  Its value is that number.  info->nkeyed counts the lines with a match,
+ * info->nnumbered the numbered ones, info->vmin and info->vmax are the extremes of the values.
+ *
+ * Selection and order.  flags == 0 selects the numbered lines, ordered by value ascending;
+ * SRE_HIP_SORT_DESC orders them descending.  Lines of equal value stay in line order in BOTH
+ * directions (sort -s -n, sort -s -n -r).  SRE_HIP_LINES_ALL selects every line: the lines that
+ * are not numbered (keyed lines whose field is no number, and lines without a match) come behind
+ * ALL numbered lines, in line order, whatever the direction, so the output is a permutation of
+ * the input's lines.  limit != 0 keeps the first `limit` rows of that order (| head -n limit):
+ * info->nselected and info->need_bytes describe the limited output; nnumbered, nkeyed, vmin and
+ * vmax are totals over the buffer whatever limit and out_cap are.  SRE_HIP_LINES_INVERT and every
+ * other bit return -1.
+ *
+ * Each row is the line's bytes plus ONE delim, so the output is a line buffer again.  Because the
+ * sort is stable, a second call on the output sorts by a second column: sort by column B, then
+ * sort the result by column A, and the lines are ordered by (A, B, line).  That is why one column
+ * a call is enough.
+ *
+ * Truncation, the sizing call and the guards are those of sre_hip_route_lines: whole lines only,
+ * in output order; nothing at or beyond out_bytes is touched and nothing in front of d_out; d_out
+ * == NULL with out_cap == 0 sizes the output.  A NULL pointer with a cap other than 0 returns -1,
+ * for d_out and d_index alike.  len == 0 gives zeros and success, with vmin / vmax the identities
+ * INT64_MAX / INT64_MIN.
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten) rows
+ * in output order it receives 6 sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the line in d_out   [4] the value (0 when the line is not numbered)
+ *   [5] the class: 1 numbered, -1 keyed but no number, -2 no match.
+ *
+ * Limits.  A sort item carries the line number in 32 bits: a buffer may hold at most 2^32 - 1
+ * lines, a larger one returns -1 with one diagnostic line.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  Up to the value table the host
+ * waits as often as in sre_hip_lookup_lines; behind it as often as in sre_hip_route_lines_by_key:
+ * one read of four words (nkeyed, nnumbered, vmin, vmax) that sizes the item arrays and fixes the
+ * keys, one read of 4 result words, then the end.  Nothing per line travels to the host.  The
+ * sort key is the value's distance from vmin (from vmax when descending), an unsigned 64-bit word;
+ * the sort is a stable radix sort of one 8-bit digit of it per pass, and the pass count follows
+ * the DATA: info->passes is 1 for values within 255 of each other, 2 for HTTP status codes, 3 for
+ * a range below 2^24, 8 for the full 18-digit range.  It is always the full sort, then the cut at limit: every pass
+ * runs over all selected lines however small limit is.
+ *
+ * Memory.  Beyond what sre_hip_lookup_lines takes, a scanner keeps of the largest call 9 bytes per
+ * line (the values, shared with sre_hip_join_lines' key ids, and one byte of class), 2 KiB per
+ * 1024 lines (the counts of a pass, shared with sre_hip_route_lines), per selected line 24 bytes
+ * for the two pairs of item arrays (16 of them shared with sre_hip_route_lines_by_key) and per
+ * row in front of the limit 16 bytes for the compact table (shared with sre_hip_route_lines); all
+ * grow-only device memory, freed with the scanner.
+ *
+ * Not offered: text or locale order, floating point, sort -u; several columns in one call
+ * (compose, see above); sorting extracted fields instead of whole lines (extract from the sorted
+ * output); a per-line value array supplied by the caller (it would give "tally rows by count");
+ * INVERT, every match of a line; Thompson and COUNT scanners, stream sets.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    int group, int flags, size_t limit,
+    void *d_out, size_t out_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_sort_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

@@ -27,6 +27,7 @@ HIP_THOMPSON, HIP_PIKE_FIRST, HIP_PIKE_COUNT = 0, 1, 2
 ENGINE_AUTO, ENGINE_VM, ENGINE_SCAN, ENGINE_NFA = 0, 1, 2, 3
 HIP_LINES_ALL = 1
 HIP_LINES_INVERT = 2
+HIP_SORT_DESC = 4
 HIP_EXTRACT_MAX_FIELDS = 32
 HIP_SUBST_MAX_PIECES = 30
 HIP_JOIN_MAX_VALUES = 31
@@ -121,6 +122,7 @@ API = {
                                           _vp, _vp]),
     "sre_hip_route_lines_by_key": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int,
                                                   _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_sort_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -727,6 +729,24 @@ class Scanner:
             raise RuntimeError("sre_hip_route_lines_by_key failed")
         return RouteKeyInfo(*info)
 
+    def sort_lines(self, ptr, length, out_ptr, out_cap, group, delim=0x0A, descending=False, all_lines=False, limit=0,
+                   index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_sort_lines: the lines of the device buffer (ptr, length) whose capture group `group` of the first match is
+        a number (tally_number's rule), ordered by that number, ascending or (descending) largest first; equal values stay
+        in line order either way.  The device buffer (out_ptr, out_cap) receives them, each followed by one delimiter.
+        With all_lines every line: the lines that are not numbered follow all numbered ones in line order.  limit != 0
+        keeps the first `limit` rows of that order.  index_ptr: an optional device array of index_cap rows [line no, offset
+        in the buffer, length, offset in the output, value, class (1 numbered, -1 keyed but no number, -2 no match)] in
+        output order.  The sort is stable, so sorting the output again by another group orders by (second, first, line).
+        The scanner's mode must be HIP_PIKE_FIRST.  Returns SortInfo(nlines, nkeyed, nnumbered, nselected, need_bytes,
+        nwritten, out_bytes, passes, vmin, vmax)."""
+        info = SortInfoStruct()
+        flags = (HIP_LINES_ALL if all_lines else 0) | (HIP_SORT_DESC if descending else 0)
+        if self.lib.sre_hip_sort_lines(self.h, ptr, length, delim, group, flags, limit, out_ptr, out_cap, index_ptr, index_cap,
+                                       ctypes.byref(info), hip_stream) != 0:
+            raise RuntimeError("sre_hip_sort_lines failed")
+        return SortInfo(*(getattr(info, name) for name in SortInfo._fields))
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -748,6 +768,12 @@ ContextInfo = collections.namedtuple("ContextInfo", "nlines nmatched nselected n
 TallyInfo = collections.namedtuple("TallyInfo", "nlines nselected nkeys need_bytes nwritten out_bytes")
 LookupInfo = collections.namedtuple("LookupInfo", "nlines nkeyed nmembers nselected need_bytes nwritten out_bytes")
 RouteKeyInfo = collections.namedtuple("RouteKeyInfo", "nlines nkeyed nmembers nselected nbuckets need_bytes nwritten out_bytes")
+SortInfo = collections.namedtuple("SortInfo", "nlines nkeyed nnumbered nselected need_bytes nwritten out_bytes passes vmin vmax")
+
+
+class SortInfoStruct(ctypes.Structure):
+    """sre_hip_sort_info_t"""
+    _fields_ = [(name, ctypes.c_int64 if name in ("vmin", "vmax") else ctypes.c_size_t) for name in SortInfo._fields]
 
 
 class TallyInfoStruct(ctypes.Structure):

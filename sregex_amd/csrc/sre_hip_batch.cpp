@@ -23,6 +23,7 @@
 #include "sre_lines_gather.h"
 #include "sre_lines_route.h"
 #include "sre_lines_route_key.h"
+#include "sre_lines_sort.h"
 #include "sre_lines_tally.h"
 #include "sre_lines_sums.h"
 #include "sre_lines_keyset.h"
@@ -191,6 +192,13 @@ struct sre_hip_scanner_s {
     uint64_t                 *d_kitem[2];       /* the items of the partition, pass by pass from one to the other: selected lines
                                                    + 1 words each (the spare one ends as the scan of the head flags) */
     size_t                    kitem_cap[2];
+    /* the line sort (sre_hip_sort_lines): the value table is the lookup's key table (d_vval, d_vstart), the per-line values
+     * d_jkey's words, the keys of the items d_kitem's, the counts of a pass d_rcnt's, the compact table the route's (d_fstart,
+     * d_rval), the scans' sums d_fblk's, the result words d_rres's; it adds */
+    int8_t                   *d_sclass;         /* the class of every line */
+    size_t                    sclass_cap;
+    uint32_t                 *d_sline[2];       /* the lines of the items, moved with their keys: selected lines words each */
+    size_t                    sline_cap[2];
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -270,6 +278,9 @@ scanner_release(void *data)
     if (sc->d_jkey) (void) hipFree(sc->d_jkey);
     if (sc->d_kitem[0]) (void) hipFree(sc->d_kitem[0]);
     if (sc->d_kitem[1]) (void) hipFree(sc->d_kitem[1]);
+    if (sc->d_sclass) (void) hipFree(sc->d_sclass);
+    if (sc->d_sline[0]) (void) hipFree(sc->d_sline[0]);
+    if (sc->d_sline[1]) (void) hipFree(sc->d_sline[1]);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -3129,6 +3140,122 @@ sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf, size_t len,
             const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
             SRE_HIP_TRY(sre_launch_route_key_index(items, sc->d_fstart, sc->d_rval, sc->d_rres, rows, nrows,
                                                    index_cap, reinterpret_cast<int64_t *>(d_index), stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The line sort: the lookup's call with the one sort group as its value group; then the values pass,
+ * which leaves the value and the class of every line and the four totals; one read of those, which sizes the item arrays and
+ * fixes the keys and the number of passes; then one count / scan / scatter per digit of the key, the compact table of the
+ * rows in front of the limit, its scan and cut, one read of the result words, the extract's gather over the compact table
+ * and the index rows. */
+extern "C" SRE_API int
+sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int group, int flags, size_t limit, void *d_out,
+    size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_sort_info_t *info, void *hip_stream)
+{
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    if ((flags & ~(SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC)) != 0) return -1;
+    /* (the sink's row rule is the filter's mode 0 whatever the flags are, as in the lookup: the sort key applies them) */
+    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
+    if (!sink_first_match(sc, "line sort", "captures") || !sink_groups(sc, &group, 1, &gr)) return -1;
+    sink.vgroups = &gr;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_sort_info_t res;
+    memset(&res, 0, sizeof(res));
+    res.vmin = INT64_MAX;
+    res.vmax = INT64_MIN;
+    if (n > SRE_LRK_MAX_LINES) {
+        fprintf(stderr, "[sregex-hip] line sort: %llu lines, at most 2^32 - 1\n", (unsigned long long) n);
+        return -1;
+    }
+    if (n != 0) {
+        const int      all = (flags & SRE_HIP_LINES_ALL) != 0, desc = (flags & SRE_HIP_SORT_DESC) != 0;
+        const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS, nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nd * nwg;
+        /* (the scans' sums: over the counts of a pass, then over at most n entries of the compact table) */
+        const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
+        static_assert(SRE_LSO_RES_WORDS <= SRE_LR_RES_WORDS + 2 * SRE_LR_MAX_BUCKETS, "the result words fit the route's");
+        static_assert(offsetof(sre_lines_info_t, snumbered) == offsetof(sre_lines_info_t, skeyed) + sizeof(uint64_t)
+                          && offsetof(sre_lines_info_t, svmin) == offsetof(sre_lines_info_t, skeyed) + 2 * sizeof(uint64_t)
+                          && offsetof(sre_lines_info_t, svmax) == offsetof(sre_lines_info_t, skeyed) + 3 * sizeof(uint64_t),
+                      "skeyed, snumbered, svmin, svmax are the four totals of the values pass, in that order");
+        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_sclass, &sc->sclass_cap, n * sizeof(int8_t)) != 0) return -1;
+        if (sc->d_rres == NULL) {
+            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
+            SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
+        }
+        /* the value and the class of every line, and the totals: the one read that sizes everything behind it */
+        SRE_HIP_TRY(sre_launch_sort_values(d_buf, sc->d_vval, sc->d_vstart, n, sc->d_jkey, sc->d_sclass, &sc->d_linfo->skeyed, stream));
+        SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(skeyed), LINFO(snumbered), LINFO(svmin), LINFO(svmax)}));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t nkeyed = sc->h_linfo->skeyed, nnum = sc->h_linfo->snumbered;
+        const int64_t  vmin = (int64_t) sc->h_linfo->svmin, vmax = (int64_t) sc->h_linfo->svmax;
+        if (nnum > nkeyed || nkeyed > n || (nnum != 0 && vmin > vmax)) return -1;        /* (cannot happen) */
+        const uint64_t range = sre_lso_range(nnum, vmin, vmax), nsel = sre_lso_selected(n, nnum, all);
+        const uint64_t nout = sre_lso_limited(nsel, limit);
+        const uint32_t passes = sre_lso_passes(n, nnum, range, all);
+        const uint32_t *lines = NULL;
+        if (nsel != 0) {
+            uint32_t cur = 0;
+            if (lines_grow(&sc->d_kitem[0], &sc->kitem_cap[0], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_kitem[1], &sc->kitem_cap[1], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_sline[0], &sc->sline_cap[0], nsel * sizeof(uint32_t)) != 0) return -1;
+            if (lines_grow(&sc->d_sline[1], &sc->sline_cap[1], nsel * sizeof(uint32_t)) != 0) return -1;
+            if (lines_grow(&sc->d_fstart, &sc->fstart_cap, nout * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_rval, &sc->rval_cap, (nout + 1) * sizeof(uint64_t)) != 0) return -1;
+            /* pass 0 over the lines makes the items and drops the unselected */
+            SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt, stream));
+            SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, ncnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+            SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt,
+                                                nsel, sc->d_kitem[0], sc->d_sline[0], stream));
+            /* the later passes over the nsel items, from one pair of arrays to the other */
+            for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
+                const uint64_t pcnt = nd * ((nsel + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
+                SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nsel, vmin, vmax, nnum, desc, all, p, sc->d_rcnt, stream));
+                SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+                SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nsel, vmin, vmax, nnum, desc, all, p,
+                                                    sc->d_rcnt, nsel, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
+            }
+            /* the compact table of the rows in front of the limit; its scan leaves the words of d_linfo as the cut at out_cap
+             * gives them */
+            lines = sc->d_sline[cur];
+            SRE_HIP_TRY(sre_launch_sort_table(lines, sc->d_ends, nout, n, sc->d_fstart, sc->d_rval, stream));
+            SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rval, nout, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        }
+        SRE_HIP_TRY(sre_launch_sort_finish(sc->d_rval, nout, out_cap, sc->d_rres, stream));
+        SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, SRE_LSO_RES_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nkeyed = (size_t) nkeyed;
+        res.nnumbered = (size_t) nnum;
+        res.nselected = (size_t) sc->h_rres[SRE_LSO_RES_NSEL];
+        res.need_bytes = (size_t) sc->h_rres[SRE_LSO_RES_NEED];
+        res.nwritten = (size_t) sc->h_rres[SRE_LSO_RES_WRITTEN];
+        res.out_bytes = (size_t) sc->h_rres[SRE_LSO_RES_BYTES];
+        res.passes = passes;
+        res.vmin = vmin;
+        res.vmax = vmax;
+        if (res.out_bytes > out_cap || res.nselected != nout || res.nwritten > nout) return -1;     /* (cannot happen) */
+        if (res.out_bytes != 0) {
+            /* the compact table is an entry table with one entry a line: the extract's gather, unchanged */
+            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_fstart, nout, res.out_bytes, (uint32_t) delim,
+                                                  (uint32_t) delim, stream));
+        }
+        if (res.nwritten != 0 && index_cap != 0) {
+            const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
+            SRE_HIP_TRY(sre_launch_sort_index(lines, sc->d_fstart, sc->d_rval, sc->d_rres, sc->d_jkey, sc->d_sclass, n, nrows, index_cap,
+                                              reinterpret_cast<int64_t *>(d_index), stream));
         }
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }

@@ -58,6 +58,11 @@ typedef struct {
     /* the line lookup (sre_hip_lookup_lines): two more words, read with the four (zeroed in front of the probe) */
     uint64_t knkeyed;       /* lines that have a key */
     uint64_t knmembers;     /* of those, lines whose key is in the set */
+    /* the line sort (sre_hip_sort_lines): four words of its own, set by the values pass and read in one copy */
+    uint64_t skeyed;        /* lines that have a match */
+    uint64_t snumbered;     /* of those, lines whose sort field is a number */
+    uint64_t svmin;         /* the least of those numbers, an int64_t (INT64_MAX without one) */
+    uint64_t svmax;         /* the greatest, an int64_t (INT64_MIN without one) */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -288,6 +293,35 @@ hipError_t sre_launch_route_key_finish(const uint64_t *d_coff, const uint64_t *d
 /* rows [line, start, len, output offset, id or -1 / -2] of the first min(index_cap, d_res[2]) ranks; nrows: that number */
 hipError_t sre_launch_route_key_index(const uint64_t *d_items, const uint64_t *d_cstart, const uint64_t *d_coff,
     const uint64_t *d_res, uint64_t rows, uint64_t nrows, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
+/* ---- the line sort (sre_hip_lines_sort.hip, sre_lines_sort.h) ---- */
+/* behind the last select pass, a lane per line: d_value[i] and d_class[i] of every line i < n from entry i of the value table
+ * of the ONE sort group (d_vval / d_vstart: the entry table of sre_launch_extract_select over that group); d_totals[0 .. 4) =
+ * the keyed lines, the numbered lines, the minimum and the maximum of the values (int64_t; set to 0, 0, INT64_MAX, INT64_MIN
+ * first), at most one add per count, one minimum and one maximum per workgroup of 1024 lines */
+hipError_t sre_launch_sort_values(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, int64_t *d_value,
+    int8_t *d_class, uint64_t *d_totals, hipStream_t stream);
+/* one digit pass of the sort, count then (behind sre_launch_filter_offsets over the 256 * nwg counts, nwg = ceil(n /
+ * SRE_LINES_ITEMS)) scatter; the digit is bits pass * 8 .. pass * 8 + 7 of the 64-bit key, pass < 8.  Pass 0 (d_value != NULL,
+ * d_src / d_sline unused): the n lines in line order, line i the item of key sre_lso_key(d_class[i], d_value[i], ...) from the
+ * totals the host read, or dropped.  A later pass (d_value == NULL): the n items (d_src[i], d_sline[i]), total == n.
+ * d_cnt[d * nwg + w] = items of digit d of workgroup w; the scatter stores the key and the line of every item at its rank of
+ * d_dkey / d_dline, which hold `total` = d_first[256 * nwg] items */
+hipError_t sre_launch_sort_count(const int64_t *d_value, const int8_t *d_class, const uint64_t *d_src, uint64_t n, int64_t vmin,
+    int64_t vmax, uint64_t nnumbered, int desc, int all, uint32_t pass, uint64_t *d_cnt, hipStream_t stream);
+hipError_t sre_launch_sort_scatter(const int64_t *d_value, const int8_t *d_class, const uint64_t *d_src, const uint32_t *d_sline,
+    uint64_t n, int64_t vmin, int64_t vmax, uint64_t nnumbered, int desc, int all, uint32_t pass, const uint64_t *d_first,
+    uint64_t total, uint64_t *d_dkey, uint32_t *d_dline, hipStream_t stream);
+/* the compact table of the first nout ranks of the sorted items: d_cstart[r] the source offset of the line d_lines[r] under
+ * SRE_LG_ENTRY_LAST | FIRST, d_cval[r] = len + 1 */
+hipError_t sre_launch_sort_table(const uint32_t *d_lines, const uint64_t *d_ends, uint64_t nout, uint64_t nlines, uint64_t *d_cstart,
+    uint64_t *d_cval, hipStream_t stream);
+/* behind sre_launch_filter_offsets over d_cval (d_coff[0 .. nout]; not read when nout == 0): d_res[0 .. SRE_LSO_RES_WORDS) =
+ * nout, the bytes of all rows, the rows that fit out_cap whole, their bytes */
+hipError_t sre_launch_sort_finish(const uint64_t *d_coff, uint64_t nout, uint64_t out_cap, uint64_t *d_res, hipStream_t stream);
+/* rows [line, start, len, output offset, value, class] of the first min(index_cap, d_res[2]) ranks; nrows: that number */
+hipError_t sre_launch_sort_index(const uint32_t *d_lines, const uint64_t *d_cstart, const uint64_t *d_coff, const uint64_t *d_res,
+    const int64_t *d_value, const int8_t *d_class, uint64_t nlines, uint64_t nrows, uint64_t index_cap, int64_t *d_index,
+    hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

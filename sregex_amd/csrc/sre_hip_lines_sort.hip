@@ -1,0 +1,315 @@
+/*
+ * sre_hip_lines_sort.hip — the line sort on the device (sregex_hip.h sre_hip_sort_lines): the lines of a
+ * buffer ordered by the number in a capture group, an LSD radix sort of (key, line) items into a compact table the
+ * extract's gather writes out.  The rules are those of sre_lines_sort.h, sre_lines_route_key.h and sre_lines_route.h, which
+ * the CPU model compiles too.
+ *
+ *   values     a lane per line: the class and the value of the line from its entry of the value table, and the four totals
+ *              of the call: at most one add per count, one minimum and one maximum per workgroup of 1024 lines;
+ *   count      per pass: a workgroup takes 1024 keys in order and writes how many have each digit to cnt[d * nwg + w];
+ *              the filter's scan (sre_launch_filter_offsets) over those words gives every (digit, workgroup) its first rank;
+ *   scatter    the same workgroups recompute the rank of every item and store its key and its line at that rank of the
+ *              other pair of arrays.  Pass 0 makes the items from the values in line order and drops the unselected;
+ *   table      a lane per rank in front of the limit: the entry of the compact table;
+ *   finish     one lane: the cut at out_cap and the words the host reads;
+ *   gather     sre_launch_extract_gather over the compact table, unchanged (sre_hip_lines_gather.hip);
+ *   index      a lane per written rank.
+ *
+ * No workgroup waits for another and no rank comes from an atomic.  Plain C++ and vector memory operations only.
+ */
+#include <sregex/sregex.h>
+#include "sre_hip_lines.h"
+#include "sre_lines_sort.h"
+#include "sre_hip_lines_block.h"
+#include "sre_hip_lines_rank.h"
+
+#define LSO_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+namespace {
+
+/* the value table of the one sort group as the values pass reads it (written by earlier kernels or copies: plain loads) */
+struct SortVals {
+    const uint8_t  *buf;
+    const uint64_t *vval, *vstart;
+    __device__ inline uint64_t val(uint64_t line, uint32_t) const { return vval[line]; }
+    __device__ inline uint64_t raw(uint64_t line, uint32_t) const { return vstart[line]; }
+    __device__ inline uint8_t  byte(uint64_t at) const { return buf[at]; }
+};
+
+/* the four words of the call: skeyed, snumbered, svmin, svmax of sre_lines_info_t, in that order */
+struct SortMem {
+    uint64_t *w;
+    __device__ inline void add_keyed(uint64_t v) { (void) __hip_atomic_fetch_add(w + 0, v, LSO_RELAXED_AGENT); }
+    __device__ inline void add_numbered(uint64_t v) { (void) __hip_atomic_fetch_add(w + 1, v, LSO_RELAXED_AGENT); }
+    __device__ inline void min(int64_t v) { (void) __hip_atomic_fetch_min(reinterpret_cast<int64_t *>(w + 2), v, LSO_RELAXED_AGENT); }
+    __device__ inline void max(int64_t v) { (void) __hip_atomic_fetch_max(reinterpret_cast<int64_t *>(w + 3), v, LSO_RELAXED_AGENT); }
+};
+
+/* every lane gets the merge of all 64 lanes' totals */
+__device__ inline sre_lso_totals_t
+wave_merge(sre_lso_totals_t t)
+{
+    for (int d = 1; d < 64; d <<= 1) {
+        sre_lso_totals_t o;
+        o.nkeyed = (uint64_t) __shfl_xor((unsigned long long) t.nkeyed, d, 64);
+        o.nnumbered = (uint64_t) __shfl_xor((unsigned long long) t.nnumbered, d, 64);
+        o.vmin = (int64_t) __shfl_xor((long long) t.vmin, d, 64);
+        o.vmax = (int64_t) __shfl_xor((long long) t.vmax, d, 64);
+        t = sre_lso_merge(t, o);
+    }
+    return t;
+}
+
+/* one lane, in front of the values pass: the identities of the four words */
+__global__ __launch_bounds__(64) void
+sre_k_sort_init(uint64_t *__restrict__ w)
+{
+    if (threadIdx.x != 0) return;
+    const sre_lso_totals_t t = sre_lso_identity();
+    w[0] = t.nkeyed;
+    w[1] = t.nnumbered;
+    w[2] = (uint64_t) t.vmin;
+    w[3] = (uint64_t) t.vmax;
+}
+
+/* workgroup w: the lines w * SRE_LSO_LINES + j * SRE_LSO_THREADS + lane, j = 0 .. SRE_LSO_PER_LANE - 1 */
+__global__ __launch_bounds__(SRE_LSO_THREADS) void
+sre_k_sort_values(const uint8_t *__restrict__ buf, const uint64_t *__restrict__ vval, const uint64_t *__restrict__ vstart, uint64_t n,
+                  int64_t *__restrict__ value, int8_t *__restrict__ cls, uint64_t *totals)
+{
+    __shared__ sre_lso_totals_t part[SRE_LSO_THREADS / 64u];
+    const SortVals   vals = {buf, vval, vstart};
+    sre_lso_totals_t t = sre_lso_identity();
+#pragma unroll
+    for (uint32_t j = 0; j < SRE_LSO_PER_LANE; j++) {
+        const uint64_t i = (uint64_t) blockIdx.x * SRE_LSO_LINES + j * SRE_LSO_THREADS + threadIdx.x;
+        if (i >= n) continue;
+        int64_t       v;
+        const int32_t c = sre_lso_line(vals, i, &v);
+        value[i] = v;
+        cls[i] = (int8_t) c;
+        t = sre_lso_merge(t, sre_lso_single(c, v));
+    }
+    t = wave_merge(t);
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (uint32_t w = 1; w < SRE_LSO_THREADS / 64u; w++) t = sre_lso_merge(t, part[w]);
+    SortMem mem = {totals};
+    sre_lso_flush(mem, t);
+}
+
+/* what every digit pass knows of the call */
+struct SortKeys {
+    int64_t  vmin, vmax;
+    uint64_t range;
+    int      desc, all;
+};
+
+/* key i of a pass: pass 0 (FIRST) makes it from the value and the class of line i, a later pass reads it */
+template <bool FIRST>
+__device__ inline uint64_t
+load_key(const int64_t *__restrict__ value, const int8_t *__restrict__ cls, const uint64_t *__restrict__ src, uint64_t i, uint64_t n,
+         const SortKeys &k)
+{
+    if (i >= n) return SRE_LSO_DROPPED;
+    return FIRST ? sre_lso_key(cls[i], value[i], k.vmin, k.vmax, k.range, k.desc, k.all) : src[i];
+}
+
+/* workgroup w: cnt[d * nwg + w] = its items of digit d */
+template <bool FIRST>
+__global__ __launch_bounds__(SRE_LR_THREADS) void
+sre_k_sort_count(const int64_t *__restrict__ value, const int8_t *__restrict__ cls, const uint64_t *__restrict__ src, uint64_t n,
+                 SortKeys k, uint32_t pass, uint64_t nwg, uint64_t *__restrict__ cnt)
+{
+    __shared__ uint32_t c[SRE_LR_SLOTS << SRE_LSO_DIGIT_BITS];
+    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nd = 1u << SRE_LSO_DIGIT_BITS;
+    for (uint32_t x = threadIdx.x; x < SRE_LR_SLOTS * nd; x += SRE_LR_THREADS) c[x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
+        const uint32_t slot = sre_lr_slot(wave, q);
+        const uint64_t key = load_key<FIRST>(value, cls, src, sre_lr_line(blockIdx.x, slot, lane), n, k);
+        (void) slot_rank<SRE_LRK_RANK_BITS>(key != SRE_LSO_DROPPED, sre_lso_digit(key, pass), SRE_LSO_DIGIT_BITS, lane, c + slot * nd);
+    }
+    __syncthreads();
+    if (threadIdx.x < nd) cnt[sre_lr_cnt_index(threadIdx.x, nwg, blockIdx.x)] = sre_lr_slot_prefix(c + threadIdx.x, nd);
+}
+
+/* the same workgroups over the scanned counts `first`: key and line of every item go to its rank of dkey / dline (total
+ * items).  Pass 0: the line of item i is i; a later pass reads it from sline */
+template <bool FIRST>
+__global__ __launch_bounds__(SRE_LR_THREADS) void
+sre_k_sort_scatter(const int64_t *__restrict__ value, const int8_t *__restrict__ cls, const uint64_t *__restrict__ src,
+                   const uint32_t *__restrict__ sline, uint64_t n, SortKeys k, uint32_t pass, uint64_t nwg,
+                   const uint64_t *__restrict__ first, uint64_t total, uint64_t *__restrict__ dkey, uint32_t *__restrict__ dline)
+{
+    __shared__ uint32_t c[SRE_LR_SLOTS << SRE_LSO_DIGIT_BITS];
+    __shared__ uint64_t gbase[1u << SRE_LSO_DIGIT_BITS];
+    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nd = 1u << SRE_LSO_DIGIT_BITS;
+    uint64_t            key[SRE_LR_ROUNDS];
+    uint32_t            rk[SRE_LR_ROUNDS];
+    for (uint32_t x = threadIdx.x; x < SRE_LR_SLOTS * nd; x += SRE_LR_THREADS) c[x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
+        const uint32_t slot = sre_lr_slot(wave, q);
+        key[q] = load_key<FIRST>(value, cls, src, sre_lr_line(blockIdx.x, slot, lane), n, k);
+        rk[q] = slot_rank<SRE_LRK_RANK_BITS>(key[q] != SRE_LSO_DROPPED, sre_lso_digit(key[q], pass), SRE_LSO_DIGIT_BITS, lane,
+                                             c + slot * nd);
+    }
+    __syncthreads();
+    if (threadIdx.x < nd) {
+        (void) sre_lr_slot_prefix(c + threadIdx.x, nd);
+        gbase[threadIdx.x] = first[sre_lr_cnt_index(threadIdx.x, nwg, blockIdx.x)];
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
+        if (key[q] == SRE_LSO_DROPPED) continue;
+        const uint32_t slot = sre_lr_slot(wave, q);
+        const uint64_t i = sre_lr_line(blockIdx.x, slot, lane);
+        const uint32_t d = sre_lso_digit(key[q], pass);
+        const uint64_t r = gbase[d] + c[slot * nd + d] + rk[q];
+        if (r >= total) continue;       /* (cannot happen: the ranks are a permutation of 0 .. total - 1) */
+        dkey[r] = key[q];
+        dline[r] = FIRST ? (uint32_t) i : sline[i];
+    }
+}
+
+/* a lane per rank in front of nout: its entry of the compact table */
+__global__ __launch_bounds__(256) void
+sre_k_sort_table(const uint32_t *__restrict__ lines, const uint64_t *__restrict__ ends, uint64_t nout, uint64_t nlines,
+                 uint64_t *__restrict__ cstart, uint64_t *__restrict__ cval)
+{
+    const uint64_t r = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (r >= nout) return;
+    const uint64_t i = lines[r];
+    if (i >= nlines) {                  /* (cannot happen: an item carries the number of its line) */
+        cstart[r] = sre_lr_entry_start(0);
+        cval[r] = 1;
+        return;
+    }
+    const uint64_t st = line_start(ends, i);
+    sre_lrk_entry(st, ends[i] - st, cstart + r, cval + r);
+}
+
+/* one lane: the cut and the words the host reads.  coff is not read when nout == 0 */
+__global__ __launch_bounds__(64) void
+sre_k_sort_finish(const uint64_t *__restrict__ coff, uint64_t nout, uint64_t out_cap, uint64_t *__restrict__ res)
+{
+    if (threadIdx.x != 0) return;
+    sre_lso_result(coff, nout, out_cap, res);
+}
+
+/* rows [line, start, len, output offset, value, class] of the first min(index_cap, written) ranks */
+__global__ __launch_bounds__(256) void
+sre_k_sort_index(const uint32_t *__restrict__ lines, const uint64_t *__restrict__ cstart, const uint64_t *__restrict__ coff,
+                 const uint64_t *__restrict__ res, const int64_t *__restrict__ value, const int8_t *__restrict__ cls, uint64_t nlines,
+                 uint64_t index_cap, int64_t *__restrict__ out)
+{
+    const uint64_t written = res[SRE_LSO_RES_WRITTEN];
+    const uint64_t limit = index_cap < written ? index_cap : written;
+    const uint64_t r = (uint64_t) blockIdx.x * 256u + threadIdx.x;
+    if (r >= limit) return;
+    const uint64_t i = lines[r];
+    if (i >= nlines) return;            /* (cannot happen) */
+    sre_lso_index_row(i, cstart, coff, r, value[i], cls[i], out + r * SRE_LSO_INDEX_WORDS);
+}
+
+SortKeys
+sort_keys(int64_t vmin, int64_t vmax, uint64_t nnumbered, int desc, int all)
+{
+    SortKeys k;
+    k.vmin = vmin;
+    k.vmax = vmax;
+    k.range = sre_lso_range(nnumbered, vmin, vmax);
+    k.desc = desc;
+    k.all = all;
+    return k;
+}
+
+}  // namespace
+
+extern "C" hipError_t
+sre_launch_sort_values(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, int64_t *d_value,
+                       int8_t *d_class, uint64_t *d_totals, hipStream_t stream)
+{
+    const uint64_t nwg = (n + SRE_LSO_LINES - 1) / SRE_LSO_LINES;
+    if (n == 0 || nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_sort_init, dim3(1), dim3(64), 0, stream, d_totals);
+    hipLaunchKernelGGL(sre_k_sort_values, dim3((uint32_t) nwg), dim3(SRE_LSO_THREADS), 0, stream, static_cast<const uint8_t *>(d_buf),
+                       d_vval, d_vstart, n, d_value, d_class, d_totals);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_sort_count(const int64_t *d_value, const int8_t *d_class, const uint64_t *d_src, uint64_t n, int64_t vmin, int64_t vmax,
+                      uint64_t nnumbered, int desc, int all, uint32_t pass, uint64_t *d_cnt, hipStream_t stream)
+{
+    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
+    if (n == 0 || pass >= SRE_LSO_MAX_PASSES || nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const SortKeys k = sort_keys(vmin, vmax, nnumbered, desc, all);
+    const dim3     grid((uint32_t) nwg), block(SRE_LR_THREADS);
+    if (d_value) {
+        if (pass != 0 || d_class == NULL) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(sre_k_sort_count<true>, grid, block, 0, stream, d_value, d_class, (const uint64_t *) NULL, n, k, 0u, nwg, d_cnt);
+    } else {
+        hipLaunchKernelGGL(sre_k_sort_count<false>, grid, block, 0, stream, (const int64_t *) NULL, (const int8_t *) NULL, d_src, n, k,
+                           pass, nwg, d_cnt);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_sort_scatter(const int64_t *d_value, const int8_t *d_class, const uint64_t *d_src, const uint32_t *d_sline, uint64_t n,
+                        int64_t vmin, int64_t vmax, uint64_t nnumbered, int desc, int all, uint32_t pass, const uint64_t *d_first,
+                        uint64_t total, uint64_t *d_dkey, uint32_t *d_dline, hipStream_t stream)
+{
+    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
+    if (n == 0 || n > SRE_LRK_MAX_LINES || pass >= SRE_LSO_MAX_PASSES || nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (total == 0) return hipSuccess;
+    const SortKeys k = sort_keys(vmin, vmax, nnumbered, desc, all);
+    const dim3     grid((uint32_t) nwg), block(SRE_LR_THREADS);
+    if (d_value) {
+        if (pass != 0 || d_class == NULL) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(sre_k_sort_scatter<true>, grid, block, 0, stream, d_value, d_class, (const uint64_t *) NULL,
+                           (const uint32_t *) NULL, n, k, 0u, nwg, d_first, total, d_dkey, d_dline);
+    } else {
+        if (total != n) return hipErrorInvalidValue;       /* (a later pass moves every item) */
+        hipLaunchKernelGGL(sre_k_sort_scatter<false>, grid, block, 0, stream, (const int64_t *) NULL, (const int8_t *) NULL, d_src,
+                           d_sline, n, k, pass, nwg, d_first, total, d_dkey, d_dline);
+    }
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_sort_table(const uint32_t *d_lines, const uint64_t *d_ends, uint64_t nout, uint64_t nlines, uint64_t *d_cstart,
+                      uint64_t *d_cval, hipStream_t stream)
+{
+    if (nout == 0) return hipSuccess;
+    const uint64_t nblk = (nout + 255) / 256;
+    if (nblk > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_sort_table, dim3((uint32_t) nblk), dim3(256), 0, stream, d_lines, d_ends, nout, nlines, d_cstart, d_cval);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_sort_finish(const uint64_t *d_coff, uint64_t nout, uint64_t out_cap, uint64_t *d_res, hipStream_t stream)
+{
+    hipLaunchKernelGGL(sre_k_sort_finish, dim3(1), dim3(64), 0, stream, d_coff, nout, out_cap, d_res);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t
+sre_launch_sort_index(const uint32_t *d_lines, const uint64_t *d_cstart, const uint64_t *d_coff, const uint64_t *d_res,
+                      const int64_t *d_value, const int8_t *d_class, uint64_t nlines, uint64_t nrows, uint64_t index_cap,
+                      int64_t *d_index, hipStream_t stream)
+{
+    if (nrows == 0 || index_cap == 0) return hipSuccess;
+    const uint64_t nblk = (nrows + 255) / 256;
+    if (nblk > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sre_k_sort_index, dim3((uint32_t) nblk), dim3(256), 0, stream, d_lines, d_cstart, d_coff, d_res, d_value, d_class,
+                       nlines, index_cap, d_index);
+    return hipGetLastError();
+}
