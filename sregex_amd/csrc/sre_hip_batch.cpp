@@ -2295,6 +2295,102 @@ hip_failed:
     return -1;
 }
 
+/* The keyed calls (the lookup, the join, the route by key, the sort) open alike: the sink's row rule is the filter's mode 0
+ * whatever the caller's flags are, so that every route leaves the per-line values, and the key groups are its value groups,
+ * so that it leaves the key table too; the pass behind the line-mode call applies the flags.  join != 0: the join's table of
+ * `join` entries per line, jsep between the fields of a row, the values from d_dict.  Then the line-mode call */
+static int
+keyed_call(sre_hip_scanner_t *sc, const char *call, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+           void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, uint32_t join, int jsep, const void *d_dict,
+           LinesSink *sink, sre_extract_groups_t *gr, uint64_t *pn, hipStream_t stream)
+{
+    uint64_t nrep = 0;
+    if (!sink_open(sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
+    if (!sink_first_match(sc, call, "captures") || !sink_groups(sc, groups, ngroups, gr)) return -1;
+    sink->vgroups = gr;
+    if (join) {
+        sink->join = join;
+        sink->fsep = jsep;
+        sink->d_dict = d_dict;
+    }
+    return lines_call(sc, d_buf, len, delim, 0, NULL, 0, sink, pn, &nrep, stream);
+}
+
+/* The tail of the lookup and the join behind keyed_call: the two counters zeroed, the call's own pass over the key table
+ * (`pass` queues it), then the sinks' three steps with the counters in the one read, and the wait */
+template <class Pass>
+static int
+keyed_finish(sre_hip_scanner_t *sc, const LinesSink *sink, const void *d_buf, uint64_t n, sre_hip_lookup_info_t *info, hipStream_t stream,
+             Pass pass)
+{
+    sre_hip_lookup_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        static_assert(offsetof(sre_lines_info_t, knmembers) == offsetof(sre_lines_info_t, knkeyed) + sizeof(uint64_t),
+                      "knkeyed, knmembers are zeroed as one run");
+        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(pass());
+        if (sink_offsets(sc, sink, n, stream) != 0) return -1;
+        if (sink_read(sc, sink, n, &res, stream, LINFO(knkeyed), LINFO(knmembers)) != 0) return -1;
+        res.nkeyed = (size_t) sc->h_linfo->knkeyed;
+        res.nmembers = (size_t) sc->h_linfo->knmembers;
+        if (sink_write(sc, sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The calls with a compact table (the route, the route by key, the sort) share what stands around their partition passes.
+ * First the words every pass needs, for n lines and nd digits a pass: the counts, the sums of the scans (over the counts of
+ * a pass, then over at most n entries of the compact table) and the result words */
+static int
+compact_reserve(sre_hip_scanner_t *sc, uint64_t n, uint64_t nd)
+{
+    const uint64_t ncnt = nd * ((n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
+    const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+    const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
+    static_assert(SRE_LRK_RES_WORDS <= SRE_LR_RES_WORDS + 2 * SRE_LR_MAX_BUCKETS && SRE_LSO_RES_WORDS <= SRE_LRK_RES_WORDS,
+                  "the result words fit the route's");
+    if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
+    if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
+    if (sc->d_rres == NULL) {
+        SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
+        SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
+    }
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* ... then the tail behind the call's finish pass: the one read of its nwords result words, the four every info has, and the
+ * extract's gather over the compact table of nrows entries (d_rval, d_fstart: an entry table with one entry a line), queued.
+ * *pindex: the index rows the call's own index pass is to write */
+template <class Info>
+static int
+compact_finish(sre_hip_scanner_t *sc, const LinesSink *sink, const void *d_buf, uint64_t n, size_t nwords, uint64_t nrows, Info *res,
+               uint64_t *pindex, hipStream_t stream)
+{
+    SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    SRE_HIP_TRY(hipStreamSynchronize(stream));
+    res->nlines = (size_t) n;
+    res->nselected = (size_t) sc->h_rres[SRE_LR_RES_NSEL];
+    res->need_bytes = (size_t) sc->h_rres[SRE_LR_RES_NEED];
+    res->nwritten = (size_t) sc->h_rres[SRE_LR_RES_WRITTEN];
+    res->out_bytes = (size_t) sc->h_rres[SRE_LR_RES_BYTES];
+    if (res->out_bytes > sink->out_cap || res->nselected != nrows || res->nwritten > nrows) return -1;      /* (cannot happen) */
+    if (res->out_bytes != 0) {
+        SRE_HIP_TRY(sre_launch_extract_gather(d_buf, sink->d_out, sc->d_rval, sc->d_fstart, nrows, res->out_bytes,
+                                              (uint32_t) sink->delim, (uint32_t) sink->delim, stream));
+    }
+    *pindex = sink->index_cap < res->nwritten ? sink->index_cap : res->nwritten;
+    return 0;
+hip_failed:
+    return -1;
+}
+
 /* The line filter: the line-mode call with a sink, then on the device the scan of the per-line
  * values to the offset table, the cut at out_cap, one read of four words, the gather and the index rows. */
 extern "C" SRE_API int
@@ -2700,33 +2796,18 @@ sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
     {
         return -1;
     }
-    /* (the sink's row rule is the filter's mode 0 whatever the flags are: the probe applies them) */
-    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
-    if (!sink_first_match(sc, "line lookup", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
-    sink.vgroups = &gr;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
-    sre_hip_lookup_info_t res;
-    memset(&res, 0, sizeof(res));
-    if (n != 0) {
-        static_assert(offsetof(sre_lines_info_t, knmembers) == offsetof(sre_lines_info_t, knkeyed) + sizeof(uint64_t),
-                      "knkeyed, knmembers are zeroed as one run");
-        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
-        SRE_HIP_TRY(sre_launch_keyset_probe(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen, ks->d_tab,
-                                            ks->nslots, ks->hash_mask, (flags & SRE_HIP_LINES_INVERT) != 0, sc->d_fval,
-                                            reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream));
-        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
-        if (sink_read(sc, &sink, n, &res, stream, LINFO(knkeyed), LINFO(knmembers)) != 0) return -1;
-        res.nkeyed = (size_t) sc->h_linfo->knkeyed;
-        res.nmembers = (size_t) sc->h_linfo->knmembers;
-        if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    uint64_t    n = 0;
+    if (keyed_call(sc, "line lookup", d_buf, len, delim, groups, ngroups, d_out, out_cap, d_index, index_cap, 0, 0, NULL, &sink, &gr, &n,
+                   stream) != 0)
+    {
+        return -1;
     }
-    if (info) *info = res;
-    return 0;
-hip_failed:
-    return -1;
+    return keyed_finish(sc, &sink, d_buf, n, info, stream, [&] {
+        return sre_launch_keyset_probe(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen, ks->d_tab,
+                                       ks->nslots, ks->hash_mask, (flags & SRE_HIP_LINES_INVERT) != 0, sc->d_fval,
+                                       reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream);
+    });
 }
 
 /* The line join: the lookup's call, key groups and host waits; in the probe's place the join pass, which
@@ -2754,36 +2835,19 @@ sre_hip_join_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
         if (vcols[x] < 0 || (size_t) vcols[x] >= ks->v) return -1;
         cols.col[x] = (uint8_t) vcols[x];
     }
-    /* (the sink's row rule is the filter's mode 0 whatever the flags are, so that the key table says which lines are keyed:
-     * the join pass applies the flags) */
-    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
-    if (!sink_first_match(sc, "line join", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
-    sink.vgroups = &gr;
-    sink.join = 1 + cols.n;
-    sink.fsep = jsep;
-    sink.d_dict = ks->d_rows;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
-    sre_hip_lookup_info_t res;
-    memset(&res, 0, sizeof(res));
-    if (n != 0) {
-        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
-        SRE_HIP_TRY(sre_launch_keyset_join(d_buf, sc->d_vval, sc->d_vstart, sc->d_ends, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen,
-                                           ks->d_vstart, ks->d_vlen, ks->v, ks->d_tab, ks->nslots, ks->hash_mask, &cols,
-                                           (flags & SRE_HIP_LINES_ALL) != 0, sc->d_fval, sc->d_fstart, sc->d_jkey,
-                                           reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream));
-        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
-        if (sink_read(sc, &sink, n, &res, stream, LINFO(knkeyed), LINFO(knmembers)) != 0) return -1;
-        res.nkeyed = (size_t) sc->h_linfo->knkeyed;
-        res.nmembers = (size_t) sc->h_linfo->knmembers;
-        if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    uint64_t    n = 0;
+    if (keyed_call(sc, "line join", d_buf, len, delim, groups, ngroups, d_out, out_cap, d_index, index_cap, 1 + cols.n, jsep, ks->d_rows,
+                   &sink, &gr, &n, stream) != 0)
+    {
+        return -1;
     }
-    if (info) *info = res;
-    return 0;
-hip_failed:
-    return -1;
+    return keyed_finish(sc, &sink, d_buf, n, info, stream, [&] {
+        return sre_launch_keyset_join(d_buf, sc->d_vval, sc->d_vstart, sc->d_ends, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen,
+                                      ks->d_vstart, ks->d_vlen, ks->v, ks->d_tab, ks->nslots, ks->hash_mask, &cols,
+                                      (flags & SRE_HIP_LINES_ALL) != 0, sc->d_fval, sc->d_fstart, sc->d_jkey,
+                                      reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream);
+    });
 }
 
 static int
@@ -2951,15 +3015,8 @@ sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
         if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
         if (n != 0) {
             const uint64_t nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nb * nwg;
-            /* (the scans' sums: over the counts first, then over at most n entries of the compact table) */
-            const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-            const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
-            if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
-            if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
-            if (sc->d_rres == NULL) {
-                SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
-                SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
-            }
+            uint64_t       nrows = 0;
+            if (compact_reserve(sc, n, nb) != 0) return -1;
             SRE_HIP_TRY(sre_launch_route_count(sc->d_fval, n, nb, sc->d_rcnt, stream));
             SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, ncnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
             /* the selected lines size the compact table */
@@ -2976,15 +3033,7 @@ sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
                 SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rval, nsel, sc->d_fblk, out_cap, sc->d_linfo, stream));
             }
             SRE_HIP_TRY(sre_launch_route_finish(sc->d_rcnt, n, nb, sc->d_rval, nsel, out_cap, sc->d_rres, stream));
-            SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, (SRE_LR_RES_WORDS + 2 * (size_t) nb) * sizeof(uint64_t),
-                                       hipMemcpyDeviceToHost, stream));
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
-            res.nlines = (size_t) n;
-            res.nselected = (size_t) sc->h_rres[SRE_LR_RES_NSEL];
-            res.need_bytes = (size_t) sc->h_rres[SRE_LR_RES_NEED];
-            res.nwritten = (size_t) sc->h_rres[SRE_LR_RES_WRITTEN];
-            res.out_bytes = (size_t) sc->h_rres[SRE_LR_RES_BYTES];
-            if (res.out_bytes > out_cap || res.nselected != nsel) return -1;     /* (cannot happen) */
+            if (compact_finish(sc, &sink, d_buf, n, SRE_LR_RES_WORDS + 2 * (size_t) nb, nsel, &res, &nrows, stream) != 0) return -1;
             if (buckets) {
                 size_t at = 0;
                 for (uint32_t b = 0; b < nb; b++) {
@@ -2994,13 +3043,7 @@ sre_hip_route_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int de
                     at += buckets[b].bytes;
                 }
             }
-            if (res.out_bytes != 0) {
-                /* the compact table is an entry table with one entry a line: the extract's gather, unchanged */
-                SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_fstart, nsel, res.out_bytes, (uint32_t) delim,
-                                                      (uint32_t) delim, stream));
-            }
-            if (res.nwritten != 0 && index_cap != 0) {
-                const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
+            if (nrows != 0) {
                 SRE_HIP_TRY(sre_launch_route_index(sc->d_rval, sc->d_fstart, sc->d_rmeta, sc->d_rres, nrows, index_cap, d_index,
                                                    stream));
             }
@@ -3041,18 +3084,18 @@ sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf, size_t len,
 {
     LinesSink            sink;
     sre_extract_groups_t gr;
-    if (ks == NULL || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1 || (keyid_cap != 0 && d_keyid == NULL)
-        || (buckets_cap != 0 && d_buckets == NULL))
+    if (ks == NULL || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1 || ngroups != ks->k
+        || (keyid_cap != 0 && d_keyid == NULL) || (buckets_cap != 0 && d_buckets == NULL))
     {
         return -1;
     }
-    /* (the sink's row rule is the filter's mode 0 whatever the flags are, as in the lookup: the sort key applies them) */
-    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap) || ngroups != ks->k) return -1;
-    if (!sink_first_match(sc, "line route by key", "captures") || !sink_groups(sc, groups, ngroups, &gr)) return -1;
-    sink.vgroups = &gr;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    uint64_t    n = 0;
+    if (keyed_call(sc, "line route by key", d_buf, len, delim, groups, ngroups, d_out, out_cap, d_index, index_cap, 0, 0, NULL, &sink,
+                   &gr, &n, stream) != 0)
+    {
+        return -1;
+    }
     sre_hip_route_key_info_t res;
     memset(&res, 0, sizeof(res));
     if (n > SRE_LRK_MAX_LINES) {
@@ -3064,17 +3107,9 @@ sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf, size_t len,
         const uint64_t rows = ks->rows;
         const uint32_t bits = route_key_digit_bits(), passes = sre_lrk_passes(sre_lrk_max_key(rows, all), bits);
         const uint64_t nd = (uint64_t) 1 << bits, nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nd * nwg;
-        /* (the scans' sums: over the counts of a pass, then over at most n entries of the compact table) */
-        const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-        const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
-        static_assert(SRE_LRK_RES_WORDS <= SRE_LR_RES_WORDS + 2 * SRE_LR_MAX_BUCKETS, "the result words fit the route's");
-        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
-        if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
+        uint64_t       nrows = 0;
+        if (compact_reserve(sc, n, nd) != 0) return -1;
         if (lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) return -1;
-        if (sc->d_rres == NULL) {
-            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
-            SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
-        }
         /* the lookup's probe, the ids of all lines into the scanner's array; the caller's are a copy */
         SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->knkeyed, 0, 2 * sizeof(uint64_t), stream));
         SRE_HIP_TRY(sre_launch_keyset_probe(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, ks->d_rows, ks->d_fstart, ks->d_flen, ks->d_tab,
@@ -3120,24 +3155,11 @@ sre_hip_route_lines_by_key(sre_hip_scanner_t *sc, const void *d_buf, size_t len,
             hoff = head;
         }
         SRE_HIP_TRY(sre_launch_route_key_finish(sc->d_rval, hoff, nsel, out_cap, sc->d_linfo, sc->d_rres, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, SRE_LRK_RES_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        res.nlines = (size_t) n;
+        if (compact_finish(sc, &sink, d_buf, n, SRE_LRK_RES_WORDS, nsel, &res, &nrows, stream) != 0) return -1;
         res.nkeyed = (size_t) sc->h_rres[SRE_LRK_RES_NKEYED];
         res.nmembers = (size_t) sc->h_rres[SRE_LRK_RES_NMEMBERS];
-        res.nselected = (size_t) sc->h_rres[SRE_LRK_RES_NSEL];
         res.nbuckets = (size_t) sc->h_rres[SRE_LRK_RES_NBUCKETS];
-        res.need_bytes = (size_t) sc->h_rres[SRE_LRK_RES_NEED];
-        res.nwritten = (size_t) sc->h_rres[SRE_LRK_RES_WRITTEN];
-        res.out_bytes = (size_t) sc->h_rres[SRE_LRK_RES_BYTES];
-        if (res.out_bytes > out_cap || res.nselected != nsel || res.nwritten > nsel) return -1;     /* (cannot happen) */
-        if (res.out_bytes != 0) {
-            /* the compact table is an entry table with one entry a line: the extract's gather, unchanged */
-            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_fstart, nsel, res.out_bytes, (uint32_t) delim,
-                                                  (uint32_t) delim, stream));
-        }
-        if (res.nwritten != 0 && index_cap != 0) {
-            const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
+        if (nrows != 0) {
             SRE_HIP_TRY(sre_launch_route_key_index(items, sc->d_fstart, sc->d_rval, sc->d_rres, rows, nrows,
                                                    index_cap, reinterpret_cast<int64_t *>(d_index), stream));
         }
@@ -3161,13 +3183,13 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     LinesSink            sink;
     sre_extract_groups_t gr;
     if ((flags & ~(SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC)) != 0) return -1;
-    /* (the sink's row rule is the filter's mode 0 whatever the flags are, as in the lookup: the sort key applies them) */
-    if (!sink_open(&sink, sc, d_buf, len, delim, 0, d_out, out_cap, d_index, index_cap)) return -1;
-    if (!sink_first_match(sc, "line sort", "captures") || !sink_groups(sc, &group, 1, &gr)) return -1;
-    sink.vgroups = &gr;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    uint64_t    n = 0;
+    if (keyed_call(sc, "line sort", d_buf, len, delim, &group, 1, d_out, out_cap, d_index, index_cap, 0, 0, NULL, &sink, &gr, &n,
+                   stream) != 0)
+    {
+        return -1;
+    }
     sre_hip_sort_info_t res;
     memset(&res, 0, sizeof(res));
     res.vmin = INT64_MAX;
@@ -3179,22 +3201,14 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     if (n != 0) {
         const int      all = (flags & SRE_HIP_LINES_ALL) != 0, desc = (flags & SRE_HIP_SORT_DESC) != 0;
         const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS, nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nd * nwg;
-        /* (the scans' sums: over the counts of a pass, then over at most n entries of the compact table) */
-        const uint64_t nblk = ((ncnt > n ? ncnt : n) + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
-        const size_t   nres = SRE_LR_RES_WORDS + 2 * (size_t) SRE_LR_MAX_BUCKETS;
-        static_assert(SRE_LSO_RES_WORDS <= SRE_LR_RES_WORDS + 2 * SRE_LR_MAX_BUCKETS, "the result words fit the route's");
+        uint64_t       nrows = 0;
         static_assert(offsetof(sre_lines_info_t, snumbered) == offsetof(sre_lines_info_t, skeyed) + sizeof(uint64_t)
                           && offsetof(sre_lines_info_t, svmin) == offsetof(sre_lines_info_t, skeyed) + 2 * sizeof(uint64_t)
                           && offsetof(sre_lines_info_t, svmax) == offsetof(sre_lines_info_t, skeyed) + 3 * sizeof(uint64_t),
                       "skeyed, snumbered, svmin, svmax are the four totals of the values pass, in that order");
-        if (lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0) return -1;
-        if (lines_grow(&sc->d_rcnt, &sc->rcnt_cap, (ncnt + 1) * sizeof(uint64_t)) != 0) return -1;
+        if (compact_reserve(sc, n, nd) != 0) return -1;
         if (lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) return -1;
         if (lines_grow(&sc->d_sclass, &sc->sclass_cap, n * sizeof(int8_t)) != 0) return -1;
-        if (sc->d_rres == NULL) {
-            SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_rres), nres * sizeof(uint64_t)));
-            SRE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sc->h_rres), nres * sizeof(uint64_t), 0));
-        }
         /* the value and the class of every line, and the totals: the one read that sizes everything behind it */
         SRE_HIP_TRY(sre_launch_sort_values(d_buf, sc->d_vval, sc->d_vstart, n, sc->d_jkey, sc->d_sclass, &sc->d_linfo->skeyed, stream));
         SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(skeyed), LINFO(snumbered), LINFO(svmin), LINFO(svmax)}));
@@ -3234,26 +3248,13 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
             SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rval, nout, sc->d_fblk, out_cap, sc->d_linfo, stream));
         }
         SRE_HIP_TRY(sre_launch_sort_finish(sc->d_rval, nout, out_cap, sc->d_rres, stream));
-        SRE_HIP_TRY(hipMemcpyAsync(sc->h_rres, sc->d_rres, SRE_LSO_RES_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        SRE_HIP_TRY(hipStreamSynchronize(stream));
-        res.nlines = (size_t) n;
+        if (compact_finish(sc, &sink, d_buf, n, SRE_LSO_RES_WORDS, nout, &res, &nrows, stream) != 0) return -1;
         res.nkeyed = (size_t) nkeyed;
         res.nnumbered = (size_t) nnum;
-        res.nselected = (size_t) sc->h_rres[SRE_LSO_RES_NSEL];
-        res.need_bytes = (size_t) sc->h_rres[SRE_LSO_RES_NEED];
-        res.nwritten = (size_t) sc->h_rres[SRE_LSO_RES_WRITTEN];
-        res.out_bytes = (size_t) sc->h_rres[SRE_LSO_RES_BYTES];
         res.passes = passes;
         res.vmin = vmin;
         res.vmax = vmax;
-        if (res.out_bytes > out_cap || res.nselected != nout || res.nwritten > nout) return -1;     /* (cannot happen) */
-        if (res.out_bytes != 0) {
-            /* the compact table is an entry table with one entry a line: the extract's gather, unchanged */
-            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_fstart, nout, res.out_bytes, (uint32_t) delim,
-                                                  (uint32_t) delim, stream));
-        }
-        if (res.nwritten != 0 && index_cap != 0) {
-            const uint64_t nrows = index_cap < res.nwritten ? index_cap : res.nwritten;
+        if (nrows != 0) {
             SRE_HIP_TRY(sre_launch_sort_index(lines, sc->d_fstart, sc->d_rval, sc->d_rres, sc->d_jkey, sc->d_sclass, n, nrows, index_cap,
                                               reinterpret_cast<int64_t *>(d_index), stream));
         }

@@ -1,7 +1,6 @@
 /*
- * sre_hip_lines_rank.h — the rank of an item inside its 64-lane slot, shared by the digit passes of the line route by key
- * (sre_hip_lines_route_key.hip) and of the line sort (sre_hip_lines_sort.hip); the rules are those of sre_lines_route_key.h.
- * Device code only.
+ * sre_hip_lines_rank.h — the rank of an item inside its 64-lane slot, for the partition pass (sre_hip_lines_partition.h) of
+ * the line route, the line route by key and the line sort; the rules are those of sre_lines_route_key.h.  Device code only.
  */
 #ifndef SRE_HIP_LINES_RANK_H
 #define SRE_HIP_LINES_RANK_H

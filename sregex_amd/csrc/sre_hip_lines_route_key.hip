@@ -4,10 +4,8 @@
  * items, into a compact table the extract's gather writes out.  The rules are those of sre_lines_route_key.h and
  * sre_lines_route.h, which the CPU model compiles too.
  *
- *   count      per pass: a workgroup takes 1024 items in order and writes how many have each digit to cnt[d * nwg + w];
- *              the filter's scan (sre_launch_filter_offsets) over those words gives every (digit, workgroup) its first rank;
- *   scatter    the same workgroups recompute the rank of every item and store it at that rank of the other array.  Pass 0
- *              makes the items from the key ids in line order and drops the unselected;
+ *   partition  per digit: the count and the scatter of sre_hip_lines_partition.h over one-word items, the filter's scan between
+ *              them.  Pass 0 makes the items from the key ids in line order and drops the unselected;
  *   table      a lane per rank of the sorted items: the entry of the compact table and the head flag;
  *   heads      behind the scan of the head flags: a lane per rank, a head leaves its rank at its bucket number;
  *   buckets    a lane per bucket: its row;
@@ -20,75 +18,33 @@
 #include <sregex/sregex.h>
 #include "sre_hip_lines.h"
 #include "sre_lines_route_key.h"
-#include "sre_hip_lines_block.h"
-#include "sre_hip_lines_rank.h"
+#include "sre_hip_lines_partition.h"
 
 namespace {
 
-/* item i of a pass: pass 0 (FIRST) makes it from the key id of line i, a later pass reads it */
-template <bool FIRST>
-__device__ inline uint64_t
-load_item(const int64_t *__restrict__ keyid, const uint64_t *__restrict__ src, uint64_t i, uint64_t n, uint64_t rows, int all)
-{
-    if (i >= n) return SRE_LRK_DROPPED;
-    return FIRST ? sre_lrk_first_item(keyid[i], i, rows, all) : src[i];
-}
-
-/* workgroup w: cnt[d * nwg + w] = its items of digit d */
-template <bool FIRST, int RULE>
-__global__ __launch_bounds__(SRE_LR_THREADS) void
-sre_k_route_key_count(const int64_t *__restrict__ keyid, const uint64_t *__restrict__ src, uint64_t n, uint64_t rows, int all,
-                      uint32_t pass, uint32_t bits, uint64_t nwg, uint64_t *__restrict__ cnt)
-{
-    __shared__ uint32_t c[SRE_LR_SLOTS << SRE_LRK_MAX_BITS];
-    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nd = 1u << bits;
-    for (uint32_t x = threadIdx.x; x < SRE_LR_SLOTS * nd; x += SRE_LR_THREADS) c[x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-        const uint32_t slot = sre_lr_slot(wave, q);
-        const uint64_t it = load_item<FIRST>(keyid, src, sre_lr_line(blockIdx.x, slot, lane), n, rows, all);
-        (void) slot_rank<RULE>(it != SRE_LRK_DROPPED, sre_lrk_digit(it, pass, bits), bits, lane, c + slot * nd);
+/* a digit pass (sre_hip_lines_partition.h): pass 0 (FIRST) makes item i from the key id of line i, a later pass reads it;
+ * every item goes to its rank of dst */
+template <bool FIRST, int RANK_RULE>
+struct KeyPass {
+    static constexpr uint32_t MAX_DIGITS = 1u << SRE_LRK_MAX_BITS;
+    static constexpr int      RULE = RANK_RULE;
+    const int64_t *__restrict__ keyid;
+    const uint64_t *__restrict__ src;
+    uint64_t n, rows;
+    int      all;
+    uint32_t pass, width;
+    uint64_t *__restrict__ dst;
+    __device__ uint32_t nd() const { return 1u << width; }
+    __device__ uint32_t bits() const { return width; }
+    __device__ uint64_t load(uint64_t i) const
+    {
+        if (i >= n) return SRE_LRK_DROPPED;
+        return FIRST ? sre_lrk_first_item(keyid[i], i, rows, all) : src[i];
     }
-    __syncthreads();
-    if (threadIdx.x < nd) cnt[sre_lr_cnt_index(threadIdx.x, nwg, blockIdx.x)] = sre_lr_slot_prefix(c + threadIdx.x, nd);
-}
-
-/* the same workgroups over the scanned counts `first`: every item goes to its rank of dst (total items) */
-template <bool FIRST, int RULE>
-__global__ __launch_bounds__(SRE_LR_THREADS) void
-sre_k_route_key_scatter(const int64_t *__restrict__ keyid, const uint64_t *__restrict__ src, uint64_t n, uint64_t rows, int all,
-                        uint32_t pass, uint32_t bits, uint64_t nwg, const uint64_t *__restrict__ first, uint64_t total,
-                        uint64_t *__restrict__ dst)
-{
-    __shared__ uint32_t c[SRE_LR_SLOTS << SRE_LRK_MAX_BITS];
-    __shared__ uint64_t gbase[1u << SRE_LRK_MAX_BITS];
-    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nd = 1u << bits;
-    uint64_t            it[SRE_LR_ROUNDS];
-    uint32_t            rk[SRE_LR_ROUNDS];
-    for (uint32_t x = threadIdx.x; x < SRE_LR_SLOTS * nd; x += SRE_LR_THREADS) c[x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-        const uint32_t slot = sre_lr_slot(wave, q);
-        it[q] = load_item<FIRST>(keyid, src, sre_lr_line(blockIdx.x, slot, lane), n, rows, all);
-        rk[q] = slot_rank<RULE>(it[q] != SRE_LRK_DROPPED, sre_lrk_digit(it[q], pass, bits), bits, lane, c + slot * nd);
-    }
-    __syncthreads();
-    if (threadIdx.x < nd) {
-        (void) sre_lr_slot_prefix(c + threadIdx.x, nd);
-        gbase[threadIdx.x] = first[sre_lr_cnt_index(threadIdx.x, nwg, blockIdx.x)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-        if (it[q] == SRE_LRK_DROPPED) continue;
-        const uint32_t d = sre_lrk_digit(it[q], pass, bits);
-        const uint64_t r = gbase[d] + c[sre_lr_slot(wave, q) * nd + d] + rk[q];
-        if (r >= total) continue;       /* (cannot happen: the ranks are a permutation of 0 .. total - 1) */
-        dst[r] = it[q];
-    }
-}
+    __device__ bool     taken(uint64_t it) const { return it != SRE_LRK_DROPPED; }
+    __device__ uint32_t digit(uint64_t it) const { return sre_lrk_digit(it, pass, width); }
+    __device__ void     store(uint64_t r, uint64_t it, uint64_t) const { dst[r] = it; }
+};
 
 /* a lane per rank of the sorted items: its entry of the compact table, and head[r] = 1 for the first rank of a bucket */
 __global__ __launch_bounds__(256) void
@@ -99,13 +55,7 @@ sre_k_route_key_table(const uint64_t *__restrict__ items, const uint64_t *__rest
     if (r >= nsel) return;
     const uint64_t i = sre_lrk_item_line(items[r]);
     head[r] = sre_lrk_is_head(items, r) ? 1 : 0;
-    if (i >= nlines) {                  /* (cannot happen: an item carries the number of its line) */
-        cstart[r] = sre_lr_entry_start(0);
-        cval[r] = 1;
-        return;
-    }
-    const uint64_t st = line_start(ends, i);
-    sre_lrk_entry(st, ends[i] - st, cstart + r, cval + r);
+    compact_entry(ends, i, nlines, r, cstart, cval);
 }
 
 /* behind the scan of head[] to hoff[0 .. nsel]: hrank[b] = the rank of bucket b's head, hrank[nbuckets] = nsel */
@@ -141,11 +91,7 @@ sre_k_route_key_finish(const uint64_t *__restrict__ coff, const uint64_t *__rest
                        const sre_lines_info_t *__restrict__ info, uint64_t *__restrict__ res)
 {
     if (threadIdx.x != 0) return;
-    const uint64_t cut = nsel ? sre_lr_cut(coff, nsel, out_cap) : 0;
-    res[SRE_LRK_RES_NSEL] = nsel;
-    res[SRE_LRK_RES_NEED] = nsel ? coff[nsel] : 0;
-    res[SRE_LRK_RES_WRITTEN] = cut;
-    res[SRE_LRK_RES_BYTES] = nsel ? coff[cut] : 0;
+    sre_lr_result(coff, nsel, out_cap, res);
     res[SRE_LRK_RES_NBUCKETS] = nsel ? hoff[nsel] : 0;
     res[SRE_LRK_RES_NKEYED] = info->knkeyed;
     res[SRE_LRK_RES_NMEMBERS] = info->knmembers;
@@ -163,33 +109,38 @@ sre_k_route_key_index(const uint64_t *__restrict__ items, const uint64_t *__rest
     sre_lrk_index_row(items, cstart, coff, r, rows, out + r * 5);
 }
 
-template <bool FIRST>
+/* the count or the scatter of one pass */
+template <bool FIRST, int RULE>
+hipError_t
+launch_pass(bool scatter, const int64_t *d_keyid, const uint64_t *d_src, uint64_t n, uint64_t rows, int all, uint32_t pass, uint32_t bits,
+            uint64_t *d_cnt, const uint64_t *d_first, uint64_t total, uint64_t *d_dst, hipStream_t stream)
+{
+    typedef KeyPass<FIRST, RULE> Pass;
+    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
+    if (n == 0 || bits < 1 || bits > SRE_LRK_MAX_BITS || pass * bits >= SRE_LRK_LINE_BITS || nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t) nwg), block(SRE_LR_THREADS);
+    const Pass p = {d_keyid, d_src, n, rows, all, pass, bits, d_dst};
+    if (!scatter) {
+        hipLaunchKernelGGL(sre_k_partition_count<Pass>, grid, block, 0, stream, p, nwg, d_cnt);
+    } else {
+        if (total == 0) return hipSuccess;
+        hipLaunchKernelGGL(sre_k_partition_scatter<Pass>, grid, block, 0, stream, p, nwg, d_first, total);
+    }
+    return hipGetLastError();
+}
+
+/* ... with the pass type the arguments name: pass 0 over the key ids when d_keyid != NULL, and the rank rule */
 hipError_t
 launch_pass(bool scatter, int rule, const int64_t *d_keyid, const uint64_t *d_src, uint64_t n, uint64_t rows, int all, uint32_t pass,
             uint32_t bits, uint64_t *d_cnt, const uint64_t *d_first, uint64_t total, uint64_t *d_dst, hipStream_t stream)
 {
-    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
-    if (n == 0 || bits < 1 || bits > SRE_LRK_MAX_BITS || pass * bits >= SRE_LRK_LINE_BITS || nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((uint32_t) nwg), block(SRE_LR_THREADS);
-    if (!scatter) {
-        if (rule == SRE_LRK_RANK_TURNS) {
-            hipLaunchKernelGGL((sre_k_route_key_count<FIRST, SRE_LRK_RANK_TURNS>), grid, block, 0, stream, d_keyid, d_src, n, rows, all,
-                               pass, bits, nwg, d_cnt);
-        } else {
-            hipLaunchKernelGGL((sre_k_route_key_count<FIRST, SRE_LRK_RANK_BITS>), grid, block, 0, stream, d_keyid, d_src, n, rows, all,
-                               pass, bits, nwg, d_cnt);
-        }
-    } else {
-        if (total == 0) return hipSuccess;
-        if (rule == SRE_LRK_RANK_TURNS) {
-            hipLaunchKernelGGL((sre_k_route_key_scatter<FIRST, SRE_LRK_RANK_TURNS>), grid, block, 0, stream, d_keyid, d_src, n, rows, all,
-                               pass, bits, nwg, d_first, total, d_dst);
-        } else {
-            hipLaunchKernelGGL((sre_k_route_key_scatter<FIRST, SRE_LRK_RANK_BITS>), grid, block, 0, stream, d_keyid, d_src, n, rows, all,
-                               pass, bits, nwg, d_first, total, d_dst);
-        }
+    const bool turns = rule == SRE_LRK_RANK_TURNS;
+    if (d_keyid) {
+        return (turns ? launch_pass<true, SRE_LRK_RANK_TURNS> : launch_pass<true, SRE_LRK_RANK_BITS>)(
+            scatter, d_keyid, NULL, n, rows, all, 0, bits, d_cnt, d_first, total, d_dst, stream);
     }
-    return hipGetLastError();
+    return (turns ? launch_pass<false, SRE_LRK_RANK_TURNS> : launch_pass<false, SRE_LRK_RANK_BITS>)(
+        scatter, NULL, d_src, n, rows, all, pass, bits, d_cnt, d_first, total, d_dst, stream);
 }
 
 }  // namespace
@@ -198,16 +149,14 @@ extern "C" hipError_t
 sre_launch_route_key_count(const int64_t *d_keyid, const uint64_t *d_src, uint64_t n, uint64_t rows, int all, uint32_t pass,
                            uint32_t bits, int rule, uint64_t *d_cnt, hipStream_t stream)
 {
-    return d_keyid ? launch_pass<true>(false, rule, d_keyid, NULL, n, rows, all, 0, bits, d_cnt, NULL, 0, NULL, stream)
-                   : launch_pass<false>(false, rule, NULL, d_src, n, rows, all, pass, bits, d_cnt, NULL, 0, NULL, stream);
+    return launch_pass(false, rule, d_keyid, d_src, n, rows, all, pass, bits, d_cnt, NULL, 0, NULL, stream);
 }
 
 extern "C" hipError_t
 sre_launch_route_key_scatter(const int64_t *d_keyid, const uint64_t *d_src, uint64_t n, uint64_t rows, int all, uint32_t pass,
                              uint32_t bits, int rule, const uint64_t *d_first, uint64_t total, uint64_t *d_dst, hipStream_t stream)
 {
-    return d_keyid ? launch_pass<true>(true, rule, d_keyid, NULL, n, rows, all, 0, bits, NULL, d_first, total, d_dst, stream)
-                   : launch_pass<false>(true, rule, NULL, d_src, n, rows, all, pass, bits, NULL, d_first, total, d_dst, stream);
+    return launch_pass(true, rule, d_keyid, d_src, n, rows, all, pass, bits, NULL, d_first, total, d_dst, stream);
 }
 
 extern "C" hipError_t

@@ -6,10 +6,9 @@
  *
  *   values     a lane per line: the class and the value of the line from its entry of the value table, and the four totals
  *              of the call: at most one add per count, one minimum and one maximum per workgroup of 1024 lines;
- *   count      per pass: a workgroup takes 1024 keys in order and writes how many have each digit to cnt[d * nwg + w];
- *              the filter's scan (sre_launch_filter_offsets) over those words gives every (digit, workgroup) its first rank;
- *   scatter    the same workgroups recompute the rank of every item and store its key and its line at that rank of the
- *              other pair of arrays.  Pass 0 makes the items from the values in line order and drops the unselected;
+ *   partition  per digit: the count and the scatter of sre_hip_lines_partition.h, the filter's scan between them; key and line
+ *              of an item go to the same rank of the other pair of arrays.  Pass 0 makes the items from the values in line
+ *              order and drops the unselected;
  *   table      a lane per rank in front of the limit: the entry of the compact table;
  *   finish     one lane: the cut at out_cap and the words the host reads;
  *   gather     sre_launch_extract_gather over the compact table, unchanged (sre_hip_lines_gather.hip);
@@ -20,8 +19,7 @@
 #include <sregex/sregex.h>
 #include "sre_hip_lines.h"
 #include "sre_lines_sort.h"
-#include "sre_hip_lines_block.h"
-#include "sre_hip_lines_rank.h"
+#include "sre_hip_lines_partition.h"
 
 #define LSO_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
@@ -106,76 +104,37 @@ struct SortKeys {
     int      desc, all;
 };
 
-/* key i of a pass: pass 0 (FIRST) makes it from the value and the class of line i, a later pass reads it */
+/* a digit pass (sre_hip_lines_partition.h) over the keys, 8-bit digits and the ballots per digit bit: pass 0 (FIRST) makes key i
+ * from the value and the class of line i, a later pass reads it; key and line of every item go to its rank of dkey / dline.
+ * Pass 0: the line of item i is i; a later pass reads it from sline */
 template <bool FIRST>
-__device__ inline uint64_t
-load_key(const int64_t *__restrict__ value, const int8_t *__restrict__ cls, const uint64_t *__restrict__ src, uint64_t i, uint64_t n,
-         const SortKeys &k)
-{
-    if (i >= n) return SRE_LSO_DROPPED;
-    return FIRST ? sre_lso_key(cls[i], value[i], k.vmin, k.vmax, k.range, k.desc, k.all) : src[i];
-}
-
-/* workgroup w: cnt[d * nwg + w] = its items of digit d */
-template <bool FIRST>
-__global__ __launch_bounds__(SRE_LR_THREADS) void
-sre_k_sort_count(const int64_t *__restrict__ value, const int8_t *__restrict__ cls, const uint64_t *__restrict__ src, uint64_t n,
-                 SortKeys k, uint32_t pass, uint64_t nwg, uint64_t *__restrict__ cnt)
-{
-    __shared__ uint32_t c[SRE_LR_SLOTS << SRE_LSO_DIGIT_BITS];
-    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nd = 1u << SRE_LSO_DIGIT_BITS;
-    for (uint32_t x = threadIdx.x; x < SRE_LR_SLOTS * nd; x += SRE_LR_THREADS) c[x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-        const uint32_t slot = sre_lr_slot(wave, q);
-        const uint64_t key = load_key<FIRST>(value, cls, src, sre_lr_line(blockIdx.x, slot, lane), n, k);
-        (void) slot_rank<SRE_LRK_RANK_BITS>(key != SRE_LSO_DROPPED, sre_lso_digit(key, pass), SRE_LSO_DIGIT_BITS, lane, c + slot * nd);
+struct SortPass {
+    static constexpr uint32_t MAX_DIGITS = 1u << SRE_LSO_DIGIT_BITS;
+    static constexpr int      RULE = SRE_LRK_RANK_BITS;
+    const int64_t *__restrict__ value;
+    const int8_t *__restrict__ cls;
+    const uint64_t *__restrict__ src;
+    const uint32_t *__restrict__ sline;
+    uint64_t n;
+    SortKeys k;
+    uint32_t pass;
+    uint64_t *__restrict__ dkey;
+    uint32_t *__restrict__ dline;
+    __device__ uint32_t nd() const { return MAX_DIGITS; }
+    __device__ uint32_t bits() const { return SRE_LSO_DIGIT_BITS; }
+    __device__ uint64_t load(uint64_t i) const
+    {
+        if (i >= n) return SRE_LSO_DROPPED;
+        return FIRST ? sre_lso_key(cls[i], value[i], k.vmin, k.vmax, k.range, k.desc, k.all) : src[i];
     }
-    __syncthreads();
-    if (threadIdx.x < nd) cnt[sre_lr_cnt_index(threadIdx.x, nwg, blockIdx.x)] = sre_lr_slot_prefix(c + threadIdx.x, nd);
-}
-
-/* the same workgroups over the scanned counts `first`: key and line of every item go to its rank of dkey / dline (total
- * items).  Pass 0: the line of item i is i; a later pass reads it from sline */
-template <bool FIRST>
-__global__ __launch_bounds__(SRE_LR_THREADS) void
-sre_k_sort_scatter(const int64_t *__restrict__ value, const int8_t *__restrict__ cls, const uint64_t *__restrict__ src,
-                   const uint32_t *__restrict__ sline, uint64_t n, SortKeys k, uint32_t pass, uint64_t nwg,
-                   const uint64_t *__restrict__ first, uint64_t total, uint64_t *__restrict__ dkey, uint32_t *__restrict__ dline)
-{
-    __shared__ uint32_t c[SRE_LR_SLOTS << SRE_LSO_DIGIT_BITS];
-    __shared__ uint64_t gbase[1u << SRE_LSO_DIGIT_BITS];
-    const uint32_t      lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nd = 1u << SRE_LSO_DIGIT_BITS;
-    uint64_t            key[SRE_LR_ROUNDS];
-    uint32_t            rk[SRE_LR_ROUNDS];
-    for (uint32_t x = threadIdx.x; x < SRE_LR_SLOTS * nd; x += SRE_LR_THREADS) c[x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-        const uint32_t slot = sre_lr_slot(wave, q);
-        key[q] = load_key<FIRST>(value, cls, src, sre_lr_line(blockIdx.x, slot, lane), n, k);
-        rk[q] = slot_rank<SRE_LRK_RANK_BITS>(key[q] != SRE_LSO_DROPPED, sre_lso_digit(key[q], pass), SRE_LSO_DIGIT_BITS, lane,
-                                             c + slot * nd);
-    }
-    __syncthreads();
-    if (threadIdx.x < nd) {
-        (void) sre_lr_slot_prefix(c + threadIdx.x, nd);
-        gbase[threadIdx.x] = first[sre_lr_cnt_index(threadIdx.x, nwg, blockIdx.x)];
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-        if (key[q] == SRE_LSO_DROPPED) continue;
-        const uint32_t slot = sre_lr_slot(wave, q);
-        const uint64_t i = sre_lr_line(blockIdx.x, slot, lane);
-        const uint32_t d = sre_lso_digit(key[q], pass);
-        const uint64_t r = gbase[d] + c[slot * nd + d] + rk[q];
-        if (r >= total) continue;       /* (cannot happen: the ranks are a permutation of 0 .. total - 1) */
-        dkey[r] = key[q];
+    __device__ bool     taken(uint64_t key) const { return key != SRE_LSO_DROPPED; }
+    __device__ uint32_t digit(uint64_t key) const { return sre_lso_digit(key, pass); }
+    __device__ void     store(uint64_t r, uint64_t key, uint64_t i) const
+    {
+        dkey[r] = key;
         dline[r] = FIRST ? (uint32_t) i : sline[i];
     }
-}
+};
 
 /* a lane per rank in front of nout: its entry of the compact table */
 __global__ __launch_bounds__(256) void
@@ -184,14 +143,7 @@ sre_k_sort_table(const uint32_t *__restrict__ lines, const uint64_t *__restrict_
 {
     const uint64_t r = (uint64_t) blockIdx.x * 256u + threadIdx.x;
     if (r >= nout) return;
-    const uint64_t i = lines[r];
-    if (i >= nlines) {                  /* (cannot happen: an item carries the number of its line) */
-        cstart[r] = sre_lr_entry_start(0);
-        cval[r] = 1;
-        return;
-    }
-    const uint64_t st = line_start(ends, i);
-    sre_lrk_entry(st, ends[i] - st, cstart + r, cval + r);
+    compact_entry(ends, lines[r], nlines, r, cstart, cval);
 }
 
 /* one lane: the cut and the words the host reads.  coff is not read when nout == 0 */
@@ -199,7 +151,7 @@ __global__ __launch_bounds__(64) void
 sre_k_sort_finish(const uint64_t *__restrict__ coff, uint64_t nout, uint64_t out_cap, uint64_t *__restrict__ res)
 {
     if (threadIdx.x != 0) return;
-    sre_lso_result(coff, nout, out_cap, res);
+    sre_lr_result(coff, nout, out_cap, res);
 }
 
 /* rows [line, start, len, output offset, value, class] of the first min(index_cap, written) ranks */
@@ -253,10 +205,11 @@ sre_launch_sort_count(const int64_t *d_value, const int8_t *d_class, const uint6
     const dim3     grid((uint32_t) nwg), block(SRE_LR_THREADS);
     if (d_value) {
         if (pass != 0 || d_class == NULL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(sre_k_sort_count<true>, grid, block, 0, stream, d_value, d_class, (const uint64_t *) NULL, n, k, 0u, nwg, d_cnt);
+        const SortPass<true> p = {d_value, d_class, NULL, NULL, n, k, 0u, NULL, NULL};
+        hipLaunchKernelGGL(sre_k_partition_count<SortPass<true>>, grid, block, 0, stream, p, nwg, d_cnt);
     } else {
-        hipLaunchKernelGGL(sre_k_sort_count<false>, grid, block, 0, stream, (const int64_t *) NULL, (const int8_t *) NULL, d_src, n, k,
-                           pass, nwg, d_cnt);
+        const SortPass<false> p = {NULL, NULL, d_src, NULL, n, k, pass, NULL, NULL};
+        hipLaunchKernelGGL(sre_k_partition_count<SortPass<false>>, grid, block, 0, stream, p, nwg, d_cnt);
     }
     return hipGetLastError();
 }
@@ -273,12 +226,12 @@ sre_launch_sort_scatter(const int64_t *d_value, const int8_t *d_class, const uin
     const dim3     grid((uint32_t) nwg), block(SRE_LR_THREADS);
     if (d_value) {
         if (pass != 0 || d_class == NULL) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(sre_k_sort_scatter<true>, grid, block, 0, stream, d_value, d_class, (const uint64_t *) NULL,
-                           (const uint32_t *) NULL, n, k, 0u, nwg, d_first, total, d_dkey, d_dline);
+        const SortPass<true> p = {d_value, d_class, NULL, NULL, n, k, 0u, d_dkey, d_dline};
+        hipLaunchKernelGGL(sre_k_partition_scatter<SortPass<true>>, grid, block, 0, stream, p, nwg, d_first, total);
     } else {
         if (total != n) return hipErrorInvalidValue;       /* (a later pass moves every item) */
-        hipLaunchKernelGGL(sre_k_sort_scatter<false>, grid, block, 0, stream, (const int64_t *) NULL, (const int8_t *) NULL, d_src,
-                           d_sline, n, k, pass, nwg, d_first, total, d_dkey, d_dline);
+        const SortPass<false> p = {NULL, NULL, d_src, d_sline, n, k, pass, d_dkey, d_dline};
+        hipLaunchKernelGGL(sre_k_partition_scatter<SortPass<false>>, grid, block, 0, stream, p, nwg, d_first, total);
     }
     return hipGetLastError();
 }

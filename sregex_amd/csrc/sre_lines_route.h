@@ -40,7 +40,7 @@
 #define SRE_LR_KEY_SHIFT    56u
 #define SRE_LR_KEY_LEN      ((1ull << SRE_LR_KEY_SHIFT) - 1)
 
-/* words the finish pass leaves for the host in front of the 2 * nbuckets per-bucket words [nlines, bytes] */
+/* words the finish pass leaves for the host (sre_lr_result) in front of the 2 * nbuckets per-bucket words [nlines, bytes] */
 #define SRE_LR_RES_NSEL     0u
 #define SRE_LR_RES_NEED     1u
 #define SRE_LR_RES_WRITTEN  2u
@@ -127,6 +127,19 @@ SRE_LG_FN uint64_t
 sre_lr_cut(const uint64_t *coff, uint64_t nsel, uint64_t out_cap)
 {
     return sre_lg_row_cut(coff, nsel, 1, out_cap);
+}
+
+/* the first SRE_LR_RES_WORDS result words of every call with a compact table (the route, the route by key, the sort), from
+ * the scanned table coff[0 .. nrows] (not read when nrows == 0): the rows, their bytes, the rows that fit out_cap whole and
+ * the bytes of those */
+SRE_LG_FN void
+sre_lr_result(const uint64_t *coff, uint64_t nrows, uint64_t out_cap, uint64_t *res)
+{
+    const uint64_t cut = nrows ? sre_lr_cut(coff, nrows, out_cap) : 0;
+    res[SRE_LR_RES_NSEL] = nrows;
+    res[SRE_LR_RES_NEED] = nrows ? coff[nrows] : 0;
+    res[SRE_LR_RES_WRITTEN] = cut;
+    res[SRE_LR_RES_BYTES] = nrows ? coff[cut] : 0;
 }
 
 #endif

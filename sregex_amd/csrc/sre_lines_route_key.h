@@ -45,15 +45,15 @@
 #define SRE_LRK_RANK_BITS   0
 #define SRE_LRK_RANK_TURNS  1
 
-/* the words the finish pass leaves for the host */
-#define SRE_LRK_RES_NSEL     0u
-#define SRE_LRK_RES_NEED     1u
-#define SRE_LRK_RES_WRITTEN  2u
-#define SRE_LRK_RES_BYTES    3u
-#define SRE_LRK_RES_NBUCKETS 4u
-#define SRE_LRK_RES_NKEYED   5u
-#define SRE_LRK_RES_NMEMBERS 6u
-#define SRE_LRK_RES_WORDS    7u
+/* the words the finish pass leaves for the host: the route's four (sre_lr_result) and three of its own */
+#define SRE_LRK_RES_NSEL     SRE_LR_RES_NSEL
+#define SRE_LRK_RES_NEED     SRE_LR_RES_NEED
+#define SRE_LRK_RES_WRITTEN  SRE_LR_RES_WRITTEN
+#define SRE_LRK_RES_BYTES    SRE_LR_RES_BYTES
+#define SRE_LRK_RES_NBUCKETS (SRE_LR_RES_WORDS + 0u)
+#define SRE_LRK_RES_NKEYED   (SRE_LR_RES_WORDS + 1u)
+#define SRE_LRK_RES_NMEMBERS (SRE_LR_RES_WORDS + 2u)
+#define SRE_LRK_RES_WORDS    (SRE_LR_RES_WORDS + 3u)
 
 /* the sort key of a line with key id `id` against a set of `rows` rows; -1 drops the line */
 SRE_LG_FN int64_t

@@ -1,11 +1,10 @@
 /*
  * sre_lines_sort.h — the rules of the line sort (sre_hip_sort_lines): the value and the class of a line
  * from its entry of the value table, what a workgroup of the values pass sends to the four words of the call, the sort key
- * of a line from its value, the largest key and the number of passes, the digit a pass looks at, the entry of the compact
- * table, the result words and the index row.  The kernels (sre_hip_lines_sort.hip), the host code of the batched API and the
+ * of a line from its value, the largest key and the number of passes, the digit a pass looks at and the index row.  The kernels (sre_hip_lines_sort.hip), the host code of the batched API and the
  * CPU model (tests/lines_sort_sim.cpp) compile this text; nothing here touches memory except through its arguments.  The
- * number rule is the tally's (sre_ls_number, sre_lines_sums.h); the slot geometry, the slot prefix, the count index and the
- * cut are the route's (sre_lines_route.h); the pass formula, the rank rule of a slot and the entry of the compact table are
+ * number rule is the tally's (sre_ls_number, sre_lines_sums.h); the slot geometry, the slot prefix, the count index, the
+ * cut and the result words are the route's (sre_lines_route.h); the pass formula, the rank rule of a slot and the entry of the compact table are
  * the route by key's (sre_lines_route_key.h).
  *
  * The CLASS of a line, from entry `line` of the value table of the ONE sort group (sre_lines_sums.h, V = 1):
@@ -56,12 +55,12 @@
 
 #define SRE_LSO_INDEX_WORDS 6u
 
-/* the words the finish pass leaves for the host */
-#define SRE_LSO_RES_NSEL     0u
-#define SRE_LSO_RES_NEED     1u
-#define SRE_LSO_RES_WRITTEN  2u
-#define SRE_LSO_RES_BYTES    3u
-#define SRE_LSO_RES_WORDS    4u
+/* the words the finish pass leaves for the host: the route's four (sre_lr_result) */
+#define SRE_LSO_RES_NSEL     SRE_LR_RES_NSEL
+#define SRE_LSO_RES_NEED     SRE_LR_RES_NEED
+#define SRE_LSO_RES_WRITTEN  SRE_LR_RES_WRITTEN
+#define SRE_LSO_RES_BYTES    SRE_LR_RES_BYTES
+#define SRE_LSO_RES_WORDS    SRE_LR_RES_WORDS
 
 /* the four totals of a call, or of a part of it */
 typedef struct {
@@ -176,15 +175,12 @@ sre_lso_digit(uint64_t key, uint32_t pass)
 /* the rows of the full output */
 SRE_LG_FN uint64_t sre_lso_limited(uint64_t nsel, uint64_t limit) { return limit != 0 && limit < nsel ? limit : nsel; }
 
-/* the result words from the scanned table coff[0 .. nout] (not read when nout == 0) */
+/* the result words from the scanned table coff[0 .. nout] (not read when nout == 0): the route's rule under the sort's name,
+ * which code compiled against this header may call */
 SRE_LG_FN void
 sre_lso_result(const uint64_t *coff, uint64_t nout, uint64_t out_cap, uint64_t *res)
 {
-    const uint64_t cut = nout ? sre_lr_cut(coff, nout, out_cap) : 0;
-    res[SRE_LSO_RES_NSEL] = nout;
-    res[SRE_LSO_RES_NEED] = nout ? coff[nout] : 0;
-    res[SRE_LSO_RES_WRITTEN] = cut;
-    res[SRE_LSO_RES_BYTES] = nout ? coff[cut] : 0;
+    sre_lr_result(coff, nout, out_cap, res);
 }
 
 /* the index row of rank r, whose line is `line` with value and class as the values pass left them */

@@ -1,86 +1,43 @@
 /*
- * lines_route_key_sim.cpp — the partition of the line route by key on the CPU: count, scan and scatter of every digit pass
- * run workgroup by workgroup, slot by slot and lane by lane with the rules the kernels compile
- * (sregex_amd/csrc/sre_lines_route_key.h and sre_lines_route.h): the sort key, the item, the digit, the two rank rules of a
- * slot on ballots, the slot prefix and the global rank; then the compact table, the head flags, the head ranks, the bucket
+ * lines_route_key_sim.cpp — the partition of the line route by key on the CPU: every digit pass through the partition model
+ * (lines_partition_sim.h) with the rules the kernels compile (sregex_amd/csrc/sre_lines_route_key.h and sre_lines_route.h):
+ * the sort key, the item, the digit and either rank rule of a slot; then the compact table, the head flags, the head ranks, the bucket
  * rows, the cut and the index rows.  Every store is counted, so tests/test_lines_route_key_model.py can assert that every
  * word of every array is written exactly once per pass.  The gather over the table is the extract's model
  * (tests/lines_extract_sim.cpp), unchanged.
  */
-#include "sre_lines_route_key.h"
-#include <stdint.h>
+#include "lines_partition_sim.h"
 #include <string.h>
-#include <vector>
 
 namespace {
 
-/* one slot of 64 lanes in lockstep: what slot_rank of sre_hip_lines_route_key.hip does with __ballot / __shfl */
-struct SimSlot {
-    bool     sel[64];
-    uint32_t digit[64];
-    uint32_t rank[64];
-
-    template <class Pred> uint64_t ballot(Pred pred) const
+/* a digit pass (KeyPass of sre_hip_lines_route_key.hip; keyid != NULL: pass 0 over the lines); writes[r] counts the stores
+ * to dst[r] */
+struct SimKeyPass {
+    const int64_t  *keyid;
+    const uint64_t *src;
+    uint64_t        n, rows;
+    int             all;
+    uint32_t        pass, width;
+    int             rank_rule;
+    uint64_t       *dst;
+    uint32_t       *writes;
+    uint32_t nd() const { return 1u << width; }
+    uint32_t bits() const { return width; }
+    int      rule() const { return rank_rule; }
+    uint64_t load(uint64_t i) const
     {
-        uint64_t m = 0;
-        for (uint32_t x = 0; x < 64; x++) m |= (uint64_t) (pred(x) ? 1 : 0) << x;
-        return m;
+        if (i >= n) return SRE_LRK_DROPPED;
+        return keyid ? sre_lrk_first_item(keyid[i], i, rows, all) : src[i];
     }
-
-    /* returns the ballots taken behind the first */
-    uint32_t run(int rule, uint32_t bits, uint32_t *c)
+    bool     taken(uint64_t it) const { return it != SRE_LRK_DROPPED; }
+    uint32_t digit(uint64_t it) const { return sre_lrk_digit(it, pass, width); }
+    void     store(uint64_t r, uint64_t it, uint64_t)
     {
-        uint32_t ballots = 0;
-        for (uint32_t x = 0; x < 64; x++) rank[x] = 0;
-        if (rule == SRE_LRK_RANK_TURNS) {
-            uint64_t rem = ballot([&](uint32_t x) { return sel[x]; });
-            while (rem) {
-                const uint32_t lead = sre_lr_leader(rem);
-                const uint32_t kd = digit[lead];
-                const uint64_t m = ballot([&](uint32_t x) { return sel[x] && digit[x] == kd; });
-                for (uint32_t x = 0; x < 64; x++) {
-                    if (sel[x] && digit[x] == kd) rank[x] = sre_lr_rank_in(m, x);
-                }
-                c[kd] = sre_lr_popc(m);
-                rem &= ~m;
-                ballots++;
-            }
-            return ballots;
-        }
-        uint64_t m[64];
-        const uint64_t all = ballot([&](uint32_t x) { return sel[x]; });
-        for (uint32_t x = 0; x < 64; x++) m[x] = all;
-        for (uint32_t bit = 0; bit < bits; bit++) {
-            const uint64_t with_bit = ballot([&](uint32_t x) { return sel[x] && ((digit[x] >> bit) & 1u); });
-            for (uint32_t x = 0; x < 64; x++) m[x] = sre_lrk_agree(m[x], with_bit, digit[x], bit);
-            ballots++;
-        }
-        for (uint32_t x = 0; x < 64; x++) {
-            const uint32_t r = sre_lr_rank_in(m[x], x);
-            if (sel[x] && r == 0) c[digit[x]] = sre_lr_popc(m[x]);
-            rank[x] = sel[x] ? r : 0;
-        }
-        return ballots;
+        dst[r] = it;
+        writes[r]++;
     }
 };
-
-uint64_t
-load_item(const int64_t *keyid, const uint64_t *src, uint64_t i, uint64_t n, uint64_t rows, int all)
-{
-    if (i >= n) return SRE_LRK_DROPPED;
-    return keyid ? sre_lrk_first_item(keyid[i], i, rows, all) : src[i];
-}
-
-void
-load_slot(SimSlot &s, const int64_t *keyid, const uint64_t *src, uint64_t n, uint64_t rows, int all, uint32_t pass, uint32_t bits,
-          uint64_t wg, uint32_t slot)
-{
-    for (uint32_t x = 0; x < 64; x++) {
-        const uint64_t it = load_item(keyid, src, sre_lr_line(wg, slot, x), n, rows, all);
-        s.sel[x] = it != SRE_LRK_DROPPED;
-        s.digit[x] = sre_lrk_digit(it, pass, bits);
-    }
-}
 
 }  // namespace
 
@@ -118,38 +75,11 @@ void
 lrksim_count(const int64_t *keyid, const uint64_t *src, uint64_t n, uint64_t rows, int all, uint32_t pass, uint32_t bits, int rule,
              uint64_t *cnt, uint32_t *writes)
 {
-    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
-    const uint32_t nd = 1u << bits;
-    SimSlot        s;
-    for (uint64_t w = 0; w < nwg; w++) {
-        std::vector<uint32_t> c(SRE_LR_SLOTS * nd, 0);
-        for (uint32_t v = 0; v < SRE_LR_WAVES; v++) {
-            for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-                const uint32_t slot = sre_lr_slot(v, q);
-                load_slot(s, keyid, src, n, rows, all, pass, bits, w, slot);
-                (void) s.run(rule, bits, c.data() + slot * nd);
-            }
-        }
-        for (uint32_t d = 0; d < nd; d++) {
-            const uint64_t at = sre_lr_cnt_index(d, nwg, w);
-            cnt[at] = sre_lr_slot_prefix(c.data() + d, nd);
-            writes[at]++;
-        }
-    }
+    const SimKeyPass p = {keyid, src, n, rows, all, pass, bits, rule, NULL, NULL};
+    (void) sim_count(p, n, cnt, writes);
 }
 
-/* the scan as the filter's scan leaves it: exclusive, the total behind the last word */
-void
-lrksim_scan(uint64_t *v, uint64_t n)
-{
-    uint64_t run = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t x = v[i];
-        v[i] = run;
-        run += x;
-    }
-    v[n] = run;
-}
+void lrksim_scan(uint64_t *v, uint64_t n) { sim_scan(v, n); }
 
 /* scatter of one pass over the scanned counts; writes[r] counts the stores to dst[r].  Returns the stores that fell outside
  * [0, total) */
@@ -157,45 +87,8 @@ uint64_t
 lrksim_scatter(const int64_t *keyid, const uint64_t *src, uint64_t n, uint64_t rows, int all, uint32_t pass, uint32_t bits, int rule,
                const uint64_t *first, uint64_t total, uint64_t *dst, uint32_t *writes)
 {
-    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
-    const uint32_t nd = 1u << bits;
-    uint64_t       bad = 0;
-    for (uint64_t w = 0; w < nwg; w++) {
-        std::vector<uint32_t> c(SRE_LR_SLOTS * nd, 0);
-        std::vector<uint32_t> rk(SRE_LR_ITEMS, 0);
-        std::vector<uint64_t> gbase(nd, 0);
-        SimSlot               s;
-        for (uint32_t v = 0; v < SRE_LR_WAVES; v++) {
-            for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-                const uint32_t slot = sre_lr_slot(v, q);
-                load_slot(s, keyid, src, n, rows, all, pass, bits, w, slot);
-                (void) s.run(rule, bits, c.data() + slot * nd);
-                for (uint32_t x = 0; x < 64; x++) rk[slot * 64 + x] = s.rank[x];
-            }
-        }
-        for (uint32_t d = 0; d < nd; d++) {
-            (void) sre_lr_slot_prefix(c.data() + d, nd);
-            gbase[d] = first[sre_lr_cnt_index(d, nwg, w)];
-        }
-        for (uint32_t v = 0; v < SRE_LR_WAVES; v++) {
-            for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-                const uint32_t slot = sre_lr_slot(v, q);
-                for (uint32_t x = 0; x < 64; x++) {
-                    const uint64_t it = load_item(keyid, src, sre_lr_line(w, slot, x), n, rows, all);
-                    if (it == SRE_LRK_DROPPED) continue;
-                    const uint32_t d = sre_lrk_digit(it, pass, bits);
-                    const uint64_t r = gbase[d] + c[slot * nd + d] + rk[slot * 64 + x];
-                    if (r >= total) {
-                        bad++;
-                        continue;
-                    }
-                    dst[r] = it;
-                    writes[r]++;
-                }
-            }
-        }
-    }
-    return bad;
+    SimKeyPass p = {keyid, src, n, rows, all, pass, bits, rule, dst, writes};
+    return sim_scatter(p, n, first, total);
 }
 
 /* the compact table and the head flags from the sorted items; writes[r] counts the stores to each of the three words of rank r */

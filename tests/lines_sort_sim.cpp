@@ -1,16 +1,14 @@
 /*
- * lines_sort_sim.cpp — the line sort on the CPU: the values pass, then count, scan and scatter of every digit pass run
- * workgroup by workgroup, slot by slot and lane by lane with the rules the kernels compile (sregex_amd/csrc/sre_lines_sort.h,
- * sre_lines_route_key.h, sre_lines_route.h, sre_lines_sums.h): the class and the value of a line, the totals a workgroup
- * sends, the sort key, the digit, the rank rule of a slot on ballots, the slot prefix and the global rank; then the compact
- * table, the result words and the index rows.  Every store and every atomic is counted, so tests/test_lines_sort_model.py
+ * lines_sort_sim.cpp — the line sort on the CPU: the values pass, then every digit pass through the partition model
+ * (lines_partition_sim.h), with the rules the kernels compile (sregex_amd/csrc/sre_lines_sort.h, sre_lines_route_key.h,
+ * sre_lines_route.h, sre_lines_sums.h): the class and the value of a line, the totals a workgroup sends, the sort key and
+ * the digit; then the compact table, the result words and the index rows.  Every store and every atomic is counted, so tests/test_lines_sort_model.py
  * can assert that every word of every array is written exactly once per pass.  The gather over the table is the extract's
  * model (tests/lines_extract_sim.cpp), unchanged.  tools/asan_sort_rule.cpp includes this file.
  */
 #include "sre_lines_sort.h"
-#include <stdint.h>
+#include "lines_partition_sim.h"
 #include <string.h>
-#include <vector>
 
 namespace {
 
@@ -50,60 +48,12 @@ struct SimMem {
     }
 };
 
-/* one slot of 64 lanes in lockstep: what slot_rank<SRE_LRK_RANK_BITS> of sre_hip_lines_rank.h does with __ballot */
-struct SimSlot {
-    bool     sel[64];
-    uint32_t digit[64];
-    uint32_t rank[64];
-
-    template <class Pred> uint64_t ballot(Pred pred) const
-    {
-        uint64_t m = 0;
-        for (uint32_t x = 0; x < 64; x++) m |= (uint64_t) (pred(x) ? 1 : 0) << x;
-        return m;
-    }
-
-    void run(uint32_t *c)
-    {
-        uint64_t       m[64];
-        const uint64_t all = ballot([&](uint32_t x) { return sel[x]; });
-        for (uint32_t x = 0; x < 64; x++) m[x] = all;
-        for (uint32_t bit = 0; bit < SRE_LSO_DIGIT_BITS; bit++) {
-            const uint64_t with_bit = ballot([&](uint32_t x) { return sel[x] && ((digit[x] >> bit) & 1u); });
-            for (uint32_t x = 0; x < 64; x++) m[x] = sre_lrk_agree(m[x], with_bit, digit[x], bit);
-        }
-        for (uint32_t x = 0; x < 64; x++) {
-            const uint32_t r = sre_lr_rank_in(m[x], x);
-            if (sel[x] && r == 0) c[digit[x]] = sre_lr_popc(m[x]);
-            rank[x] = sel[x] ? r : 0;
-        }
-    }
-};
-
 /* what every digit pass knows of the call (SortKeys of sre_hip_lines_sort.hip) */
 struct SimKeys {
     int64_t  vmin, vmax;
     uint64_t range;
     int      desc, all;
 };
-
-uint64_t
-load_key(const int64_t *value, const int8_t *cls, const uint64_t *src, uint64_t i, uint64_t n, const SimKeys &k)
-{
-    if (i >= n) return SRE_LSO_DROPPED;
-    return value ? sre_lso_key(cls[i], value[i], k.vmin, k.vmax, k.range, k.desc, k.all) : src[i];
-}
-
-void
-load_slot(SimSlot &s, const int64_t *value, const int8_t *cls, const uint64_t *src, uint64_t n, const SimKeys &k, uint32_t pass,
-          uint64_t wg, uint32_t slot)
-{
-    for (uint32_t x = 0; x < 64; x++) {
-        const uint64_t key = load_key(value, cls, src, sre_lr_line(wg, slot, x), n, k);
-        s.sel[x] = key != SRE_LSO_DROPPED;
-        s.digit[x] = sre_lso_digit(key, pass);
-    }
-}
 
 SimKeys
 sim_keys(int64_t vmin, int64_t vmax, uint64_t nnumbered, int desc, int all)
@@ -116,6 +66,35 @@ sim_keys(int64_t vmin, int64_t vmax, uint64_t nnumbered, int desc, int all)
     k.all = all;
     return k;
 }
+
+/* a digit pass (SortPass of sre_hip_lines_sort.hip; value != NULL: pass 0 over the lines); kw[r] / lw[r] count the stores to
+ * dkey[r] / dline[r] */
+struct SimSortPass {
+    const int64_t  *value;
+    const int8_t   *cls;
+    const uint64_t *src;
+    const uint32_t *sline;
+    uint64_t        n;
+    SimKeys         k;
+    uint32_t        pass;
+    uint64_t       *dkey;
+    uint32_t       *dline, *kw, *lw;
+    uint32_t nd() const { return 1u << SRE_LSO_DIGIT_BITS; }
+    uint32_t bits() const { return SRE_LSO_DIGIT_BITS; }
+    int      rule() const { return SRE_LRK_RANK_BITS; }
+    uint64_t load(uint64_t i) const
+    {
+        if (i >= n) return SRE_LSO_DROPPED;
+        return value ? sre_lso_key(cls[i], value[i], k.vmin, k.vmax, k.range, k.desc, k.all) : src[i];
+    }
+    bool     taken(uint64_t key) const { return key != SRE_LSO_DROPPED; }
+    uint32_t digit(uint64_t key) const { return sre_lso_digit(key, pass); }
+    void     store(uint64_t r, uint64_t key, uint64_t i)
+    {
+        dkey[r] = key, kw[r]++;
+        dline[r] = value ? (uint32_t) i : sline[i], lw[r]++;
+    }
+};
 
 }  // namespace
 
@@ -182,39 +161,11 @@ void
 lsosim_count(const int64_t *value, const int8_t *cls, const uint64_t *src, uint64_t n, int64_t vmin, int64_t vmax, uint64_t nnum,
              int desc, int all, uint32_t pass, uint64_t *cnt, uint32_t *writes)
 {
-    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
-    const uint32_t nd = 1u << SRE_LSO_DIGIT_BITS;
-    const SimKeys  k = sim_keys(vmin, vmax, nnum, desc, all);
-    SimSlot        s;
-    for (uint64_t w = 0; w < nwg; w++) {
-        std::vector<uint32_t> c(SRE_LR_SLOTS * nd, 0);
-        for (uint32_t v = 0; v < SRE_LR_WAVES; v++) {
-            for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-                const uint32_t slot = sre_lr_slot(v, q);
-                load_slot(s, value, cls, src, n, k, pass, w, slot);
-                s.run(c.data() + slot * nd);
-            }
-        }
-        for (uint32_t d = 0; d < nd; d++) {
-            const uint64_t at = sre_lr_cnt_index(d, nwg, w);
-            cnt[at] = sre_lr_slot_prefix(c.data() + d, nd);
-            writes[at]++;
-        }
-    }
+    const SimSortPass p = {value, cls, src, NULL, n, sim_keys(vmin, vmax, nnum, desc, all), pass, NULL, NULL, NULL, NULL};
+    (void) sim_count(p, n, cnt, writes);
 }
 
-/* the scan as the filter's scan leaves it: exclusive, the total behind the last word */
-void
-lsosim_scan(uint64_t *v, uint64_t n)
-{
-    uint64_t run = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t x = v[i];
-        v[i] = run;
-        run += x;
-    }
-    v[n] = run;
-}
+void lsosim_scan(uint64_t *v, uint64_t n) { sim_scan(v, n); }
 
 /* scatter of one pass over the scanned counts; kw[r] / lw[r] count the stores to dkey[r] / dline[r].  Returns the stores that
  * fell outside [0, total) */
@@ -223,47 +174,8 @@ lsosim_scatter(const int64_t *value, const int8_t *cls, const uint64_t *src, con
                int64_t vmax, uint64_t nnum, int desc, int all, uint32_t pass, const uint64_t *first, uint64_t total, uint64_t *dkey,
                uint32_t *dline, uint32_t *kw, uint32_t *lw)
 {
-    const uint64_t nwg = (n + SRE_LR_ITEMS - 1) / SRE_LR_ITEMS;
-    const uint32_t nd = 1u << SRE_LSO_DIGIT_BITS;
-    const SimKeys  k = sim_keys(vmin, vmax, nnum, desc, all);
-    uint64_t       bad = 0;
-    for (uint64_t w = 0; w < nwg; w++) {
-        std::vector<uint32_t> c(SRE_LR_SLOTS * nd, 0);
-        std::vector<uint32_t> rk(SRE_LR_ITEMS, 0);
-        std::vector<uint64_t> gbase(nd, 0);
-        SimSlot               s;
-        for (uint32_t v = 0; v < SRE_LR_WAVES; v++) {
-            for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-                const uint32_t slot = sre_lr_slot(v, q);
-                load_slot(s, value, cls, src, n, k, pass, w, slot);
-                s.run(c.data() + slot * nd);
-                for (uint32_t x = 0; x < 64; x++) rk[slot * 64 + x] = s.rank[x];
-            }
-        }
-        for (uint32_t d = 0; d < nd; d++) {
-            (void) sre_lr_slot_prefix(c.data() + d, nd);
-            gbase[d] = first[sre_lr_cnt_index(d, nwg, w)];
-        }
-        for (uint32_t v = 0; v < SRE_LR_WAVES; v++) {
-            for (uint32_t q = 0; q < SRE_LR_ROUNDS; q++) {
-                const uint32_t slot = sre_lr_slot(v, q);
-                for (uint32_t x = 0; x < 64; x++) {
-                    const uint64_t i = sre_lr_line(w, slot, x);
-                    const uint64_t key = load_key(value, cls, src, i, n, k);
-                    if (key == SRE_LSO_DROPPED) continue;
-                    const uint32_t d = sre_lso_digit(key, pass);
-                    const uint64_t r = gbase[d] + c[slot * nd + d] + rk[slot * 64 + x];
-                    if (r >= total) {
-                        bad++;
-                        continue;
-                    }
-                    dkey[r] = key, kw[r]++;
-                    dline[r] = value ? (uint32_t) i : sline[i], lw[r]++;
-                }
-            }
-        }
-    }
-    return bad;
+    SimSortPass p = {value, cls, src, sline, n, sim_keys(vmin, vmax, nnum, desc, all), pass, dkey, dline, kw, lw};
+    return sim_scatter(p, n, first, total);
 }
 
 /* the compact table of the first nout ranks; writes[r] counts the stores to the two words of rank r */
@@ -280,7 +192,7 @@ lsosim_table(const uint32_t *lines, const uint64_t *ends, uint64_t nout, uint64_
     }
 }
 
-void lsosim_result(const uint64_t *coff, uint64_t nout, uint64_t out_cap, uint64_t *res) { sre_lso_result(coff, nout, out_cap, res); }
+void lsosim_result(const uint64_t *coff, uint64_t nout, uint64_t out_cap, uint64_t *res) { sre_lr_result(coff, nout, out_cap, res); }
 
 void
 lsosim_index_row(uint64_t line, const uint64_t *cstart, const uint64_t *coff, uint64_t r, int64_t value, int32_t cls, int64_t *row)

@@ -208,7 +208,7 @@ def profile(calls, stats_out):
             names = sorted({n for c in mine for n in c})
             kernels = {n: {"us": statistics.median([c.get(n, (0, 0))[0] for c in mine]) / 1e3, "dispatches": mine[0].get(n, (0, 0))[1]}
                        for n in names}
-            part = sum(v["us"] for n, v in kernels.items() if "route_key_count" in n or "route_key_scatter" in n)
+            part = sum(v["us"] for n, v in kernels.items() if "partition_count" in n or "partition_scatter" in n)
             out.append({"set_keys": size, "passes": PASSES[size], "rule": rule, "kernels": kernels,
                         "count_and_scatter_us": part, "count_and_scatter_us_per_pass": part / PASSES[size],
                         "all_kernels_us": statistics.median([sum(v[0] for v in c.values()) for c in mine]) / 1e3})

@@ -16,7 +16,7 @@ slow whichever call it is.  Then, in a run of its own, the child under rocprofv3
 (s) ascending with limit 0 and (b); the kernels of a call are listed per range with their time and dispatches per call.
 
 --parent-lib PATH: the condition that the calls that existed before cost what they cost before.  lookup_lines,
-route_lines_by_key and tally_sums_lines are timed in child processes that load PATH (a build of the parent commit, through
+route_lines_by_key, tally_sums_lines and sort_lines (three passes) are timed in child processes that load PATH (a build of the parent commit, through
 SREGEX_AMD_LIB) and this tree's library in turn: parent, branch, parent, branch.  A difference between the medians counts as
 none when it is no larger than the span of the --reps calls of one parent process; every call's figure is kept.
 
@@ -215,8 +215,7 @@ def profile(calls, stats_out):
             names = sorted({n for c in mine for n in c})
             kernels = {n: {"us": statistics.median([c.get(n, (0, 0))[0] for c in mine]) / 1e3, "dispatches": mine[0].get(n, (0, 0))[1]}
                        for n in names}
-            tag = "k_sort_" if call == "sort" else "route_key_"
-            part = sum(v["us"] for n, v in kernels.items() if tag + "count" in n or tag + "scatter" in n)
+            part = sum(v["us"] for n, v in kernels.items() if "partition_count" in n or "partition_scatter" in n)
             out.append({"passes": passes, "call": call, "kernels": kernels, "count_and_scatter_us": part,
                         "count_and_scatter_us_per_pass": part / passes,
                         "all_kernels_us": statistics.median([sum(v[0] for v in c.values()) for c in mine]) / 1e3})
@@ -228,7 +227,7 @@ def profile(calls, stats_out):
 
 
 def older(reps):
-    """lookup_lines, route_lines_by_key and tally_sums_lines with whatever library this process loaded"""
+    """lookup_lines, route_lines_by_key, tally_sums_lines and sort_lines with whatever library this process loaded"""
     lib = S.load_library()
     size = 4096
     with S.Pool() as pool:
@@ -239,7 +238,7 @@ def older(reps):
         buf, nbytes, _ = fill_lines(lib, 1 << 24, size)
         out, keyid, buckets = S.DeviceBuffer(nbytes), S.DeviceBuffer(8 * NLINES), S.DeviceBuffer(40 * NLINES)
         sums = S.DeviceBuffer(32 * size)
-        tl, tr, tt = [], [], []
+        tl, tr, tt, ts = [], [], [], []
         for rep in range(reps + 1):
             d, info = timed(lambda: sc.lookup_lines(buf.ptr, nbytes, out.ptr, nbytes, KEY_GROUP, ks, keyid_ptr=keyid.ptr, keyid_cap=NLINES))
             assert info.nwritten == NLINES
@@ -252,7 +251,11 @@ def older(reps):
                                                          sums_ptr=sums.ptr, sums_cap=size))
             assert tinfo.nkeys == size
             tt.append(d)
-        print(json.dumps({"lookup_ms": ms(tl[1:]), "route_lines_by_key_ms": ms(tr[1:]), "tally_sums_ms": ms(tt[1:])}))
+            d, sinfo = timed(lambda: sort_call(sc, buf, nbytes, out, False, 0))
+            assert sinfo.nwritten == NLINES and sinfo.passes == 3
+            ts.append(d)
+        print(json.dumps({"lookup_ms": ms(tl[1:]), "route_lines_by_key_ms": ms(tr[1:]), "tally_sums_ms": ms(tt[1:]),
+                          "sort_lines_ms": ms(ts[1:])}))
 
 
 def older_ab(parent_lib, reps):
@@ -268,7 +271,7 @@ def older_ab(parent_lib, reps):
                               stdout=subprocess.PIPE, timeout=300).stdout.decode()
         runs.append((which, json.loads(text.strip().splitlines()[-1])))
     rows = []
-    for metric in ("lookup_ms", "route_lines_by_key_ms", "tally_sums_ms"):
+    for metric in ("lookup_ms", "route_lines_by_key_ms", "tally_sums_ms", "sort_lines_ms"):
         p_runs = [r[metric]["all"] for w, r in runs if w == "parent"]
         p = [r[metric]["median"] for w, r in runs if w == "parent"]
         b = [r[metric]["median"] for w, r in runs if w == "branch"]
@@ -325,8 +328,8 @@ def main():
                           "kernel_stats_top": top, "rows": per}
     if args.parent_lib:
         doc["older_calls_parent_vs_branch"] = {
-            "run": "lookup_lines, route_lines_by_key (4096 keys each) and tally_sums_lines (4096 keys, one value column) over a "
-                   "million lines in child processes that load the parent commit's library and this tree's in turn (parent, branch, "
+            "run": "lookup_lines, route_lines_by_key (4096 keys each), tally_sums_lines (4096 keys, one value column) and sort_lines "
+                   "(ascending, no limit, 2^24 values: three passes) over a million lines in child processes that load the parent commit's library and this tree's in turn (parent, branch, "
                    "parent, branch); medians of reps after a warm-up",
             "rows": older_ab(args.parent_lib, args.reps)}
     text = json.dumps(doc, indent=1)
