@@ -42,6 +42,49 @@ typedef sre_u32x4 __attribute__((aligned(1))) sre_u32x4_unaligned;
  * (address space 1) on purpose: a flat load also counts on lgkmcnt, so every
  * wait for an LDS lookup in the consumer would wait for the prefetch as well.
  */
+/* Load policy of the staged loads.  Every input line is read once and never again, so
+ * the loads can be issued non-temporal (global_load_dwordx4 ... nt).  Measured per
+ * kernel, this build against the default policy and the parent commit in alternating
+ * runs on one box (profiles/scan_fetch_rate.json): the scan kernels gain (headline
+ * 0.95-0.97 x the step time, 128 streams of 64 MiB 0.93 x, nothing without nt), the
+ * plain-slice NFA kernel gains 0.7 % more than it does without; the shift-and kernel
+ * LOSES 4 % with nt and the wide kernel does not move, so the half-line staging
+ * (tile2_fetch) keeps the default policy.  SRE_TILE_LOAD_NT=0 builds tile_fetch with the
+ * default policy too (the A/B build); a caller chooses through the template argument. */
+#ifndef SRE_TILE_LOAD_NT
+#define SRE_TILE_LOAD_NT 1
+#endif
+
+/* what a piece outside its row's readable range is loaded from */
+__device__ const uint4 sre_tile_zeros = {0, 0, 0, 0};
+
+/* The four loads of a stage, given the lane's four row descriptors and offsets.
+ * Every load is issued, without a branch: a piece outside its row's readable range
+ * loads the block of zeros instead (an `if` around each load puts each behind its
+ * own branch and descriptor round trip, and the compiler then cannot count the loads
+ * in flight: the consumer waits for all four before it classifies the first). */
+template <bool NT>
+__device__ inline void
+tile_load4(uint4 (&regs)[4], const uint4 (&d)[4], const int32_t (&off)[4])
+{
+    typedef const __attribute__((address_space(1))) sre_u32x4_unaligned *src_t;
+    const uint64_t zeros = (uint64_t) reinterpret_cast<uintptr_t>(&sre_tile_zeros);
+    uint64_t       a[4];
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+        const bool ok = (off[i] >= (int32_t) d[i].z) & (off[i] <= (int32_t) d[i].w);
+        a[i] = ok ? (((uint64_t) d[i].y << 32) | d[i].x) + (uint64_t) (int64_t) off[i] : zeros;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 4; i++) {
+        /* rows start wherever the stream does: the load may be unaligned,
+         * which the hardware handles */
+        const sre_u32x4 v = NT ? __builtin_nontemporal_load(reinterpret_cast<src_t>(a[i])) : *reinterpret_cast<src_t>(a[i]);
+        regs[i] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+}
+
+template <bool NT = (SRE_TILE_LOAD_NT != 0)>
 __device__ inline void
 tile_fetch(uint4 (&regs)[4], const RowDesc *rows, uint32_t tid, uint32_t stage)
 {
@@ -49,21 +92,13 @@ tile_fetch(uint4 (&regs)[4], const RowDesc *rows, uint32_t tid, uint32_t stage)
      * wave, so no workgroup barrier is needed between rounds */
     const uint32_t wbase = (tid & ~63u) + (stage & 1u) * 32u, lane = tid & 63u;
     const int32_t  line_off = (int32_t) ((stage >> 1) * SRE_SCAN_LINE);
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++) {
-        const uint32_t piece = i * 64 + lane;
-        const uint32_t row = wbase + piece / 8, col = piece % 8;
-        const int32_t  off = line_off + (int32_t) (col * 16);
-        const uint4    d = *reinterpret_cast<const uint4 *>(&rows[row]);
-        sre_u32x4      v = {0, 0, 0, 0};
-        if ((off >= (int32_t) d.z) & (off <= (int32_t) d.w)) {
-            const uint64_t a = (((uint64_t) d.y << 32) | d.x) + (uint64_t) (int64_t) off;
-            /* rows start wherever the stream does: the load may be unaligned,
-             * which the hardware handles */
-            v = *reinterpret_cast<const __attribute__((address_space(1))) sre_u32x4_unaligned *>(a);
-        }
-        regs[i] = make_uint4(v.x, v.y, v.z, v.w);
-    }
+    /* piece i = 64 i + lane lies in row wbase + 8 i + lane / 8: the lane's four
+     * descriptors are fixed offsets from one address, read in one LDS round trip */
+    const uint4   *mine = reinterpret_cast<const uint4 *>(&rows[wbase + lane / 8]);
+    const uint4    d[4] = {mine[0], mine[8], mine[16], mine[24]};
+    const int32_t  o = line_off + (int32_t) (lane % 8 * 16);
+    const int32_t  off[4] = {o, o, o, o};
+    tile_load4<NT>(regs, d, off);
 }
 
 /* Stage one line per row of half a wave into LDS.  The raw bytes are classified
@@ -130,23 +165,20 @@ tile_store(const uint4 (&regs)[4], uint8_t *tile, const uint16_t (*clsx)[256], u
  */
 constexpr uint32_t SRE_TILE2_ROWB = SRE_SCAN_ROUND + 16;    /* 64 bytes + pad: 16-byte reads of a row are conflict-free */
 
+template <bool NT = false>        /* see SRE_TILE_LOAD_NT */
 __device__ inline void
 tile2_fetch(uint4 (&regs)[4], const RowDesc *rows, uint32_t tid, uint32_t stage)
 {
     const uint32_t wbase = (tid & ~63u) + (stage & 1u) * 32u, lane = tid & 63u;
     const int32_t  line_off = (int32_t) ((stage >> 1) * SRE_SCAN_LINE);
-#pragma unroll
-    for (uint32_t i = 0; i < 4; i++) {
-        const uint32_t row = wbase + (lane >> 2) + 16u * (i >> 1), col = (lane & 3u) + 4u * (i & 1u);
-        const int32_t  off = line_off + (int32_t) (col * 16);
-        const uint4    d = *reinterpret_cast<const uint4 *>(&rows[row]);
-        sre_u32x4      v = {0, 0, 0, 0};
-        if ((off >= (int32_t) d.z) & (off <= (int32_t) d.w)) {
-            const uint64_t a = (((uint64_t) d.y << 32) | d.x) + (uint64_t) (int64_t) off;
-            v = *reinterpret_cast<const __attribute__((address_space(1))) sre_u32x4_unaligned *>(a);
-        }
-        regs[i] = make_uint4(v.x, v.y, v.z, v.w);
-    }
+    /* pieces 0 / 1 are the two halves of the line of row q, pieces 2 / 3 those of row q + 16:
+     * two descriptors, read in one LDS round trip */
+    const uint4   *mine = reinterpret_cast<const uint4 *>(&rows[wbase + (lane >> 2)]);
+    const uint4    d0 = mine[0], d1 = mine[16];
+    const uint4    d[4] = {d0, d0, d1, d1};
+    const int32_t  o = line_off + (int32_t) ((lane & 3u) * 16);
+    const int32_t  off[4] = {o, o + 64, o, o + 64};
+    tile_load4<NT>(regs, d, off);
 }
 
 __device__ inline void
