@@ -1048,6 +1048,101 @@ SRE_API int sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t 
     sre_int_t *d_index, size_t index_cap,
     sre_hip_sort_info_t *info, void *hip_stream);
 
+/* ---- the ordered tally: key rows ordered by count or by an aggregate, with a limit ---- */
+
+enum { SRE_HIP_TOP_COUNT = 0, SRE_HIP_TOP_SUM = 1, SRE_HIP_TOP_MIN = 2, SRE_HIP_TOP_MAX = 3, SRE_HIP_TOP_N = 4 };
+
+typedef struct {
+    size_t  nlines;      /* lines of the buffer */
+    size_t  nselected;   /* lines that have a key (the sum of all counts) */
+    size_t  nkeys;       /* distinct keys, whatever limit is */
+    size_t  nordered;    /* keys whose order column holds a value */
+    size_t  nrows;       /* rows of the limited output: min(limit, nkeys), nkeys when limit == 0 */
+    size_t  need_bytes, nwritten, out_bytes;   /* of those nrows rows; truncation as in the tally */
+    size_t  passes;      /* digit passes of the sort */
+    int64_t vmin, vmax;  /* extremes of the order values; INT64_MAX / INT64_MIN when nordered == 0 */
+} sre_hip_tally_top_info_t;
+
+/*
+ * Ordered tally: sre_hip_tally_sums_lines whose rows, counts, aggregates and index come out in a
+ * chosen order, optionally only the first `limit` keys (`sort | uniq -c | sort -rn | head`, GROUP
+ * BY key ORDER BY COUNT(*) DESC LIMIT k: "the ten busiest clients", "endpoints by total bytes").
+ * It offers what the "Not offered" lists of sre_hip_tally_lines ("keys ordered by count ..,
+ * top-k") and of sre_hip_sort_lines ("a per-line value array ..") decline, for counts and
+ * aggregates; the order stays on the device, and so does the output.
+ *
+ * What is the tally's.  On the same (sc, d_buf, len, delim, groups, ngroups, vgroups, nvgroups,
+ * fsep, max_keys) and the SRE_HIP_LINES_ALL bit of flags the split, the matching, the routing to
+ * an engine (host routes included), the batching, the diagnostics, the demand for an
+ * SRE_HIP_PIKE_FIRST scanner, the key, the rules of groups / vgroups / fsep, the number rule,
+ * max_keys and SRE_HIP_TALLY_OVERFLOW are exactly those of sre_hip_tally_sums_lines.  On overflow
+ * nothing of the caller's arrays is written and info holds nlines and nselected only.
+ *
+ * Flags.  flags is any of SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC; any other bit returns -1.
+ * nvgroups == 0 with vgroups == NULL is allowed only with by == SRE_HIP_TOP_COUNT and sums_cap
+ * == 0; d_sums must be 8-byte aligned.
+ *
+ * The order value of key k: SRE_HIP_TOP_COUNT its count; SRE_HIP_TOP_N the n of value column
+ * by_col; SRE_HIP_TOP_SUM / _MIN / _MAX that field of column by_col, the sum as d_sums holds it,
+ * after wrapping.  `by` outside the enum, by_col >= nvgroups for a column order and by_col != 0
+ * for SRE_HIP_TOP_COUNT return -1.  A key is ORDERED unless by is SUM, MIN or MAX and the
+ * column's n is 0.  info->nordered counts the ordered keys, vmin / vmax are their extremes; they
+ * are the identities INT64_MAX / INT64_MIN without an ordered key, for len == 0 (zeros elsewhere,
+ * and success) and on overflow.
+ *
+ * The order.  First the ordered keys by order value, ascending, or descending with
+ * SRE_HIP_SORT_DESC; keys of equal value in first-appearance order in BOTH directions; then the
+ * keys that are not ordered, in first-appearance order, whatever the direction.  The sort, its
+ * stability and info->passes are those of sre_hip_sort_lines over the keys.  limit != 0 keeps the
+ * first `limit` rows: info->nrows = min(limit, nkeys).  It is always the full sort, then the cut.
+ *
+ * Outputs, all in output order.  Row r of d_out is the tally's row of the key at rank r, in the
+ * extract's row format.  Truncation and the sizing call are the tally's: whole rows, and d_out ==
+ * NULL with out_cap == 0 sizes the output; need_bytes, nwritten and out_bytes describe the nrows
+ * rows.  d_counts[r] holds the count for r below min(counts_cap, nrows), d_sums[r * nvgroups + v]
+ * the aggregates for r below min(sums_cap, nrows), both whatever out_cap is.  d_index holds for
+ * the first min(index_cap, nwritten) rows the extract's index row of the key's first line, 4 + 2
+ * ngroups sre_int_t with [3] the row's offset in THIS output, and two more words: the key's
+ * number in first-appearance order, and its order value (0 when not ordered); 6 + 2 ngroups
+ * sre_int_t a row.  d_rank[i], for i below min(rank_cap, nlines), is the rank of line i's key in
+ * the FULL order, whatever limit and out_cap are, -1 for a line without a key.  The output with
+ * limit == 0 is a valid dictionary for sre_hip_keyset_create, and d_rank then equals the key ids
+ * sre_hip_lookup_lines gives against it.  Nothing beyond the entries named is touched.  A NULL
+ * pointer with a cap other than 0 returns -1, for every array.
+ *
+ * Range.  The sort's key rule reserves the all-ones key and gives the keys that are not ordered
+ * RANGE + 1, so a call whose vmax - vmin exceeds 2^64 - 3 returns -1 with one diagnostic line and
+ * nothing written to the caller's arrays.  Only sums that wrapped reach that.  An item carries
+ * the key's number in 32 bits, which max_keys <= 2^30 guarantees.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  The host waits as often as in
+ * sre_hip_tally_sums_lines, plus two reads: one of the four totals (nkeys, nordered, vmin, vmax),
+ * which fixes the sort keys and the passes, and one of the four result words.  Nothing per key or
+ * per line travels to the host.
+ *
+ * Memory.  Beyond what sre_hip_tally_sums_lines takes, a scanner keeps of the largest call per
+ * key 20 + 32 nvgroups bytes of its own (count, aggregates, first line, inverse rank) and 8
+ * ngroups bytes per row in front of the limit (the ordered table's starts); with
+ * sre_hip_sort_lines it shares per key 9 bytes (value and class), 24 bytes of items and 2 KiB per
+ * 1024 keys of counts, and with sre_hip_route_lines 8 ngroups bytes per row.  Nothing is kept per
+ * line.  All grow-only device memory, freed with the scanner; sre_hip_tally_lines,
+ * sre_hip_tally_sums_lines and sre_hip_sort_lines neither allocate nor fill the call's own.
+ *
+ * Not offered: order by key text; several order columns in one call; a partial top-k selection
+ * in place of the full sort; floating-point averages; every match of a line; Thompson and COUNT
+ * scanners; stream sets.
+ * Returns 0 on success, SRE_HIP_TALLY_OVERFLOW, or -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_tally_top_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, const int *vgroups, size_t nvgroups, int fsep, int flags,
+    size_t max_keys, int by, size_t by_col, size_t limit,
+    void *d_out, size_t out_cap,
+    uint64_t *d_counts, size_t counts_cap,
+    sre_hip_tally_sum_t *d_sums, size_t sums_cap,
+    sre_int_t *d_rank, size_t rank_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_tally_top_info_t *info, void *hip_stream);
+
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 
 typedef struct sre_hip_streams_s sre_hip_streams_t;

@@ -28,6 +28,7 @@ ENGINE_AUTO, ENGINE_VM, ENGINE_SCAN, ENGINE_NFA = 0, 1, 2, 3
 HIP_LINES_ALL = 1
 HIP_LINES_INVERT = 2
 HIP_SORT_DESC = 4
+HIP_TOP_COUNT, HIP_TOP_SUM, HIP_TOP_MIN, HIP_TOP_MAX, HIP_TOP_N = 0, 1, 2, 3, 4
 HIP_EXTRACT_MAX_FIELDS = 32
 HIP_SUBST_MAX_PIECES = 30
 HIP_JOIN_MAX_VALUES = 31
@@ -123,6 +124,9 @@ API = {
     "sre_hip_route_lines_by_key": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int,
                                                   _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_sort_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_tally_top_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz,
+                                               ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _sz, ctypes.c_int, _sz,
+                                               _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_scanner_last_line_batches": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_lines_device": (ctypes.c_int, [_vp]),
     "sre_hip_scanner_last_short_lines": (_sz, [_vp]),
@@ -747,6 +751,35 @@ class Scanner:
             raise RuntimeError("sre_hip_sort_lines failed")
         return SortInfo(*(getattr(info, name) for name in SortInfo._fields))
 
+    def tally_top_lines(self, ptr, length, out_ptr, out_cap, groups, vgroups, max_keys, by=HIP_TOP_COUNT, by_col=0,
+                        descending=True, limit=0, delim=0x0A, fsep=0x09, all_lines=False, counts_ptr=None, counts_cap=0,
+                        sums_ptr=None, sums_cap=0, rank_ptr=None, rank_cap=0, index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_tally_top_lines: tally_sums_lines whose rows, counts, aggregates and index rows come out ordered by the
+        keys' order value: the count (by=HIP_TOP_COUNT), or the n / sum / min / max of value column by_col (HIP_TOP_N,
+        _SUM, _MIN, _MAX), descending or ascending; keys of equal value stay in first-appearance order either way, and
+        the keys whose column holds no number (SUM, MIN, MAX only) follow all others.  limit != 0 keeps the first
+        `limit` rows of that order.  vgroups may be empty with by=HIP_TOP_COUNT and no sums.  counts_ptr / sums_ptr: as
+        in tally_sums_lines, row r the key at rank r; index_ptr: an optional device array of index_cap rows of 6 + 2 *
+        len(groups) int64, the extract's index row of the key's first line with [3] the row's offset in this output, then
+        the key's number in first-appearance order and its order value; rank_ptr: an optional device array of rank_cap
+        int64, the rank of line i's key in the full order or -1.  Returns TallyTopInfo(nlines, nselected, nkeys,
+        nordered, nrows, need_bytes, nwritten, out_bytes, passes, vmin, vmax); raises TallyOverflow as tally_lines does,
+        with nothing written."""
+        groups, vgroups = list(groups), list(vgroups or ())
+        arr = (ctypes.c_int * max(len(groups), 1))(*groups)
+        varr = (ctypes.c_int * len(vgroups))(*vgroups) if vgroups else None
+        info = TallyTopInfoStruct()
+        flags = (HIP_LINES_ALL if all_lines else 0) | (HIP_SORT_DESC if descending else 0)
+        rc = self.lib.sre_hip_tally_top_lines(self.h, ptr, length, delim, arr, len(groups), varr, len(vgroups), fsep, flags,
+                                              max_keys, by, by_col, limit, out_ptr, out_cap, counts_ptr, counts_cap, sums_ptr,
+                                              sums_cap, rank_ptr, rank_cap, index_ptr, index_cap, ctypes.byref(info), hip_stream)
+        res = TallyTopInfo(*(getattr(info, name) for name in TallyTopInfo._fields))
+        if rc == HIP_TALLY_OVERFLOW:
+            raise TallyOverflow(TallyInfo(res.nlines, res.nselected, 0, 0, 0, 0), max_keys)
+        if rc != 0:
+            raise RuntimeError("sre_hip_tally_top_lines failed")
+        return res
+
     @property
     def last_line_batches(self):
         return self.lib.sre_hip_scanner_last_line_batches(self.h)
@@ -769,6 +802,14 @@ TallyInfo = collections.namedtuple("TallyInfo", "nlines nselected nkeys need_byt
 LookupInfo = collections.namedtuple("LookupInfo", "nlines nkeyed nmembers nselected need_bytes nwritten out_bytes")
 RouteKeyInfo = collections.namedtuple("RouteKeyInfo", "nlines nkeyed nmembers nselected nbuckets need_bytes nwritten out_bytes")
 SortInfo = collections.namedtuple("SortInfo", "nlines nkeyed nnumbered nselected need_bytes nwritten out_bytes passes vmin vmax")
+
+
+TallyTopInfo = collections.namedtuple("TallyTopInfo", "nlines nselected nkeys nordered nrows need_bytes nwritten out_bytes passes vmin vmax")
+
+
+class TallyTopInfoStruct(ctypes.Structure):
+    """sre_hip_tally_top_info_t"""
+    _fields_ = [(name, ctypes.c_int64 if name in ("vmin", "vmax") else ctypes.c_size_t) for name in TallyTopInfo._fields]
 
 
 class SortInfoStruct(ctypes.Structure):

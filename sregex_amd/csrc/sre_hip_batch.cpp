@@ -25,6 +25,7 @@
 #include "sre_lines_route_key.h"
 #include "sre_lines_sort.h"
 #include "sre_lines_tally.h"
+#include "sre_lines_tally_top.h"
 #include "sre_lines_sums.h"
 #include "sre_lines_keyset.h"
 #include "sre_lines_join.h"
@@ -199,6 +200,18 @@ struct sre_hip_scanner_s {
     size_t                    sclass_cap;
     uint32_t                 *d_sline[2];       /* the lines of the items, moved with their keys: selected lines words each */
     size_t                    sline_cap[2];
+    /* the ordered tally (sre_hip_tally_top_lines): the tally's tables as they are, the sort's values, classes, items and counts
+     * over the keys (d_jkey, d_sclass, d_kitem, d_sline, d_rcnt), the ordered table's values d_rval's words; it adds */
+    uint64_t                 *d_pcount;         /* the count of every key, in first-appearance order */
+    size_t                    pcount_cap;
+    sre_ls_agg_t             *d_psums;          /* ... and its aggregates: keys x columns */
+    size_t                    psums_cap;
+    uint64_t                 *d_pfirst;         /* ... and its first line */
+    size_t                    pfirst_cap;
+    uint32_t                 *d_pinv;           /* ... and its rank in the order */
+    size_t                    pinv_cap;
+    uint64_t                 *d_pstart;         /* the ordered table's starts: rows in front of the limit x fields words */
+    size_t                    pstart_cap;
 };
 
 /* one stream of a find-all count on the NFA tier */
@@ -281,6 +294,11 @@ scanner_release(void *data)
     if (sc->d_sclass) (void) hipFree(sc->d_sclass);
     if (sc->d_sline[0]) (void) hipFree(sc->d_sline[0]);
     if (sc->d_sline[1]) (void) hipFree(sc->d_sline[1]);
+    if (sc->d_pcount) (void) hipFree(sc->d_pcount);
+    if (sc->d_psums) (void) hipFree(sc->d_psums);
+    if (sc->d_pfirst) (void) hipFree(sc->d_pfirst);
+    if (sc->d_pinv) (void) hipFree(sc->d_pinv);
+    if (sc->d_pstart) (void) hipFree(sc->d_pstart);
     if (sc->d_linfo) (void) hipFree(sc->d_linfo);
     if (sc->h_linfo) (void) hipHostFree(sc->h_linfo);
     if (sc->ntab.accept) (void) hipFree(const_cast<uint64_t *>(sc->ntab.accept));
@@ -3262,6 +3280,171 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     }
     if (info) *info = res;
     return 0;
+hip_failed:
+    return -1;
+}
+
+/* The ordered tally: the tally's call up to its one read, with the cut left open (the rows come out in
+ * another order); the ranks and the sums into the scanner's own arrays; the first line and the order value of every key and
+ * the four totals, one read; the sort's digit passes over the keys; the ordered table of the rows in front of the limit, the
+ * extract's scan and cut over it, one read of its four words; the extract's gather, then counts, aggregates, index rows and
+ * ranks in output order. */
+extern "C" SRE_API int
+sre_hip_tally_top_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+    const int *vgroups, size_t nvgroups, int fsep, int flags, size_t max_keys, int by, size_t by_col, size_t limit, void *d_out,
+    size_t out_cap, uint64_t *d_counts, size_t counts_cap, sre_hip_tally_sum_t *d_sums, size_t sums_cap, sre_int_t *d_rank,
+    size_t rank_cap, sre_int_t *d_index, size_t index_cap, sre_hip_tally_top_info_t *info, void *hip_stream)
+{
+    static_assert(SRE_HIP_TOP_COUNT == SRE_LTT_COUNT && SRE_HIP_TOP_SUM == SRE_LTT_SUM && SRE_HIP_TOP_MIN == SRE_LTT_MIN
+                      && SRE_HIP_TOP_MAX == SRE_LTT_MAX && SRE_HIP_TOP_N == SRE_LTT_N,
+                  "sre_lines_tally_top.h mirrors the public enum");
+    LinesSink            sink;
+    sre_extract_groups_t gr, vg;
+    if (fsep < 0 || fsep > 255 || (flags & ~(SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC)) != 0 || groups == NULL || ngroups < 1
+        || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (counts_cap != 0 && d_counts == NULL) || (sums_cap != 0 && d_sums == NULL)
+        || (rank_cap != 0 && d_rank == NULL) || (reinterpret_cast<uintptr_t>(d_sums) & 7u) != 0 || max_keys < 1
+        || max_keys > SRE_LT_MAX_KEYS || nvgroups > SRE_HIP_TALLY_MAX_VALUES || (vgroups == NULL) != (nvgroups == 0)
+        || (nvgroups == 0 && sums_cap != 0) || !sre_ltt_by_ok(by, by_col, nvgroups))
+    {
+        return -1;
+    }
+    if (!sink_open(&sink, sc, d_buf, len, delim, flags & SRE_HIP_LINES_ALL, d_out, out_cap, d_index, index_cap)) return -1;
+    if (!sink_first_match(sc, "ordered tally", "captures") || !sink_groups(sc, groups, ngroups, &gr)
+        || !sink_groups(sc, vgroups, nvgroups, &vg))
+    {
+        return -1;
+    }
+    sink.groups = &gr;
+    sink.fsep = fsep;
+    if (vgroups) sink.vgroups = &vg;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_tally_top_info_t res;
+    memset(&res, 0, sizeof(res));
+    res.vmin = INT64_MAX;
+    res.vmax = INT64_MIN;
+    int rc = 0;
+    if (n != 0) {
+        const int      desc = (flags & SRE_HIP_SORT_DESC) != 0;
+        const uint32_t k = gr.k, v = (uint32_t) nvgroups;
+        const uint64_t nslots = sre_lt_nslots(max_keys);
+        if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
+        uint64_t *const tab = sc->d_ttab, *const cnt = sc->d_ttab + nslots;
+        SRE_HIP_TRY(hipMemsetAsync(tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
+        SRE_HIP_TRY(hipMemsetAsync(cnt, 0, nslots * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
+        SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, k, nslots, max_keys, tally_hash_mask(), tab, cnt,
+                                            sc->d_tslot, sc->d_linfo, stream));
+        /* the scan of the entry table without a cut: its rows are the source of the ordered table */
+        LinesSink            whole = sink;
+        sre_hip_tally_info_t first;
+        memset(&first, 0, sizeof(first));
+        whole.out_cap = ~(size_t) 0;
+        if (sink_offsets(sc, &whole, n, stream) != 0) return -1;
+        if (sink_read(sc, &whole, n, &first, stream, LINFO(tsel), LINFO(tclaims), LINFO(tover)) != 0) return -1;
+        res.nlines = (size_t) n;
+        res.nselected = (size_t) sc->h_linfo->tsel;
+        if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
+            rc = SRE_HIP_TALLY_OVERFLOW;        /* (nothing is written: only the two counts of lines stand) */
+        } else {
+            const uint64_t nkeys = first.nselected;
+            if (nkeys != sc->h_linfo->tclaims || nkeys > n) return -1;      /* (cannot happen) */
+            const uint64_t nrows = sre_ltt_rows(nkeys, limit);
+            uint64_t       nordered = 0, nwritten = 0, out_bytes = 0;
+            if (nkeys != 0) {
+                const bool     with_sums = v != 0 && (by != SRE_LTT_COUNT || sums_cap != 0);
+                const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS;
+                const uint64_t pcnt = nd * ((nkeys + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
+                /* (d_fblk holds the block sums of the scan above, which the ranks below read: nkeys <= n entries and the
+                 * counts of a pass over them need no more of it than that scan took, so it is not grown here) */
+                if (compact_reserve(sc, nkeys, nd) != 0) return -1;
+                if (lines_grow(&sc->d_pcount, &sc->pcount_cap, nkeys * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_pfirst, &sc->pfirst_cap, nkeys * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_pinv, &sc->pinv_cap, nkeys * sizeof(uint32_t)) != 0) return -1;
+                if (lines_grow(&sc->d_jkey, &sc->jkey_cap, nkeys * sizeof(int64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_sclass, &sc->sclass_cap, nkeys * sizeof(int8_t)) != 0) return -1;
+                if (lines_grow(&sc->d_kitem[0], &sc->kitem_cap[0], (nkeys + 1) * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_kitem[1], &sc->kitem_cap[1], (nkeys + 1) * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_sline[0], &sc->sline_cap[0], nkeys * sizeof(uint32_t)) != 0) return -1;
+                if (lines_grow(&sc->d_sline[1], &sc->sline_cap[1], nkeys * sizeof(uint32_t)) != 0) return -1;
+                if (lines_grow(&sc->d_pstart, &sc->pstart_cap, nrows * k * sizeof(uint64_t)) != 0) return -1;
+                if (lines_grow(&sc->d_rval, &sc->rval_cap, (nrows * k + 1) * sizeof(uint64_t)) != 0) return -1;
+                if (with_sums && lines_grow(&sc->d_psums, &sc->psums_cap, nkeys * v * sizeof(sre_ls_agg_t)) != 0) return -1;
+                /* the tally's ranks and sums, into the scanner's arrays: d_pcount[key], d_psums[key], cnt[slot] = key */
+                SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, k, sc->d_fblk, sc->d_tslot, cnt, sc->d_pcount, nkeys, NULL,
+                                                   0, stream));
+                if (with_sums) {
+                    const uint32_t copies = tally_sum_copies(nkeys, v);
+                    if (copies > 1 && lines_grow(&sc->d_vcopy, &sc->vcopy_cap, copies * nkeys * v * sizeof(sre_ls_agg_t)) != 0) return -1;
+                    SRE_HIP_TRY(sre_launch_tally_sums(d_buf, sc->d_vval, sc->d_vstart, n, v, sc->d_tslot, cnt, nkeys, sc->d_psums,
+                                                      sc->d_vcopy, copies, stream));
+                }
+                const sre_ls_agg_t *psums = with_sums ? sc->d_psums : NULL;
+                SRE_HIP_TRY(sre_launch_tally_top_first(tab, sc->d_tslot, cnt, n, nkeys, sc->d_pfirst, stream));
+                /* the order value and the class of every key, and the totals: the one read that fixes the sort keys */
+                SRE_HIP_TRY(sre_launch_tally_top_values(sc->d_pcount, psums, nkeys, v, by, (uint32_t) by_col, sc->d_jkey, sc->d_sclass,
+                                                        &sc->d_linfo->skeyed, stream));
+                SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(skeyed), LINFO(snumbered), LINFO(svmin), LINFO(svmax)}));
+                SRE_HIP_TRY(hipStreamSynchronize(stream));
+                nordered = sc->h_linfo->snumbered;
+                const int64_t vmin = (int64_t) sc->h_linfo->svmin, vmax = (int64_t) sc->h_linfo->svmax;
+                if (sc->h_linfo->skeyed != nkeys || nordered > nkeys || (nordered != 0 && vmin > vmax)) return -1;   /* (cannot happen) */
+                if (!sre_ltt_range_ok(nordered, vmin, vmax)) {
+                    fprintf(stderr, "[sregex-hip] ordered tally: the order values span %lld .. %lld, more than 2^64 - 3\n",
+                            (long long) vmin, (long long) vmax);
+                    return -1;
+                }
+                const uint32_t passes = sre_ltt_passes(nkeys, nordered, vmin, vmax);
+                uint32_t       cur = 0;
+                /* the sort's passes over the keys: pass 0 makes the items (every key is selected), the later ones move them */
+                SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, nkeys, vmin, vmax, nordered, desc, 1, 0, sc->d_rcnt, stream));
+                SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+                SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, nkeys, vmin, vmax, nordered, desc, 1, 0, sc->d_rcnt,
+                                                    nkeys, sc->d_kitem[0], sc->d_sline[0], stream));
+                for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
+                    SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nkeys, vmin, vmax, nordered, desc, 1, p, sc->d_rcnt, stream));
+                    SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+                    SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nkeys, vmin, vmax, nordered, desc, 1,
+                                                        p, sc->d_rcnt, nkeys, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
+                }
+                const uint32_t *keys = sc->d_sline[cur];
+                /* the ordered table of the rows in front of the limit (its source is the entry table: d_fval, d_fstart), the
+                 * extract's scan and cut over it, and the one read of the result words */
+                SRE_HIP_TRY(sre_launch_tally_top_table(keys, sc->d_pfirst, sc->d_fval, sc->d_fstart, nrows, nkeys, n, k, sc->d_pstart,
+                                                       sc->d_rval, stream));
+                SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_rval, nrows, k, sc->d_fblk, out_cap, sc->d_linfo, stream));
+                SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(fsel), LINFO(fneed), LINFO(fwritten), LINFO(fbytes)}));
+                SRE_HIP_TRY(hipStreamSynchronize(stream));
+                nwritten = sc->h_linfo->fwritten;
+                out_bytes = sc->h_linfo->fbytes;
+                if (sc->h_linfo->fsel != nrows || nwritten > nrows || out_bytes > out_cap) return -1;        /* (cannot happen) */
+                res.need_bytes = (size_t) sc->h_linfo->fneed;
+                res.passes = passes;
+                res.vmin = vmin;
+                res.vmax = vmax;
+                SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_pstart, nrows * k, out_bytes, (uint32_t) delim,
+                                                      (uint32_t) fsep, stream));
+                /* counts, aggregates and index rows in output order, the inverse permutation, then the ranks of the lines */
+                const uint64_t counts_rows = counts_cap < nrows ? counts_cap : nrows, sums_rows = sums_cap < nrows ? sums_cap : nrows;
+                const uint64_t index_rows = index_cap < nwritten ? index_cap : nwritten;
+                SRE_HIP_TRY(sre_launch_tally_top_permute(keys, nkeys, nrows, sc->d_pcount, psums, v, sc->d_pfirst, sc->d_ends, n, sc->d_pstart,
+                                                         sc->d_rval, k, sc->d_jkey, sc->d_sclass, d_counts, counts_rows, d_sums, sums_rows,
+                                                         reinterpret_cast<int64_t *>(d_index), index_rows, sc->d_pinv, stream));
+            }
+            SRE_HIP_TRY(sre_launch_tally_top_ranks(sc->d_tslot, cnt, sc->d_pinv, rank_cap < n ? rank_cap : n, nkeys,
+                                                   reinterpret_cast<int64_t *>(d_rank), stream));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            res.nkeys = (size_t) nkeys;
+            res.nordered = (size_t) nordered;
+            res.nrows = (size_t) nrows;
+            res.nwritten = (size_t) nwritten;
+            res.out_bytes = (size_t) out_bytes;
+        }
+    }
+    if (info) *info = res;
+    return rc;
 hip_failed:
     return -1;
 }

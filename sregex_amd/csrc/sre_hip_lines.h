@@ -322,6 +322,33 @@ hipError_t sre_launch_sort_finish(const uint64_t *d_coff, uint64_t nout, uint64_
 hipError_t sre_launch_sort_index(const uint32_t *d_lines, const uint64_t *d_cstart, const uint64_t *d_coff, const uint64_t *d_res,
     const int64_t *d_value, const int8_t *d_class, uint64_t nlines, uint64_t nrows, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
+/* ---- the ordered tally (sre_hip_lines_tally_top.hip, sre_lines_tally_top.h) ---- */
+/* behind the tally's ranks (d_cnt[slot] is the key's number), a lane per line: d_first[key] = the line the keep pass left
+ * selected for the key, the one line i with d_tab[d_lslot[i]] == i; nkeys words */
+hipError_t sre_launch_tally_top_first(const uint64_t *d_tab, const uint32_t *d_lslot, const uint64_t *d_cnt, uint64_t n,
+    uint64_t nkeys, uint64_t *d_first, hipStream_t stream);
+/* a lane per key: d_value[k] and d_class[k] (SRE_LSO_NUMBER ordered, SRE_LSO_TEXT not) of sre_ltt_order from d_counts[k] and
+ * the aggregate d_sums[k * v + by_col] (sre_ls_agg_t; not read for SRE_LTT_COUNT, may be NULL then); d_totals[0 .. 4) = the
+ * keys, the ordered keys, the minimum and the maximum of their values (set to 0, 0, INT64_MAX, INT64_MIN first), at most one
+ * add per count, one minimum and one maximum per workgroup of 1024 keys */
+hipError_t sre_launch_tally_top_values(const uint64_t *d_counts, const void *d_sums, uint64_t nkeys, uint32_t v, int by,
+    uint32_t by_col, int64_t *d_value, int8_t *d_class, uint64_t *d_totals, hipStream_t stream);
+/* behind the last digit pass (d_keys[r]: the key at rank r), a lane per entry of the first nrows ranks: entries r * k + f of the
+ * ordered table d_cstart / d_cval (nrows * k words; d_cval one more for its scan) from the entries d_first[key] * k + f of the
+ * scanned entry table d_off / d_start (n * k entries), which the ordered table may not overlap */
+hipError_t sre_launch_tally_top_table(const uint32_t *d_keys, const uint64_t *d_first, const uint64_t *d_off, const uint64_t *d_start,
+    uint64_t nrows, uint64_t nkeys, uint64_t n, uint32_t k, uint64_t *d_cstart, uint64_t *d_cval, hipStream_t stream);
+/* a lane per rank r < nkeys, key = d_keys[r]: d_inv[key] = r; d_ocounts[r] = d_counts[key] for r < counts_rows; the v
+ * aggregates of the key to d_osums[r * v ..] for r < sums_rows; the index row of sre_ltt_index_row (sre_ltt_index_words(k)
+ * words) for r < index_rows, from the scanned ordered table d_cstart / d_coff.  The three row counts are at most nrows, the
+ * rows of the ordered table */
+hipError_t sre_launch_tally_top_permute(const uint32_t *d_keys, uint64_t nkeys, uint64_t nrows, const uint64_t *d_counts,
+    const void *d_sums, uint32_t v, const uint64_t *d_first, const uint64_t *d_ends, uint64_t n, const uint64_t *d_cstart,
+    const uint64_t *d_coff, uint32_t k, const int64_t *d_value, const int8_t *d_class, uint64_t *d_ocounts, uint64_t counts_rows,
+    void *d_osums, uint64_t sums_rows, int64_t *d_index, uint64_t index_rows, uint32_t *d_inv, hipStream_t stream);
+/* behind it, a lane per line i < m: d_rank[i] = d_inv[d_cnt[d_lslot[i]]], -1 for a line without a slot */
+hipError_t sre_launch_tally_top_ranks(const uint32_t *d_lslot, const uint64_t *d_cnt, const uint32_t *d_inv, uint64_t m,
+    uint64_t nkeys, int64_t *d_rank, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif
