@@ -171,12 +171,13 @@ struct sre_hip_scanner_s {
     int32_t                  *h_rmap;           /* the map the device holds, so that a repeated map uploads nothing */
     bool                      rmap_valid;
     uint64_t                 *d_rres, *h_rres;  /* the words the host reads: SRE_LR_RES_WORDS + 2 x SRE_LR_MAX_BUCKETS */
-    /* the line tally (sre_hip_tally_lines): the entry table is the extract's (d_fval, d_fstart, d_fblk); it adds */
-    uint64_t                 *d_ttab;           /* the table of keys: nslots words of line numbers, then nslots counts */
+    /* the tallies (sre_hip_tally_lines, _sums_lines, _top_lines; tally_front): the entry table is the extract's (d_fval, d_fstart,
+     * d_fblk); they add */
+    uint64_t                 *d_ttab;           /* the table of keys: nslots words of line numbers, then nslots counts or key numbers */
     size_t                    ttab_cap;
     uint32_t                 *d_tslot;          /* the slot of every line */
     size_t                    tslot_cap;
-    /* the tally's sums (sre_hip_tally_sums_lines) add a second entry table over the value groups: lines x columns words each */
+    /* with value groups they add a second entry table over those: lines x columns words each */
     uint64_t                 *d_vval;
     size_t                    vval_cap;
     uint64_t                 *d_vstart;
@@ -193,15 +194,16 @@ struct sre_hip_scanner_s {
     uint64_t                 *d_kitem[2];       /* the items of the partition, pass by pass from one to the other: selected lines
                                                    + 1 words each (the spare one ends as the scan of the head flags) */
     size_t                    kitem_cap[2];
-    /* the line sort (sre_hip_sort_lines): the value table is the lookup's key table (d_vval, d_vstart), the per-line values
-     * d_jkey's words, the keys of the items d_kitem's, the counts of a pass d_rcnt's, the compact table the route's (d_fstart,
-     * d_rval), the scans' sums d_fblk's, the result words d_rres's; it adds */
-    int8_t                   *d_sclass;         /* the class of every line */
+    /* the line sort (sre_hip_sort_lines): the value table is the lookup's key table (d_vval, d_vstart), the compact table the
+     * route's (d_fstart, d_rval), the result words d_rres's.  Its items are also the ordered tally's, over keys in the place of
+     * lines (sort_passes): the values d_jkey's words, the keys d_kitem's, the counts of a pass d_rcnt's, the scans' sums
+     * d_fblk's; it adds */
+    int8_t                   *d_sclass;         /* the class of every item */
     size_t                    sclass_cap;
-    uint32_t                 *d_sline[2];       /* the lines of the items, moved with their keys: selected lines words each */
+    uint32_t                 *d_sline[2];       /* the lines of the items, moved with their keys: selected items words each */
     size_t                    sline_cap[2];
-    /* the ordered tally (sre_hip_tally_top_lines): the tally's tables as they are, the sort's values, classes, items and counts
-     * over the keys (d_jkey, d_sclass, d_kitem, d_sline, d_rcnt), the ordered table's values d_rval's words; it adds */
+    /* the ordered tally (sre_hip_tally_top_lines): the tallies' tables and the sort's items as they are (d_rcnt and d_fblk sized
+     * for the passes in front of the entry table's scan), the ordered table's values d_rval's words; it adds */
     uint64_t                 *d_pcount;         /* the count of every key, in first-appearance order */
     size_t                    pcount_cap;
     sre_ls_agg_t             *d_psums;          /* ... and its aggregates: keys x columns */
@@ -2515,6 +2517,72 @@ tally_sum_copies(uint64_t rows, uint32_t v)
     return most < 1 ? 1 : (uint32_t) most < copies ? (uint32_t) most : copies;
 }
 
+/* what the tallies (tally_call, sre_hip_tally_top_lines) know of a call: the sink with its key and value groups, the lines of
+ * the buffer and, behind tally_front, the table of keys and the key number of every slot (the halves of d_ttab) */
+struct TallyCall {
+    LinesSink            sink;
+    sre_extract_groups_t gr, vg;
+    uint64_t             n, *tab, *cnt;
+};
+
+/* The tallies open alike: the arguments they share checked (`known`: the flags the caller has, of which the sink sees
+ * SRE_HIP_LINES_ALL), the entry table over the key groups and, with value groups, the value table; then the line-mode call */
+static int
+tally_open(sre_hip_scanner_t *sc, const char *call, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups,
+           const int *vgroups, size_t nvgroups, int fsep, int flags, int known, size_t max_keys, void *d_out, size_t out_cap,
+           const uint64_t *d_counts, size_t counts_cap, sre_int_t *d_index, size_t index_cap, TallyCall *t, hipStream_t stream)
+{
+    uint64_t nrep = 0;
+    if (fsep < 0 || fsep > 255 || (flags & ~known) != 0 || groups == NULL || ngroups < 1 || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS
+        || (counts_cap != 0 && d_counts == NULL) || max_keys < 1 || max_keys > SRE_LT_MAX_KEYS
+        || !sink_open(&t->sink, sc, d_buf, len, delim, flags & SRE_HIP_LINES_ALL, d_out, out_cap, d_index, index_cap)
+        || !sink_first_match(sc, call, "captures") || !sink_groups(sc, groups, ngroups, &t->gr)
+        || !sink_groups(sc, vgroups, nvgroups, &t->vg))
+    {
+        return -1;
+    }
+    t->sink.groups = &t->gr;
+    t->sink.fsep = fsep;
+    if (vgroups) t->sink.vgroups = &t->vg;
+    return lines_call(sc, d_buf, len, delim, 0, NULL, 0, &t->sink, &t->n, &nrep, stream);
+}
+
+/* Behind the line-mode call (t->n != 0): the table grown and cleared, the insert of every selected line and the keep pass
+ * that leaves the first line of every key selected, the extract's scan with the cut at `cut` bytes and the one read (its
+ * four words and the tally's three) into res.  0, SRE_HIP_TALLY_OVERFLOW (nothing is to be written) or -1 */
+template <class Info>
+static int
+tally_front(sre_hip_scanner_t *sc, TallyCall *t, const void *d_buf, size_t max_keys, size_t cut, Info *res, hipStream_t stream)
+{
+    const uint64_t n = t->n, nslots = sre_lt_nslots(max_keys);
+    LinesSink      whole = t->sink;
+    whole.out_cap = cut;
+    if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
+    if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
+    t->tab = sc->d_ttab;
+    t->cnt = sc->d_ttab + nslots;
+    SRE_HIP_TRY(hipMemsetAsync(t->tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
+    SRE_HIP_TRY(hipMemsetAsync(t->cnt, 0, nslots * sizeof(uint64_t), stream));
+    static_assert(offsetof(sre_lines_info_t, tclaims) == offsetof(sre_lines_info_t, tsel) + sizeof(uint64_t)
+                      && offsetof(sre_lines_info_t, tover) == offsetof(sre_lines_info_t, tsel) + 2 * sizeof(uint64_t),
+                  "tsel, tclaims, tover are zeroed as one run");
+    SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
+    SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, t->gr.k, nslots, max_keys, tally_hash_mask(), t->tab, t->cnt,
+                                        sc->d_tslot, sc->d_linfo, stream));
+    if (sink_offsets(sc, &whole, n, stream) != 0) return -1;
+    if (sink_read(sc, &whole, n, res, stream, LINFO(tsel), LINFO(tclaims), LINFO(tover)) != 0) return -1;
+    /* the table selected the first line of every key: what the scan counted are the keys */
+    res->nkeys = res->nselected;
+    res->nselected = (size_t) sc->h_linfo->tsel;
+    if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
+        res->nkeys = res->need_bytes = res->nwritten = res->out_bytes = 0;      /* (only the two counts of lines stand) */
+        return SRE_HIP_TALLY_OVERFLOW;
+    }
+    return res->nkeys == sc->h_linfo->tclaims ? 0 : -1;     /* (-1 cannot happen) */
+hip_failed:
+    return -1;
+}
+
 /* The line tally: the extract's call up to its select passes, then on the device the insert of every
  * selected line into the table of keys and the keep pass that leaves the first line of every key selected, then the
  * extract's scan, cut, one read (its four words and the tally's three), gather and index, and the ranks.
@@ -2526,69 +2594,34 @@ tally_call(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, cons
     sre_hip_tally_sum_t *d_sums, size_t sums_cap, sre_int_t *d_keyid, size_t keyid_cap, sre_int_t *d_index, size_t index_cap,
     sre_hip_tally_info_t *info, void *hip_stream)
 {
-    LinesSink            sink;
-    sre_extract_groups_t gr, vg;
-    if (fsep < 0 || fsep > 255 || (flags & ~SRE_HIP_LINES_ALL) != 0 || groups == NULL || ngroups < 1
-        || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (counts_cap != 0 && d_counts == NULL) || (keyid_cap != 0 && d_keyid == NULL)
-        || max_keys < 1 || max_keys > SRE_LT_MAX_KEYS)
-    {
-        return -1;
-    }
-    if (!sink_open(&sink, sc, d_buf, len, delim, flags, d_out, out_cap, d_index, index_cap)) return -1;
-    if (!sink_first_match(sc, "line tally", "captures") || !sink_groups(sc, groups, ngroups, &gr)
-        || !sink_groups(sc, vgroups, nvgroups, &vg))
-    {
-        return -1;
-    }
-    sink.groups = &gr;
-    sink.fsep = fsep;
-    if (vgroups) sink.vgroups = &vg;
+    TallyCall   t;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    if ((keyid_cap != 0 && d_keyid == NULL)
+        || tally_open(sc, "line tally", d_buf, len, delim, groups, ngroups, vgroups, nvgroups, fsep, flags, SRE_HIP_LINES_ALL, max_keys,
+                      d_out, out_cap, d_counts, counts_cap, d_index, index_cap, &t, stream) != 0)
+    {
+        return -1;
+    }
     sre_hip_tally_info_t res;
     memset(&res, 0, sizeof(res));
-    int rc = 0;
-    if (n != 0) {
-        const uint64_t nslots = sre_lt_nslots(max_keys);
-        if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
-        if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
-        uint64_t *const tab = sc->d_ttab, *const cnt = sc->d_ttab + nslots;
-        SRE_HIP_TRY(hipMemsetAsync(tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
-        SRE_HIP_TRY(hipMemsetAsync(cnt, 0, nslots * sizeof(uint64_t), stream));
-        static_assert(offsetof(sre_lines_info_t, tclaims) == offsetof(sre_lines_info_t, tsel) + sizeof(uint64_t)
-                          && offsetof(sre_lines_info_t, tover) == offsetof(sre_lines_info_t, tsel) + 2 * sizeof(uint64_t),
-                      "tsel, tclaims, tover are zeroed as one run");
-        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
-        SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, gr.k, nslots, max_keys, tally_hash_mask(), tab, cnt,
-                                            sc->d_tslot, sc->d_linfo, stream));
-        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
-        if (sink_read(sc, &sink, n, &res, stream, LINFO(tsel), LINFO(tclaims), LINFO(tover)) != 0) return -1;
-        if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
-            memset(&res, 0, sizeof(res));       /* (nothing is written: only the two counts of lines stand) */
-            rc = SRE_HIP_TALLY_OVERFLOW;
-        } else {
-            /* the table selected the first line of every key: what the scan counted are the keys */
-            res.nkeys = res.nselected;
-            if (res.nkeys != sc->h_linfo->tclaims) return -1;    /* (cannot happen) */
-            if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
-            SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, gr.k, sc->d_fblk, sc->d_tslot, cnt, d_counts, counts_cap,
-                                               reinterpret_cast<int64_t *>(d_keyid), keyid_cap, stream));
-            if (vgroups && sums_cap != 0) {
-                /* (without counts and key ids the ranks above launched nothing: the key numbers are still needed) */
-                if (counts_cap == 0 && keyid_cap == 0) {
-                    SRE_HIP_TRY(sre_launch_tally_numbers(sc->d_fval, sc->d_fstart, n, gr.k, sc->d_fblk, sc->d_tslot, cnt, stream));
-                }
-                const uint64_t rows = sums_cap < res.nkeys ? sums_cap : res.nkeys;
-                const uint32_t copies = tally_sum_copies(rows, vg.k);
-                if (copies > 1 && lines_grow(&sc->d_vcopy, &sc->vcopy_cap, copies * rows * vg.k * sizeof(sre_ls_agg_t)) != 0) return -1;
-                SRE_HIP_TRY(sre_launch_tally_sums(d_buf, sc->d_vval, sc->d_vstart, n, vg.k, sc->d_tslot, cnt, rows, d_sums,
-                                                  sc->d_vcopy, copies, stream));
+    const int rc = t.n != 0 ? tally_front(sc, &t, d_buf, max_keys, out_cap, &res, stream) : 0;
+    if (rc < 0) return -1;
+    if (t.n != 0 && rc == 0) {
+        if (sink_write(sc, &t.sink, d_buf, t.n, res.out_bytes, res.nwritten, stream) != 0) return -1;
+        SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, t.n, t.gr.k, sc->d_fblk, sc->d_tslot, t.cnt, d_counts, counts_cap,
+                                           reinterpret_cast<int64_t *>(d_keyid), keyid_cap, stream));
+        if (vgroups && sums_cap != 0) {
+            /* (without counts and key ids the ranks above launched nothing: the key numbers are still needed) */
+            if (counts_cap == 0 && keyid_cap == 0) {
+                SRE_HIP_TRY(sre_launch_tally_numbers(sc->d_fval, sc->d_fstart, t.n, t.gr.k, sc->d_fblk, sc->d_tslot, t.cnt, stream));
             }
-            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            const uint64_t rows = sums_cap < res.nkeys ? sums_cap : res.nkeys;
+            const uint32_t copies = tally_sum_copies(rows, t.vg.k);
+            if (copies > 1 && lines_grow(&sc->d_vcopy, &sc->vcopy_cap, copies * rows * t.vg.k * sizeof(sre_ls_agg_t)) != 0) return -1;
+            SRE_HIP_TRY(sre_launch_tally_sums(d_buf, sc->d_vval, sc->d_vstart, t.n, t.vg.k, sc->d_tslot, t.cnt, rows, d_sums,
+                                              sc->d_vcopy, copies, stream));
         }
-        res.nlines = (size_t) n;
-        res.nselected = (size_t) sc->h_linfo->tsel;
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
     if (info) *info = res;
     return rc;
@@ -3189,6 +3222,35 @@ hip_failed:
     return -1;
 }
 
+/* The digit passes of the sort and of the ordered tally, queued behind the read of the totals of the values pass (vmin, vmax,
+ * nnum; compact_reserve has the counts of a pass): the item arrays of the nsel items selected (at least one); pass 0 over the n
+ * values and classes (d_jkey, d_sclass) makes the items and drops the unselected, the later passes move them from one pair of
+ * arrays to the other.  Returns the pair that holds the sorted items, -1 on failure */
+static int
+sort_passes(sre_hip_scanner_t *sc, uint64_t n, uint64_t nsel, int64_t vmin, int64_t vmax, uint64_t nnum, int desc, int all,
+            uint32_t passes, hipStream_t stream)
+{
+    const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS, per = SRE_LINES_ITEMS;
+    uint32_t       cur = 0;
+    for (int h = 0; h < 2; h++) {
+        if (lines_grow(&sc->d_kitem[h], &sc->kitem_cap[h], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_sline[h], &sc->sline_cap[h], nsel * sizeof(uint32_t)) != 0) return -1;
+    }
+    SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt, stream));
+    SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, nd * ((n + per - 1) / per), sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+    SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt, nsel,
+                                        sc->d_kitem[0], sc->d_sline[0], stream));
+    for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
+        SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nsel, vmin, vmax, nnum, desc, all, p, sc->d_rcnt, stream));
+        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, nd * ((nsel + per - 1) / per), sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+        SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nsel, vmin, vmax, nnum, desc, all, p,
+                                            sc->d_rcnt, nsel, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
+    }
+    return (int) cur;
+hip_failed:
+    return -1;
+}
+
 /* The line sort: the lookup's call with the one sort group as its value group; then the values pass,
  * which leaves the value and the class of every line and the four totals; one read of those, which sizes the item arrays and
  * fixes the keys and the number of passes; then one count / scan / scatter per digit of the key, the compact table of the
@@ -3218,13 +3280,12 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
     }
     if (n != 0) {
         const int      all = (flags & SRE_HIP_LINES_ALL) != 0, desc = (flags & SRE_HIP_SORT_DESC) != 0;
-        const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS, nwg = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS, ncnt = nd * nwg;
         uint64_t       nrows = 0;
         static_assert(offsetof(sre_lines_info_t, snumbered) == offsetof(sre_lines_info_t, skeyed) + sizeof(uint64_t)
                           && offsetof(sre_lines_info_t, svmin) == offsetof(sre_lines_info_t, skeyed) + 2 * sizeof(uint64_t)
                           && offsetof(sre_lines_info_t, svmax) == offsetof(sre_lines_info_t, skeyed) + 3 * sizeof(uint64_t),
                       "skeyed, snumbered, svmin, svmax are the four totals of the values pass, in that order");
-        if (compact_reserve(sc, n, nd) != 0) return -1;
+        if (compact_reserve(sc, n, (uint64_t) 1 << SRE_LSO_DIGIT_BITS) != 0) return -1;
         if (lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) return -1;
         if (lines_grow(&sc->d_sclass, &sc->sclass_cap, n * sizeof(int8_t)) != 0) return -1;
         /* the value and the class of every line, and the totals: the one read that sizes everything behind it */
@@ -3234,31 +3295,14 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
         const uint64_t nkeyed = sc->h_linfo->skeyed, nnum = sc->h_linfo->snumbered;
         const int64_t  vmin = (int64_t) sc->h_linfo->svmin, vmax = (int64_t) sc->h_linfo->svmax;
         if (nnum > nkeyed || nkeyed > n || (nnum != 0 && vmin > vmax)) return -1;        /* (cannot happen) */
-        const uint64_t range = sre_lso_range(nnum, vmin, vmax), nsel = sre_lso_selected(n, nnum, all);
-        const uint64_t nout = sre_lso_limited(nsel, limit);
-        const uint32_t passes = sre_lso_passes(n, nnum, range, all);
+        const uint64_t nsel = sre_lso_selected(n, nnum, all), nout = sre_lso_limited(nsel, limit);
+        const uint32_t passes = sre_lso_passes(n, nnum, sre_lso_range(nnum, vmin, vmax), all);
         const uint32_t *lines = NULL;
         if (nsel != 0) {
-            uint32_t cur = 0;
-            if (lines_grow(&sc->d_kitem[0], &sc->kitem_cap[0], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
-            if (lines_grow(&sc->d_kitem[1], &sc->kitem_cap[1], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
-            if (lines_grow(&sc->d_sline[0], &sc->sline_cap[0], nsel * sizeof(uint32_t)) != 0) return -1;
-            if (lines_grow(&sc->d_sline[1], &sc->sline_cap[1], nsel * sizeof(uint32_t)) != 0) return -1;
             if (lines_grow(&sc->d_fstart, &sc->fstart_cap, nout * sizeof(uint64_t)) != 0) return -1;
             if (lines_grow(&sc->d_rval, &sc->rval_cap, (nout + 1) * sizeof(uint64_t)) != 0) return -1;
-            /* pass 0 over the lines makes the items and drops the unselected */
-            SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt, stream));
-            SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, ncnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
-            SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt,
-                                                nsel, sc->d_kitem[0], sc->d_sline[0], stream));
-            /* the later passes over the nsel items, from one pair of arrays to the other */
-            for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
-                const uint64_t pcnt = nd * ((nsel + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
-                SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nsel, vmin, vmax, nnum, desc, all, p, sc->d_rcnt, stream));
-                SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
-                SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nsel, vmin, vmax, nnum, desc, all, p,
-                                                    sc->d_rcnt, nsel, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
-            }
+            const int cur = sort_passes(sc, n, nsel, vmin, vmax, nnum, desc, all, passes, stream);
+            if (cur < 0) return -1;
             /* the compact table of the rows in front of the limit; its scan leaves the words of d_linfo as the cut at out_cap
              * gives them */
             lines = sc->d_sline[cur];
@@ -3298,150 +3342,102 @@ sre_hip_tally_top_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, in
     static_assert(SRE_HIP_TOP_COUNT == SRE_LTT_COUNT && SRE_HIP_TOP_SUM == SRE_LTT_SUM && SRE_HIP_TOP_MIN == SRE_LTT_MIN
                       && SRE_HIP_TOP_MAX == SRE_LTT_MAX && SRE_HIP_TOP_N == SRE_LTT_N,
                   "sre_lines_tally_top.h mirrors the public enum");
-    LinesSink            sink;
-    sre_extract_groups_t gr, vg;
-    if (fsep < 0 || fsep > 255 || (flags & ~(SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC)) != 0 || groups == NULL || ngroups < 1
-        || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (counts_cap != 0 && d_counts == NULL) || (sums_cap != 0 && d_sums == NULL)
-        || (rank_cap != 0 && d_rank == NULL) || (reinterpret_cast<uintptr_t>(d_sums) & 7u) != 0 || max_keys < 1
-        || max_keys > SRE_LT_MAX_KEYS || nvgroups > SRE_HIP_TALLY_MAX_VALUES || (vgroups == NULL) != (nvgroups == 0)
-        || (nvgroups == 0 && sums_cap != 0) || !sre_ltt_by_ok(by, by_col, nvgroups))
-    {
-        return -1;
-    }
-    if (!sink_open(&sink, sc, d_buf, len, delim, flags & SRE_HIP_LINES_ALL, d_out, out_cap, d_index, index_cap)) return -1;
-    if (!sink_first_match(sc, "ordered tally", "captures") || !sink_groups(sc, groups, ngroups, &gr)
-        || !sink_groups(sc, vgroups, nvgroups, &vg))
-    {
-        return -1;
-    }
-    sink.groups = &gr;
-    sink.fsep = fsep;
-    if (vgroups) sink.vgroups = &vg;
+    TallyCall   t;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    uint64_t    n = 0, nrep = 0;
-    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    if ((sums_cap != 0 && d_sums == NULL) || (rank_cap != 0 && d_rank == NULL) || (reinterpret_cast<uintptr_t>(d_sums) & 7u) != 0
+        || nvgroups > SRE_HIP_TALLY_MAX_VALUES || (vgroups == NULL) != (nvgroups == 0) || (nvgroups == 0 && sums_cap != 0)
+        || !sre_ltt_by_ok(by, by_col, nvgroups)
+        || tally_open(sc, "ordered tally", d_buf, len, delim, groups, ngroups, vgroups, nvgroups, fsep, flags,
+                      SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC, max_keys, d_out, out_cap, d_counts, counts_cap, d_index, index_cap, &t,
+                      stream) != 0)
+    {
+        return -1;
+    }
     sre_hip_tally_top_info_t res;
     memset(&res, 0, sizeof(res));
     res.vmin = INT64_MAX;
     res.vmax = INT64_MIN;
-    int rc = 0;
-    if (n != 0) {
-        const int      desc = (flags & SRE_HIP_SORT_DESC) != 0;
-        const uint32_t k = gr.k, v = (uint32_t) nvgroups;
-        const uint64_t nslots = sre_lt_nslots(max_keys);
-        if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
-        if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
-        uint64_t *const tab = sc->d_ttab, *const cnt = sc->d_ttab + nslots;
-        SRE_HIP_TRY(hipMemsetAsync(tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
-        SRE_HIP_TRY(hipMemsetAsync(cnt, 0, nslots * sizeof(uint64_t), stream));
-        SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
-        SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, k, nslots, max_keys, tally_hash_mask(), tab, cnt,
-                                            sc->d_tslot, sc->d_linfo, stream));
-        /* the scan of the entry table without a cut: its rows are the source of the ordered table */
-        LinesSink            whole = sink;
-        sre_hip_tally_info_t first;
-        memset(&first, 0, sizeof(first));
-        whole.out_cap = ~(size_t) 0;
-        if (sink_offsets(sc, &whole, n, stream) != 0) return -1;
-        if (sink_read(sc, &whole, n, &first, stream, LINFO(tsel), LINFO(tclaims), LINFO(tover)) != 0) return -1;
-        res.nlines = (size_t) n;
-        res.nselected = (size_t) sc->h_linfo->tsel;
-        if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
-            rc = SRE_HIP_TALLY_OVERFLOW;        /* (nothing is written: only the two counts of lines stand) */
-        } else {
-            const uint64_t nkeys = first.nselected;
-            if (nkeys != sc->h_linfo->tclaims || nkeys > n) return -1;      /* (cannot happen) */
-            const uint64_t nrows = sre_ltt_rows(nkeys, limit);
-            uint64_t       nordered = 0, nwritten = 0, out_bytes = 0;
-            if (nkeys != 0) {
-                const bool     with_sums = v != 0 && (by != SRE_LTT_COUNT || sums_cap != 0);
-                const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS;
-                const uint64_t pcnt = nd * ((nkeys + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS);
-                /* (d_fblk holds the block sums of the scan above, which the ranks below read: nkeys <= n entries and the
-                 * counts of a pass over them need no more of it than that scan took, so it is not grown here) */
-                if (compact_reserve(sc, nkeys, nd) != 0) return -1;
-                if (lines_grow(&sc->d_pcount, &sc->pcount_cap, nkeys * sizeof(uint64_t)) != 0) return -1;
-                if (lines_grow(&sc->d_pfirst, &sc->pfirst_cap, nkeys * sizeof(uint64_t)) != 0) return -1;
-                if (lines_grow(&sc->d_pinv, &sc->pinv_cap, nkeys * sizeof(uint32_t)) != 0) return -1;
-                if (lines_grow(&sc->d_jkey, &sc->jkey_cap, nkeys * sizeof(int64_t)) != 0) return -1;
-                if (lines_grow(&sc->d_sclass, &sc->sclass_cap, nkeys * sizeof(int8_t)) != 0) return -1;
-                if (lines_grow(&sc->d_kitem[0], &sc->kitem_cap[0], (nkeys + 1) * sizeof(uint64_t)) != 0) return -1;
-                if (lines_grow(&sc->d_kitem[1], &sc->kitem_cap[1], (nkeys + 1) * sizeof(uint64_t)) != 0) return -1;
-                if (lines_grow(&sc->d_sline[0], &sc->sline_cap[0], nkeys * sizeof(uint32_t)) != 0) return -1;
-                if (lines_grow(&sc->d_sline[1], &sc->sline_cap[1], nkeys * sizeof(uint32_t)) != 0) return -1;
-                if (lines_grow(&sc->d_pstart, &sc->pstart_cap, nrows * k * sizeof(uint64_t)) != 0) return -1;
-                if (lines_grow(&sc->d_rval, &sc->rval_cap, (nrows * k + 1) * sizeof(uint64_t)) != 0) return -1;
-                if (with_sums && lines_grow(&sc->d_psums, &sc->psums_cap, nkeys * v * sizeof(sre_ls_agg_t)) != 0) return -1;
-                /* the tally's ranks and sums, into the scanner's arrays: d_pcount[key], d_psums[key], cnt[slot] = key */
-                SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, k, sc->d_fblk, sc->d_tslot, cnt, sc->d_pcount, nkeys, NULL,
-                                                   0, stream));
-                if (with_sums) {
-                    const uint32_t copies = tally_sum_copies(nkeys, v);
-                    if (copies > 1 && lines_grow(&sc->d_vcopy, &sc->vcopy_cap, copies * nkeys * v * sizeof(sre_ls_agg_t)) != 0) return -1;
-                    SRE_HIP_TRY(sre_launch_tally_sums(d_buf, sc->d_vval, sc->d_vstart, n, v, sc->d_tslot, cnt, nkeys, sc->d_psums,
-                                                      sc->d_vcopy, copies, stream));
-                }
-                const sre_ls_agg_t *psums = with_sums ? sc->d_psums : NULL;
-                SRE_HIP_TRY(sre_launch_tally_top_first(tab, sc->d_tslot, cnt, n, nkeys, sc->d_pfirst, stream));
-                /* the order value and the class of every key, and the totals: the one read that fixes the sort keys */
-                SRE_HIP_TRY(sre_launch_tally_top_values(sc->d_pcount, psums, nkeys, v, by, (uint32_t) by_col, sc->d_jkey, sc->d_sclass,
-                                                        &sc->d_linfo->skeyed, stream));
-                SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(skeyed), LINFO(snumbered), LINFO(svmin), LINFO(svmax)}));
-                SRE_HIP_TRY(hipStreamSynchronize(stream));
-                nordered = sc->h_linfo->snumbered;
-                const int64_t vmin = (int64_t) sc->h_linfo->svmin, vmax = (int64_t) sc->h_linfo->svmax;
-                if (sc->h_linfo->skeyed != nkeys || nordered > nkeys || (nordered != 0 && vmin > vmax)) return -1;   /* (cannot happen) */
-                if (!sre_ltt_range_ok(nordered, vmin, vmax)) {
-                    fprintf(stderr, "[sregex-hip] ordered tally: the order values span %lld .. %lld, more than 2^64 - 3\n",
-                            (long long) vmin, (long long) vmax);
-                    return -1;
-                }
-                const uint32_t passes = sre_ltt_passes(nkeys, nordered, vmin, vmax);
-                uint32_t       cur = 0;
-                /* the sort's passes over the keys: pass 0 makes the items (every key is selected), the later ones move them */
-                SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, nkeys, vmin, vmax, nordered, desc, 1, 0, sc->d_rcnt, stream));
-                SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
-                SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, nkeys, vmin, vmax, nordered, desc, 1, 0, sc->d_rcnt,
-                                                    nkeys, sc->d_kitem[0], sc->d_sline[0], stream));
-                for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
-                    SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nkeys, vmin, vmax, nordered, desc, 1, p, sc->d_rcnt, stream));
-                    SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, pcnt, sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
-                    SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nkeys, vmin, vmax, nordered, desc, 1,
-                                                        p, sc->d_rcnt, nkeys, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
-                }
-                const uint32_t *keys = sc->d_sline[cur];
-                /* the ordered table of the rows in front of the limit (its source is the entry table: d_fval, d_fstart), the
-                 * extract's scan and cut over it, and the one read of the result words */
-                SRE_HIP_TRY(sre_launch_tally_top_table(keys, sc->d_pfirst, sc->d_fval, sc->d_fstart, nrows, nkeys, n, k, sc->d_pstart,
-                                                       sc->d_rval, stream));
-                SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_rval, nrows, k, sc->d_fblk, out_cap, sc->d_linfo, stream));
-                SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(fsel), LINFO(fneed), LINFO(fwritten), LINFO(fbytes)}));
-                SRE_HIP_TRY(hipStreamSynchronize(stream));
-                nwritten = sc->h_linfo->fwritten;
-                out_bytes = sc->h_linfo->fbytes;
-                if (sc->h_linfo->fsel != nrows || nwritten > nrows || out_bytes > out_cap) return -1;        /* (cannot happen) */
-                res.need_bytes = (size_t) sc->h_linfo->fneed;
-                res.passes = passes;
-                res.vmin = vmin;
-                res.vmax = vmax;
-                SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_pstart, nrows * k, out_bytes, (uint32_t) delim,
-                                                      (uint32_t) fsep, stream));
-                /* counts, aggregates and index rows in output order, the inverse permutation, then the ranks of the lines */
-                const uint64_t counts_rows = counts_cap < nrows ? counts_cap : nrows, sums_rows = sums_cap < nrows ? sums_cap : nrows;
-                const uint64_t index_rows = index_cap < nwritten ? index_cap : nwritten;
-                SRE_HIP_TRY(sre_launch_tally_top_permute(keys, nkeys, nrows, sc->d_pcount, psums, v, sc->d_pfirst, sc->d_ends, n, sc->d_pstart,
-                                                         sc->d_rval, k, sc->d_jkey, sc->d_sclass, d_counts, counts_rows, d_sums, sums_rows,
-                                                         reinterpret_cast<int64_t *>(d_index), index_rows, sc->d_pinv, stream));
+    const uint32_t k = t.gr.k, v = (uint32_t) nvgroups;
+    const uint64_t n = t.n;
+    /* the counts and the scans' sums of the digit passes over the keys (at most n, at most max_keys) are reserved in front of
+     * the scan of the entry table: its block sums in d_fblk, which the ranks read, stay where they are */
+    if (n != 0 && compact_reserve(sc, n < max_keys ? n : max_keys, (uint64_t) 1 << SRE_LSO_DIGIT_BITS) != 0) return -1;
+    /* the scan of the entry table without a cut: its rows are the source of the ordered table */
+    const int rc = n != 0 ? tally_front(sc, &t, d_buf, max_keys, ~(size_t) 0, &res, stream) : 0;
+    if (rc < 0) return -1;
+    if (n != 0 && rc == 0) {
+        const uint64_t nkeys = res.nkeys;
+        if (nkeys > n) return -1;       /* (cannot happen) */
+        const uint64_t nrows = sre_ltt_rows(nkeys, limit);
+        res.nrows = (size_t) nrows;
+        res.need_bytes = res.nwritten = res.out_bytes = 0;      /* (the front's are those of the scan without a cut) */
+        if (nkeys != 0) {
+            const bool with_sums = v != 0 && (by != SRE_LTT_COUNT || sums_cap != 0);
+            if (lines_grow(&sc->d_pcount, &sc->pcount_cap, nkeys * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_pfirst, &sc->pfirst_cap, nkeys * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_pinv, &sc->pinv_cap, nkeys * sizeof(uint32_t)) != 0) return -1;
+            if (lines_grow(&sc->d_jkey, &sc->jkey_cap, nkeys * sizeof(int64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_sclass, &sc->sclass_cap, nkeys * sizeof(int8_t)) != 0) return -1;
+            if (lines_grow(&sc->d_pstart, &sc->pstart_cap, nrows * k * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_rval, &sc->rval_cap, (nrows * k + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (with_sums && lines_grow(&sc->d_psums, &sc->psums_cap, nkeys * v * sizeof(sre_ls_agg_t)) != 0) return -1;
+            /* the tally's ranks and sums, into the scanner's arrays: d_pcount[key], d_psums[key], cnt[slot] = key */
+            SRE_HIP_TRY(sre_launch_tally_ranks(sc->d_fval, sc->d_fstart, n, k, sc->d_fblk, sc->d_tslot, t.cnt, sc->d_pcount, nkeys, NULL,
+                                               0, stream));
+            if (with_sums) {
+                const uint32_t copies = tally_sum_copies(nkeys, v);
+                if (copies > 1 && lines_grow(&sc->d_vcopy, &sc->vcopy_cap, copies * nkeys * v * sizeof(sre_ls_agg_t)) != 0) return -1;
+                SRE_HIP_TRY(sre_launch_tally_sums(d_buf, sc->d_vval, sc->d_vstart, n, v, sc->d_tslot, t.cnt, nkeys, sc->d_psums,
+                                                  sc->d_vcopy, copies, stream));
             }
-            SRE_HIP_TRY(sre_launch_tally_top_ranks(sc->d_tslot, cnt, sc->d_pinv, rank_cap < n ? rank_cap : n, nkeys,
-                                                   reinterpret_cast<int64_t *>(d_rank), stream));
+            const sre_ls_agg_t *psums = with_sums ? sc->d_psums : NULL;
+            SRE_HIP_TRY(sre_launch_tally_top_first(t.tab, sc->d_tslot, t.cnt, n, nkeys, sc->d_pfirst, stream));
+            /* the order value and the class of every key, and the totals: the one read that fixes the sort keys */
+            SRE_HIP_TRY(sre_launch_tally_top_values(sc->d_pcount, psums, nkeys, v, by, (uint32_t) by_col, sc->d_jkey, sc->d_sclass,
+                                                    &sc->d_linfo->skeyed, stream));
+            SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(skeyed), LINFO(snumbered), LINFO(svmin), LINFO(svmax)}));
             SRE_HIP_TRY(hipStreamSynchronize(stream));
-            res.nkeys = (size_t) nkeys;
+            const uint64_t nordered = sc->h_linfo->snumbered;
+            const int64_t  vmin = (int64_t) sc->h_linfo->svmin, vmax = (int64_t) sc->h_linfo->svmax;
+            if (sc->h_linfo->skeyed != nkeys || nordered > nkeys || (nordered != 0 && vmin > vmax)) return -1;   /* (cannot happen) */
+            if (!sre_ltt_range_ok(nordered, vmin, vmax)) {
+                fprintf(stderr, "[sregex-hip] ordered tally: the order values span %lld .. %lld, more than 2^64 - 3\n",
+                        (long long) vmin, (long long) vmax);
+                return -1;
+            }
+            const uint32_t passes = sre_ltt_passes(nkeys, nordered, vmin, vmax);
+            /* the sort's passes over the keys: every key is selected */
+            const int cur = sort_passes(sc, nkeys, nkeys, vmin, vmax, nordered, (flags & SRE_HIP_SORT_DESC) != 0, 1, passes, stream);
+            if (cur < 0) return -1;
+            const uint32_t *keys = sc->d_sline[cur];
+            /* the ordered table of the rows in front of the limit (its source is the entry table: d_fval, d_fstart), the
+             * extract's scan and cut over it, and the one read of the result words */
+            SRE_HIP_TRY(sre_launch_tally_top_table(keys, sc->d_pfirst, sc->d_fval, sc->d_fstart, nrows, nkeys, n, k, sc->d_pstart,
+                                                   sc->d_rval, stream));
+            SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_rval, nrows, k, sc->d_fblk, out_cap, sc->d_linfo, stream));
+            SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(fsel), LINFO(fneed), LINFO(fwritten), LINFO(fbytes)}));
+            SRE_HIP_TRY(hipStreamSynchronize(stream));
+            const uint64_t nwritten = sc->h_linfo->fwritten, out_bytes = sc->h_linfo->fbytes;
+            if (sc->h_linfo->fsel != nrows || nwritten > nrows || out_bytes > out_cap) return -1;        /* (cannot happen) */
             res.nordered = (size_t) nordered;
-            res.nrows = (size_t) nrows;
+            res.need_bytes = (size_t) sc->h_linfo->fneed;
             res.nwritten = (size_t) nwritten;
             res.out_bytes = (size_t) out_bytes;
+            res.passes = passes;
+            res.vmin = vmin;
+            res.vmax = vmax;
+            SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_rval, sc->d_pstart, nrows * k, out_bytes, (uint32_t) delim,
+                                                  (uint32_t) fsep, stream));
+            /* counts, aggregates and index rows in output order, the inverse permutation, then the ranks of the lines */
+            const uint64_t counts_rows = counts_cap < nrows ? counts_cap : nrows, sums_rows = sums_cap < nrows ? sums_cap : nrows;
+            const uint64_t index_rows = index_cap < nwritten ? index_cap : nwritten;
+            SRE_HIP_TRY(sre_launch_tally_top_permute(keys, nkeys, nrows, sc->d_pcount, psums, v, sc->d_pfirst, sc->d_ends, n, sc->d_pstart,
+                                                     sc->d_rval, k, sc->d_jkey, sc->d_sclass, d_counts, counts_rows, d_sums, sums_rows,
+                                                     reinterpret_cast<int64_t *>(d_index), index_rows, sc->d_pinv, stream));
         }
+        SRE_HIP_TRY(sre_launch_tally_top_ranks(sc->d_tslot, t.cnt, sc->d_pinv, rank_cap < n ? rank_cap : n, nkeys,
+                                               reinterpret_cast<int64_t *>(d_rank), stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
     if (info) *info = res;
     return rc;

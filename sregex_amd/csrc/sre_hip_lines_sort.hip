@@ -4,8 +4,8 @@
  * extract's gather writes out.  The rules are those of sre_lines_sort.h, sre_lines_route_key.h and sre_lines_route.h, which
  * the CPU model compiles too.
  *
- *   values     a lane per line: the class and the value of the line from its entry of the value table, and the four totals
- *              of the call: at most one add per count, one minimum and one maximum per workgroup of 1024 lines;
+ *   values     the values pass of sre_hip_lines_values.h, a lane per line: the class and the value of the line from its entry
+ *              of the value table, and the four totals of the call;
  *   partition  per digit: the count and the scatter of sre_hip_lines_partition.h, the filter's scan between them; key and line
  *              of an item go to the same rank of the other pair of arrays.  Pass 0 makes the items from the values in line
  *              order and drops the unselected;
@@ -20,82 +20,21 @@
 #include "sre_hip_lines.h"
 #include "sre_lines_sort.h"
 #include "sre_hip_lines_partition.h"
-
-#define LSO_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+#include "sre_hip_lines_values.h"
 
 namespace {
 
-/* the value table of the one sort group as the values pass reads it (written by earlier kernels or copies: plain loads) */
+/* the value table of the one sort group as the values pass reads it (written by earlier kernels or copies: plain loads): the
+ * source of the values pass (sre_hip_lines_values.h), item i is line i */
 struct SortVals {
-    const uint8_t  *buf;
-    const uint64_t *vval, *vstart;
+    const uint8_t *__restrict__ buf;
+    const uint64_t *__restrict__ vval, *__restrict__ vstart;
+    uint64_t n;
     __device__ inline uint64_t val(uint64_t line, uint32_t) const { return vval[line]; }
     __device__ inline uint64_t raw(uint64_t line, uint32_t) const { return vstart[line]; }
     __device__ inline uint8_t  byte(uint64_t at) const { return buf[at]; }
+    __device__ inline int32_t  classify(uint64_t i, int64_t *v) const { return sre_lso_line(*this, i, v); }
 };
-
-/* the four words of the call: skeyed, snumbered, svmin, svmax of sre_lines_info_t, in that order */
-struct SortMem {
-    uint64_t *w;
-    __device__ inline void add_keyed(uint64_t v) { (void) __hip_atomic_fetch_add(w + 0, v, LSO_RELAXED_AGENT); }
-    __device__ inline void add_numbered(uint64_t v) { (void) __hip_atomic_fetch_add(w + 1, v, LSO_RELAXED_AGENT); }
-    __device__ inline void min(int64_t v) { (void) __hip_atomic_fetch_min(reinterpret_cast<int64_t *>(w + 2), v, LSO_RELAXED_AGENT); }
-    __device__ inline void max(int64_t v) { (void) __hip_atomic_fetch_max(reinterpret_cast<int64_t *>(w + 3), v, LSO_RELAXED_AGENT); }
-};
-
-/* every lane gets the merge of all 64 lanes' totals */
-__device__ inline sre_lso_totals_t
-wave_merge(sre_lso_totals_t t)
-{
-    for (int d = 1; d < 64; d <<= 1) {
-        sre_lso_totals_t o;
-        o.nkeyed = (uint64_t) __shfl_xor((unsigned long long) t.nkeyed, d, 64);
-        o.nnumbered = (uint64_t) __shfl_xor((unsigned long long) t.nnumbered, d, 64);
-        o.vmin = (int64_t) __shfl_xor((long long) t.vmin, d, 64);
-        o.vmax = (int64_t) __shfl_xor((long long) t.vmax, d, 64);
-        t = sre_lso_merge(t, o);
-    }
-    return t;
-}
-
-/* one lane, in front of the values pass: the identities of the four words */
-__global__ __launch_bounds__(64) void
-sre_k_sort_init(uint64_t *__restrict__ w)
-{
-    if (threadIdx.x != 0) return;
-    const sre_lso_totals_t t = sre_lso_identity();
-    w[0] = t.nkeyed;
-    w[1] = t.nnumbered;
-    w[2] = (uint64_t) t.vmin;
-    w[3] = (uint64_t) t.vmax;
-}
-
-/* workgroup w: the lines w * SRE_LSO_LINES + j * SRE_LSO_THREADS + lane, j = 0 .. SRE_LSO_PER_LANE - 1 */
-__global__ __launch_bounds__(SRE_LSO_THREADS) void
-sre_k_sort_values(const uint8_t *__restrict__ buf, const uint64_t *__restrict__ vval, const uint64_t *__restrict__ vstart, uint64_t n,
-                  int64_t *__restrict__ value, int8_t *__restrict__ cls, uint64_t *totals)
-{
-    __shared__ sre_lso_totals_t part[SRE_LSO_THREADS / 64u];
-    const SortVals   vals = {buf, vval, vstart};
-    sre_lso_totals_t t = sre_lso_identity();
-#pragma unroll
-    for (uint32_t j = 0; j < SRE_LSO_PER_LANE; j++) {
-        const uint64_t i = (uint64_t) blockIdx.x * SRE_LSO_LINES + j * SRE_LSO_THREADS + threadIdx.x;
-        if (i >= n) continue;
-        int64_t       v;
-        const int32_t c = sre_lso_line(vals, i, &v);
-        value[i] = v;
-        cls[i] = (int8_t) c;
-        t = sre_lso_merge(t, sre_lso_single(c, v));
-    }
-    t = wave_merge(t);
-    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (uint32_t w = 1; w < SRE_LSO_THREADS / 64u; w++) t = sre_lso_merge(t, part[w]);
-    SortMem mem = {totals};
-    sre_lso_flush(mem, t);
-}
 
 /* what every digit pass knows of the call */
 struct SortKeys {
@@ -187,12 +126,9 @@ extern "C" hipError_t
 sre_launch_sort_values(const void *d_buf, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n, int64_t *d_value,
                        int8_t *d_class, uint64_t *d_totals, hipStream_t stream)
 {
-    const uint64_t nwg = (n + SRE_LSO_LINES - 1) / SRE_LSO_LINES;
-    if (n == 0 || nwg > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sre_k_sort_init, dim3(1), dim3(64), 0, stream, d_totals);
-    hipLaunchKernelGGL(sre_k_sort_values, dim3((uint32_t) nwg), dim3(SRE_LSO_THREADS), 0, stream, static_cast<const uint8_t *>(d_buf),
-                       d_vval, d_vstart, n, d_value, d_class, d_totals);
-    return hipGetLastError();
+    if (n == 0) return hipErrorInvalidValue;
+    const SortVals src = {static_cast<const uint8_t *>(d_buf), d_vval, d_vstart, n};
+    return values_launch(src, d_value, d_class, d_totals, stream);
 }
 
 extern "C" hipError_t

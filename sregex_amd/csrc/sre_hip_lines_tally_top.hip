@@ -6,8 +6,8 @@
  *
  *   first      behind the tally's ranks, a lane per line: the line the keep pass left selected for a key is the key's
  *              first line, first[key number] = line;
- *   values     a lane per key: the order value and the class of the key, and the four totals of the call: at most one add
- *              per count, one minimum and one maximum per workgroup of 1024 keys;
+ *   values     the values pass of sre_hip_lines_values.h, a lane per key: the order value and the class of the key, and the
+ *              four totals of the call;
  *   (the sort's digit passes run over the keys unchanged: sre_hip_lines_sort.hip, all = 1, the "line" of an item is the
  *   key's number)
  *   table      a lane per entry of the rows in front of the limit: the entries of the key's first line, copied from the
@@ -23,8 +23,7 @@
 #include "sre_hip_lines.h"
 #include "sre_lines_tally_top.h"
 #include "sre_hip_lines_block.h"
-
-#define LTT_RELAXED_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+#include "sre_hip_lines_values.h"
 
 namespace {
 
@@ -41,69 +40,20 @@ sre_k_tally_top_first(const uint64_t *__restrict__ tab, const uint32_t *__restri
     if (key < nkeys) first[key] = i;        /* (always: the ranks numbered the kept lines 0 .. nkeys - 1) */
 }
 
-/* the four words of the call: skeyed, snumbered, svmin, svmax of sre_lines_info_t, in that order */
-struct TopMem {
-    uint64_t *w;
-    __device__ inline void add_keyed(uint64_t v) { (void) __hip_atomic_fetch_add(w + 0, v, LTT_RELAXED_AGENT); }
-    __device__ inline void add_numbered(uint64_t v) { (void) __hip_atomic_fetch_add(w + 1, v, LTT_RELAXED_AGENT); }
-    __device__ inline void min(int64_t v) { (void) __hip_atomic_fetch_min(reinterpret_cast<int64_t *>(w + 2), v, LTT_RELAXED_AGENT); }
-    __device__ inline void max(int64_t v) { (void) __hip_atomic_fetch_max(reinterpret_cast<int64_t *>(w + 3), v, LTT_RELAXED_AGENT); }
-};
-
-/* every lane gets the merge of all 64 lanes' totals */
-__device__ inline sre_lso_totals_t
-wave_merge(sre_lso_totals_t t)
-{
-    for (int d = 1; d < 64; d <<= 1) {
-        sre_lso_totals_t o;
-        o.nkeyed = (uint64_t) __shfl_xor((unsigned long long) t.nkeyed, d, 64);
-        o.nnumbered = (uint64_t) __shfl_xor((unsigned long long) t.nnumbered, d, 64);
-        o.vmin = (int64_t) __shfl_xor((long long) t.vmin, d, 64);
-        o.vmax = (int64_t) __shfl_xor((long long) t.vmax, d, 64);
-        t = sre_lso_merge(t, o);
-    }
-    return t;
-}
-
-/* one lane, in front of the values pass: the identities of the four words */
-__global__ __launch_bounds__(64) void
-sre_k_tally_top_init(uint64_t *__restrict__ w)
-{
-    if (threadIdx.x != 0) return;
-    const sre_lso_totals_t t = sre_lso_identity();
-    w[0] = t.nkeyed;
-    w[1] = t.nnumbered;
-    w[2] = (uint64_t) t.vmin;
-    w[3] = (uint64_t) t.vmax;
-}
-
-/* workgroup w: the keys w * SRE_LTT_KEYS + j * SRE_LTT_THREADS + lane, j = 0 .. SRE_LTT_PER_LANE - 1 */
-__global__ __launch_bounds__(SRE_LTT_THREADS) void
-sre_k_tally_top_values(const uint64_t *__restrict__ counts, const sre_ls_agg_t *__restrict__ sums, uint64_t nkeys, uint32_t v, int by,
-                       uint32_t by_col, int64_t *__restrict__ value, int8_t *__restrict__ cls, uint64_t *totals)
-{
-    __shared__ sre_lso_totals_t part[SRE_LTT_THREADS / 64u];
-    sre_lso_totals_t            t = sre_lso_identity();
-#pragma unroll
-    for (uint32_t j = 0; j < SRE_LTT_PER_LANE; j++) {
-        const uint64_t k = (uint64_t) blockIdx.x * SRE_LTT_KEYS + j * SRE_LTT_THREADS + threadIdx.x;
-        if (k >= nkeys) continue;
+/* the counts and the aggregates of the keys: the source of the values pass (sre_hip_lines_values.h), item i is key i */
+struct TopVals {
+    const uint64_t *__restrict__ counts;
+    const sre_ls_agg_t *__restrict__ sums;
+    uint64_t n;
+    uint32_t v, by_col;
+    int      by;
+    __device__ inline int32_t classify(uint64_t k, int64_t *x) const
+    {
         sre_ls_agg_t a = sre_ls_identity();
         if (by != SRE_LTT_COUNT) a = sums[k * v + by_col];
-        int64_t       x;
-        const int32_t c = sre_ltt_order(by, counts[k], &a, &x);
-        value[k] = x;
-        cls[k] = (int8_t) c;
-        t = sre_lso_merge(t, sre_lso_single(c, x));
+        return sre_ltt_order(by, counts[k], &a, x);
     }
-    t = wave_merge(t);
-    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    for (uint32_t w = 1; w < SRE_LTT_THREADS / 64u; w++) t = sre_lso_merge(t, part[w]);
-    TopMem mem = {totals};
-    sre_lso_flush(mem, t);
-}
+};
 
 /* lane per entry x = r * k + f of the ordered table */
 __global__ __launch_bounds__(256) void
@@ -194,14 +144,9 @@ extern "C" hipError_t
 sre_launch_tally_top_values(const uint64_t *d_counts, const void *d_sums, uint64_t nkeys, uint32_t v, int by, uint32_t by_col,
                             int64_t *d_value, int8_t *d_class, uint64_t *d_totals, hipStream_t stream)
 {
-    uint32_t grid;
     if (!sre_ltt_by_ok(by, by_col, v) || (by != SRE_LTT_COUNT && d_sums == NULL)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sre_k_tally_top_init, dim3(1), dim3(64), 0, stream, d_totals);
-    if (nkeys == 0) return hipGetLastError();
-    if (!grid_of(nkeys, SRE_LTT_KEYS, &grid)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sre_k_tally_top_values, dim3(grid), dim3(SRE_LTT_THREADS), 0, stream, d_counts,
-                       static_cast<const sre_ls_agg_t *>(d_sums), nkeys, v, by, by_col, d_value, d_class, d_totals);
-    return hipGetLastError();
+    const TopVals src = {d_counts, static_cast<const sre_ls_agg_t *>(d_sums), nkeys, v, by_col, by};
+    return values_launch(src, d_value, d_class, d_totals, stream);
 }
 
 extern "C" hipError_t

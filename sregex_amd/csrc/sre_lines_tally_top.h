@@ -42,9 +42,10 @@
 #define SRE_LTT_MAX         3
 #define SRE_LTT_N           4
 
-#define SRE_LTT_THREADS     256u
-#define SRE_LTT_PER_LANE    4u
-#define SRE_LTT_KEYS        (SRE_LTT_THREADS * SRE_LTT_PER_LANE)       /* 1024 keys a workgroup of the order-values pass */
+/* a workgroup of the order-values pass is a workgroup of the sort's values pass: 256 lanes x 4 keys */
+#define SRE_LTT_THREADS     SRE_LSO_THREADS
+#define SRE_LTT_PER_LANE    SRE_LSO_PER_LANE
+#define SRE_LTT_KEYS        SRE_LSO_LINES
 
 #define SRE_LTT_MAX_RANGE   (~(uint64_t) 0 - 2)                         /* 2^64 - 3 */
 

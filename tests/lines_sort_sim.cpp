@@ -96,6 +96,40 @@ struct SimSortPass {
     }
 };
 
+/* the values pass (sre_k_values of sre_hip_lines_values.h) over n items, workgroup by workgroup, wave by wave, lane by lane:
+ * value[i] and cls[i] of every item, totals[4] with the identities first, sent[4] the atomics each word received.
+ * classify(i, &v): the class of item i, v its value; it counts the stores to value[i] and cls[i] */
+template <class Classify>
+void
+sim_values(uint64_t n, int64_t *value, int8_t *cls, uint64_t *totals, uint32_t *sent, Classify classify)
+{
+    const sre_lso_totals_t id = sre_lso_identity();
+    SimMem                 mem = {totals, sent};
+    totals[0] = id.nkeyed, totals[1] = id.nnumbered, totals[2] = (uint64_t) id.vmin, totals[3] = (uint64_t) id.vmax;
+    const uint64_t nwg = (n + SRE_LSO_LINES - 1) / SRE_LSO_LINES;
+    for (uint64_t w = 0; w < nwg; w++) {
+        sre_lso_totals_t part[SRE_LSO_THREADS / 64u];
+        for (uint32_t wave = 0; wave < SRE_LSO_THREADS / 64u; wave++) {
+            sre_lso_totals_t t = sre_lso_identity();
+            for (uint32_t lane = 0; lane < 64; lane++) {
+                for (uint32_t j = 0; j < SRE_LSO_PER_LANE; j++) {
+                    const uint64_t i = w * SRE_LSO_LINES + j * SRE_LSO_THREADS + wave * 64u + lane;
+                    if (i >= n) continue;
+                    int64_t       v;
+                    const int32_t c = classify(i, &v);
+                    value[i] = v;
+                    cls[i] = (int8_t) c;
+                    t = sre_lso_merge(t, sre_lso_single(c, v));
+                }
+            }
+            part[wave] = t;
+        }
+        sre_lso_totals_t t = part[0];
+        for (uint32_t wave = 1; wave < SRE_LSO_THREADS / 64u; wave++) t = sre_lso_merge(t, part[wave]);
+        sre_lso_flush(mem, t);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -126,33 +160,12 @@ uint64_t
 lsosim_values(const uint8_t *buf, uint64_t len, const uint64_t *vval, const uint64_t *vstart, uint64_t n, int64_t *value, int8_t *cls,
               uint32_t *vw, uint32_t *cw, uint64_t *totals, uint32_t *sent)
 {
-    uint64_t               bad = 0;
-    const SimVals          vals = {buf, len, vval, vstart, &bad};
-    const sre_lso_totals_t id = sre_lso_identity();
-    SimMem                 mem = {totals, sent};
-    totals[0] = id.nkeyed, totals[1] = id.nnumbered, totals[2] = (uint64_t) id.vmin, totals[3] = (uint64_t) id.vmax;
-    const uint64_t nwg = (n + SRE_LSO_LINES - 1) / SRE_LSO_LINES;
-    for (uint64_t w = 0; w < nwg; w++) {
-        sre_lso_totals_t part[SRE_LSO_THREADS / 64u];
-        for (uint32_t wave = 0; wave < SRE_LSO_THREADS / 64u; wave++) {
-            sre_lso_totals_t t = sre_lso_identity();
-            for (uint32_t lane = 0; lane < 64; lane++) {
-                for (uint32_t j = 0; j < SRE_LSO_PER_LANE; j++) {
-                    const uint64_t i = w * SRE_LSO_LINES + j * SRE_LSO_THREADS + wave * 64u + lane;
-                    if (i >= n) continue;
-                    int64_t       v;
-                    const int32_t c = sre_lso_line(vals, i, &v);
-                    value[i] = v, vw[i]++;
-                    cls[i] = (int8_t) c, cw[i]++;
-                    t = sre_lso_merge(t, sre_lso_single(c, v));
-                }
-            }
-            part[wave] = t;
-        }
-        sre_lso_totals_t t = part[0];
-        for (uint32_t wave = 1; wave < SRE_LSO_THREADS / 64u; wave++) t = sre_lso_merge(t, part[wave]);
-        sre_lso_flush(mem, t);
-    }
+    uint64_t      bad = 0;
+    const SimVals vals = {buf, len, vval, vstart, &bad};
+    sim_values(n, value, cls, totals, sent, [&](uint64_t i, int64_t *v) {
+        vw[i]++, cw[i]++;
+        return sre_lso_line(vals, i, v);
+    });
     return bad;
 }
 

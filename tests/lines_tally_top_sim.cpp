@@ -50,41 +50,22 @@ lttsim_first(const uint64_t *tab, const uint32_t *lslot, const uint64_t *cnt, ui
     return bad;
 }
 
-/* the order-values pass over nkeys keys, workgroup by workgroup: value[k], cls[k] (vw[k] counts the stores to both), totals[4]
- * with the identities first, sent[4] the atomics each word received.  aggs: nkeys * v aggregates of four words */
+/* the order-values pass over nkeys keys, the walk of sim_values (lines_sort_sim.cpp): value[k], cls[k] (vw[k] counts the stores
+ * to both), totals[4] with the identities first, sent[4] the atomics each word received.  aggs: nkeys * v aggregates of four
+ * words */
 void
 lttsim_values(const uint64_t *counts, const int64_t *aggs, uint64_t nkeys, uint32_t v, int by, uint32_t by_col, int64_t *value,
               int8_t *cls, uint32_t *vw, uint64_t *totals, uint32_t *sent)
 {
-    const sre_lso_totals_t id = sre_lso_identity();
-    SimMem                 mem = {totals, sent};
-    totals[0] = id.nkeyed, totals[1] = id.nnumbered, totals[2] = (uint64_t) id.vmin, totals[3] = (uint64_t) id.vmax;
-    const uint64_t nwg = (nkeys + SRE_LTT_KEYS - 1) / SRE_LTT_KEYS;
-    for (uint64_t w = 0; w < nwg; w++) {
-        sre_lso_totals_t part[SRE_LTT_THREADS / 64u];
-        for (uint32_t wave = 0; wave < SRE_LTT_THREADS / 64u; wave++) {
-            sre_lso_totals_t t = sre_lso_identity();
-            for (uint32_t lane = 0; lane < 64; lane++) {
-                for (uint32_t j = 0; j < SRE_LTT_PER_LANE; j++) {
-                    const uint64_t k = w * SRE_LTT_KEYS + j * SRE_LTT_THREADS + wave * 64u + lane;
-                    if (k >= nkeys) continue;
-                    sre_ls_agg_t a = sre_ls_identity();
-                    if (by != SRE_LTT_COUNT) {
-                        const int64_t *g = aggs + 4 * (k * v + by_col);
-                        a.sum = g[0], a.min = g[1], a.max = g[2], a.n = (uint64_t) g[3];
-                    }
-                    int64_t       x;
-                    const int32_t c = sre_ltt_order(by, counts[k], &a, &x);
-                    value[k] = x, cls[k] = (int8_t) c, vw[k]++;
-                    t = sre_lso_merge(t, sre_lso_single(c, x));
-                }
-            }
-            part[wave] = t;
+    sim_values(nkeys, value, cls, totals, sent, [&](uint64_t k, int64_t *x) {
+        sre_ls_agg_t a = sre_ls_identity();
+        if (by != SRE_LTT_COUNT) {
+            const int64_t *g = aggs + 4 * (k * v + by_col);
+            a.sum = g[0], a.min = g[1], a.max = g[2], a.n = (uint64_t) g[3];
         }
-        sre_lso_totals_t t = part[0];
-        for (uint32_t wave = 1; wave < SRE_LTT_THREADS / 64u; wave++) t = sre_lso_merge(t, part[wave]);
-        sre_lso_flush(mem, t);
-    }
+        vw[k]++;
+        return sre_ltt_order(by, counts[k], &a, x);
+    });
 }
 
 /* the ordered table, a lane per entry of the first nrows ranks; tw[x] counts the stores to the two words of entry x.  Returns

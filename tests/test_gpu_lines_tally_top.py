@@ -435,3 +435,22 @@ def test_the_scanners_other_calls_behave_as_on_a_fresh_scanner(gpu):
         _, got_rows, _ = run_extract(p.sc, p.exp, data, [1, 2], src_off=2, dst_off=9)
         assert got_sums == want_sums and got_sort == want_sort and got_rows == want_rows
         run_top(p.sc, p.exp, data, [1], [3, 2], MAX, 1, False, limit=4, src_off=2, dst_off=9)
+
+
+def test_scratch_that_grows_inside_a_call_on_a_used_scanner(gpu):
+    """a scanner whose arrays are sized for 60 lines takes 2 101 lines over 1 025 keys: two workgroups of the values pass, three
+    blocks of the entry table's scan, two digit passes; every array of the ordered tally grows inside that call, and the sort
+    and the tally with sums behind it find what a fresh scanner finds"""
+    small, data = top_lines(14, 20, miss=0), top_lines(15, 1025, extra=1.05, span=300, miss=0)
+    assert len(split_lines(small, 0x0A)) == 60 and len(split_lines(data, 0x0A)) == 2101
+    with S.Pool() as pool:
+        p, fresh = Program(pool, KVW), Program(pool, KVW)
+        want_top, _, _ = run_top(fresh.sc, fresh.exp, data, [1], [2, 3], SUM, 0, src_off=2, dst_off=9)
+        assert want_top.nkeys == 1025 and want_top.vmax - want_top.vmin >= 256 and want_top.passes >= 2
+        want_sort = run_sort(fresh.sc, fresh.exp, data, 2, desc=True, src_off=2, dst_off=9)
+        want_sums, _ = run_sums(fresh.sc, fresh.exp, data, [1], [2, 3], src_off=2, dst_off=9)
+        run_top(p.sc, p.exp, small, [1], [2, 3], SUM, 0)
+        got_top, _, _ = run_top(p.sc, p.exp, data, [1], [2, 3], SUM, 0, src_off=2, dst_off=9)
+        got_sort = run_sort(p.sc, p.exp, data, 2, desc=True, src_off=2, dst_off=9)
+        got_sums, _ = run_sums(p.sc, p.exp, data, [1], [2, 3], src_off=2, dst_off=9)
+        assert got_top == want_top and got_sort == want_sort and got_sums == want_sums

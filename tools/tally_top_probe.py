@@ -15,7 +15,8 @@ the kernels of a call are listed per key count with their time and dispatches pe
 
 --parent-lib PATH: the condition that the calls that existed before cost what they cost before.  tally_lines,
 tally_sums_lines and sort_lines are timed in child processes that load PATH (a build of the parent commit, through
-SREGEX_AMD_LIB) and this tree's library in turn: parent, parent, branch, parent, branch.  The first two parent runs are the
+SREGEX_AMD_LIB) and this tree's library in turn: parent, parent, branch, parent, branch; so is tally_top_lines, by COUNT and by
+SUM, descending, limit 0, at 4096 and 200 000 keys, which the parent has too.  The first two parent runs are the
 A/A pair: their difference is the noise of the box.  A difference between the medians of branch and parent counts as none
 when it is no larger than the A/A difference or the span of the --reps calls of one parent process.
 
@@ -49,8 +50,9 @@ SPAN = 1 << 24
 KEYS = (1, 4096, 200000, NLINES)
 LIMITS = (0, 100)
 BYS = {"count": S.HIP_TOP_COUNT, "sum": S.HIP_TOP_SUM}
-NEW_KERNELS = ("sre_k_tally_top_first", "sre_k_tally_top_init", "sre_k_tally_top_values", "sre_k_tally_top_table",
+NEW_KERNELS = ("sre_k_tally_top_first", "sre_k_values_init", "sre_k_values<TopVals>", "sre_k_tally_top_table",
                "sre_k_tally_top_permute", "sre_k_tally_top_ranks")
+OLDER_TOP_KEYS = (4096, 200000)
 
 
 def top_call(sc, buf, nbytes, out, counts, sums, by, limit, rank=None):
@@ -185,8 +187,14 @@ def profile(calls, stats_out):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def older_metrics():
+    return ["tally_lines_ms", "tally_sums_lines_ms", "sort_lines_ms"] + \
+        ["tally_top_lines_%s_%d_keys_ms" % (name, keys) for keys in OLDER_TOP_KEYS for name in BYS]
+
+
 def older(reps):
-    """tally_lines, tally_sums_lines and sort_lines with whatever library this process loaded"""
+    """tally_lines, tally_sums_lines and sort_lines (4096 keys), and tally_top_lines by COUNT and by SUM, descending, limit 0, at
+    4096 and 200 000 keys, with whatever library this process loaded"""
     lib = S.load_library()
     size = 4096
     with S.Pool() as pool:
@@ -206,7 +214,19 @@ def older(reps):
             d, sinfo = timed(lambda: sort_call(sc, buf, nbytes, out, False, 0))
             assert sinfo.nwritten == NLINES and sinfo.passes == 3
             to.append(d)
-        print(json.dumps({"tally_lines_ms": ms(tt[1:]), "tally_sums_lines_ms": ms(ts[1:]), "sort_lines_ms": ms(to[1:])}))
+        res = {"tally_lines_ms": ms(tt[1:]), "tally_sums_lines_ms": ms(ts[1:]), "sort_lines_ms": ms(to[1:])}
+        for keys in OLDER_TOP_KEYS:
+            if keys != size:
+                buf.free()
+                buf, nbytes, _ = fill_lines(lib, SPAN, keys)
+            for name in BYS:
+                tp = []
+                for rep in range(reps + 1):
+                    d, info = timed(lambda: top_call(sc, buf, nbytes, out, counts, sums, BYS[name], 0))
+                    assert (info.nkeys, info.nrows, info.nwritten) == (keys, keys, keys), info
+                    tp.append(d)
+                res["tally_top_lines_%s_%d_keys_ms" % (name, keys)] = ms(tp[1:])
+        print(json.dumps(res))
 
 
 def older_ab(parent_lib, reps):
@@ -222,7 +242,7 @@ def older_ab(parent_lib, reps):
                               stdout=subprocess.PIPE, timeout=300).stdout.decode()
         runs.append((which, json.loads(text.strip().splitlines()[-1])))
     rows = []
-    for metric in ("tally_lines_ms", "tally_sums_lines_ms", "sort_lines_ms"):
+    for metric in older_metrics():
         p_runs = [r[metric]["all"] for w, r in runs if w == "parent"]
         p = [r[metric]["median"] for w, r in runs if w == "parent"]
         b = [r[metric]["median"] for w, r in runs if w == "branch"]
@@ -277,8 +297,9 @@ def main():
                           "kernel_stats_top": top, "rows": per}
     if args.parent_lib:
         doc["older_calls_parent_vs_branch"] = {
-            "run": "tally_lines, tally_sums_lines (4096 keys, one value column) and sort_lines (ascending, no limit, 2^24 values: three "
-                   "passes) over a million lines in child processes that load the parent commit's library and this tree's in turn "
+            "run": "tally_lines, tally_sums_lines (4096 keys, one value column), sort_lines (ascending, no limit, 2^24 values: three "
+                   "passes) and tally_top_lines (by COUNT and by SUM, descending, limit 0, 4096 and 200 000 keys) over a million lines in "
+                   "child processes that load the parent commit's library and this tree's in turn "
                    "(parent, parent, branch, parent, branch); medians of reps after a warm-up; the first two parent runs are the A/A pair",
             "rows": older_ab(args.parent_lib, args.reps)}
     text = json.dumps(doc, indent=1)
