@@ -5,12 +5,15 @@ scan_geometry).  Each test runs a fixed sequence of different call kinds on ONE 
 every answer, and the diagnostics the other suites assert, with the same call on a scanner created
 for it alone; the oracle checks of each call kind are in the suites of that kind.
 """
+import os
 import random
 
 import pytest
 
 import sregex_amd as S
+from test_gpu_caller_stream import CALLS, CALL_IDS, Src, keys, kvw_scanner, line_cap      # noqa: F401 (keys: a fixture)
 from test_gpu_lines import random_text, split_lines
+from test_gpu_lines_tally_top import top_lines
 
 pytestmark = pytest.mark.gpu
 
@@ -185,3 +188,60 @@ def test_nfa_tier_find_all(gpu, monkeypatch):
             assert rows[137][2] > SHORT_MAX and rows[137][4] > 2
     finally:
         t.free()
+
+
+# ------------------------------------------------------------------ every kind after every other
+
+@pytest.fixture(scope="module")
+def order_texts(gpu, keys):
+    """small: 60 lines (one batch); big: 2 101 lines over 1 025 keys (33 batches), the shapes of
+    test_scratch_that_grows_inside_a_call_on_a_used_scanner: two workgroups of the values pass, three blocks of the entry
+    table's scan, two digit passes; and the answer of every table call on each, from a scanner created for that call
+    alone: 28 answers, computed once.  Every kind runs on a scanner of the KVW program here, route_lines with that
+    program's one rule: the sinks that read capture groups cannot run on route_lines' own program, which has none"""
+    saved = os.environ.get("SRE_HIP_LINES_BATCH")
+    os.environ["SRE_HIP_LINES_BATCH"] = str(BATCH)
+    texts = {"small": Src(top_lines(14, 20, miss=0)), "big": Src(top_lines(15, 1025, extra=1.05, span=300, miss=0))}
+    try:
+        assert len(texts["small"].lines) == 60 and len(texts["big"].lines) == 2101
+        assert all(len(t.lines) <= line_cap(len(t.data)) for t in texts.values())
+        fresh = {}
+        with S.Pool() as pool:
+            for name, _, call in CALLS:
+                for size, t in texts.items():
+                    fresh[name, size] = call(kvw_scanner(pool, keys=keys), t.ptr, len(t.data), None, t.lines)
+                assert name == "scan" or fresh[name, "big"][2][0] > 1, "a line call of one batch"
+                assert fresh[name, "small"] != fresh[name, "big"]
+        assert fresh["tally_top_lines", "big"][0].nkeys == 1025 and fresh["tally_top_lines", "big"][0].passes >= 2
+        assert fresh["sort_lines", "big"][0].passes >= 2
+    except BaseException:
+        for t in texts.values():
+            t.free()
+        raise
+    finally:
+        if saved is None:
+            del os.environ["SRE_HIP_LINES_BATCH"]
+        else:
+            os.environ["SRE_HIP_LINES_BATCH"] = saved
+    yield texts, fresh
+    for t in texts.values():
+        t.free()
+
+
+@pytest.mark.parametrize("first", range(len(CALLS)), ids=CALL_IDS)
+def test_every_line_call_after_every_other(gpu, monkeypatch, keys, order_texts, first):
+    """A(small), B(big), A(small), B(small), A(big) on ONE scanner for every kind B: scratch that grows inside a call on
+    a used scanner and is used again at the smaller size, and every ordered pair of kinds, all on the null stream"""
+    monkeypatch.setenv("SRE_HIP_LINES_BATCH", str(BATCH))
+    texts, fresh = order_texts
+    name_a, _, call_a = CALLS[first]
+    with S.Pool() as pool:
+        sc = kvw_scanner(pool, keys=keys)
+        for name_b, _, call_b in CALLS:
+            steps = [(name_a, call_a, "small"), (name_b, call_b, "big"), (name_a, call_a, "small"), (name_b, call_b, "small"),
+                     (name_a, call_a, "big")]
+            for k, (name, call, size) in enumerate(steps):
+                t = texts[size]
+                got = call(sc, t.ptr, len(t.data), None, t.lines)
+                assert got == fresh[name, size], "A = %s, B = %s, step %d: %s(%s) differs from a fresh scanner's" % (
+                    name_a, name_b, k, name, size)
