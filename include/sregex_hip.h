@@ -1040,6 +1040,7 @@ typedef struct {
  * (compose, see above); sorting extracted fields instead of whole lines (extract from the sorted
  * output); a per-line value array supplied by the caller (it would give "tally rows by count");
  * INVERT, every match of a line; Thompson and COUNT scanners, stream sets.
+ * Byte order of the group's text is a call of its own, sre_hip_sort_lines_text.
  * Returns 0 on success, -1 on bad arguments or failure.
  */
 SRE_API int sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
@@ -1142,6 +1143,93 @@ SRE_API int sre_hip_tally_top_lines(sre_hip_scanner_t *sc, const void *d_buf, si
     sre_int_t *d_rank, size_t rank_cap,
     sre_int_t *d_index, size_t index_cap,
     sre_hip_tally_top_info_t *info, void *hip_stream);
+
+/* ---- the line sort by text: order lines by the bytes of a capture group ---- */
+
+typedef struct {
+    size_t nlines;
+    size_t nkeyed;      /* lines with a match */
+    size_t nselected;   /* rows of the full output: min(limit, candidates), limit == 0: all */
+    size_t need_bytes, nwritten, out_bytes;
+    size_t passes;      /* the length of the plan: digit passes that can move a line */
+    size_t minlen, maxlen;   /* shortest and longest COMPARED text over the keyed lines; SIZE_MAX / 0 when there is none */
+} sre_hip_sort_text_info_t;
+
+/*
+ * Line sort by text: the lines of d_buf ordered by the BYTES of one capture group of their first
+ * match, optionally only the first `limit` of them (`LC_ALL=C sort -s -k`, ORDER BY text [DESC]
+ * LIMIT k: by client address as text, by host name or URL path, by an ISO timestamp with a
+ * fraction, by a hexadecimal id, by any key longer than 18 digits).  It is what the "Not offered"
+ * list of sre_hip_sort_lines declines as "text .. order", in byte order.
+ *
+ * What is the numeric sort's.  On the same (sc, d_buf, len, delim, group) the split, the matching,
+ * the routing to an engine (host routes included), the batching, the diagnostics, the demand for
+ * an SRE_HIP_PIKE_FIRST scanner, the range rule of `group`, the overlap check of d_out, limit,
+ * truncation at whole lines, the sizing call, the NULL-pointer rule and the bound of 2^32 - 1
+ * lines are exactly those of sre_hip_sort_lines.
+ *
+ * The text.  A line with a match is KEYED; its text is the bytes of `group` in the first match,
+ * and an unset group is the empty text, as an unset group is an empty field in the extract's rows
+ * (the index row tells the two apart).  max_bytes != 0 compares only the first max_bytes bytes of
+ * the text (sort -k1.1,1.N); max_bytes == 0 compares the whole text.  info->nkeyed counts the
+ * keyed lines, info->minlen and info->maxlen are the shortest and the longest COMPARED text over
+ * them, SIZE_MAX and 0 without a keyed line (and for len == 0, with zeros elsewhere and success).
+ *
+ * The order is that of memcmp over unsigned bytes with a proper prefix first (LC_ALL=C sort).  Any
+ * byte other than delim may occur, NUL included: "a" < "a\0" < "a\0\0" < "aa".
+ *
+ * Flags.  flags is any of SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC; any other bit returns -1 with
+ * info untouched.  flags == 0 writes the keyed lines ascending, SRE_HIP_SORT_DESC descending.
+ * Lines of equal compared text stay in line order in BOTH directions.  SRE_HIP_LINES_ALL selects
+ * every line: the lines without a match come behind ALL keyed lines, in line order, whatever the
+ * direction, so the output is a permutation of the input's lines.
+ *
+ * Each row is the line's bytes plus ONE delim, so the output is a line buffer again, and the sort
+ * is stable: a second call, this one or sre_hip_sort_lines, on the output sorts by a second
+ * column.
+ *
+ * Index.  d_index is an optional DEVICE array: for each of the first min(index_cap, nwritten) rows
+ * in output order it receives 6 sre_int_t,
+ *   [0] line number   [1] offset of the line in d_buf   [2] line length
+ *   [3] offset of the line in d_out
+ *   [4] offset of the field in d_buf   [5] its FULL length, whatever max_bytes is;
+ * [4] and [5] are -1, -1 for an unset group and for a line without a match.
+ *
+ * The plan.  The compared text is cut into chunks of 7 bytes; the key of a chunk is a 64-bit word
+ * of its bytes, big-endian, and the count of bytes it holds, and the sort is a stable radix sort
+ * of one 8-bit digit of one chunk per pass, last chunk first.  After the one read of (nkeyed,
+ * minlen, maxlen) the host lists the (chunk, digit) passes at which two selected lines can differ
+ * at all; sre_hip_sort_text_plan tells the same list, and info->passes is its length: maxlen for
+ * texts of one length, about 8/7 of maxlen + 1 otherwise, eight for chunk 0 when ALL has a line
+ * without a match to place, 0 when every compared text is empty.  THE COST IS LINEAR IN maxlen:
+ * every pass runs over all selected lines, however small limit is, and max_bytes is the caller's
+ * bound on it.
+ *
+ * The call is synchronous and all its work runs on hip_stream.  The host waits exactly as often
+ * as in sre_hip_sort_lines: one read of four words behind the value table, one read of 4 result
+ * words, then the end.  Nothing per line travels to the host.
+ *
+ * Memory.  The call has no arrays of its own: per line 9 bytes (compared length, then the key of
+ * the first chunk, and a byte of class), 2 KiB per 1024 lines of counts, per selected line 24
+ * bytes of items and per row in front of the limit 16 bytes of compact table, all of them the
+ * arrays sre_hip_sort_lines keeps; grow-only device memory, freed with the scanner.
+ *
+ * Not offered: locale or caseless order; several columns in one call (compose, see above);
+ * sort -u; text order for the keys of sre_hip_tally_top_lines; a radix sort that skips passes by
+ * looking at histograms; Thompson and COUNT scanners; stream sets.
+ * Returns 0 on success, -1 on bad arguments or failure.
+ */
+SRE_API int sre_hip_sort_lines_text(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    int group, size_t max_bytes, int flags, size_t limit,
+    void *d_out, size_t out_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_sort_text_info_t *info, void *hip_stream);
+
+/* The plan of sre_hip_sort_lines_text on the host, from what its info reports; rest: the call had
+ * SRE_HIP_LINES_ALL and at least one line without a match.  pairs[2 i] and pairs[2 i + 1] receive
+ * the chunk and the digit (0: the count byte, 7 - j: byte j of the chunk) of pass i, for i below
+ * min(cap, length); pairs may be NULL with cap 0.  Returns the length.  Needs no device. */
+SRE_API size_t sre_hip_sort_text_plan(size_t minlen, size_t maxlen, int rest, uint64_t *pairs, size_t cap);
 
 /* ---- stream sets: many device-resident streams of one program, fed chunk by chunk ---- */
 

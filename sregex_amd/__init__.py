@@ -124,6 +124,9 @@ API = {
     "sre_hip_route_lines_by_key": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int,
                                                   _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_sort_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_sort_lines_text": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _sz, ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp,
+                                               _vp]),
+    "sre_hip_sort_text_plan": (_sz, [_sz, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), _sz]),
     "sre_hip_tally_top_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz,
                                                ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _sz, ctypes.c_int, _sz,
                                                _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
@@ -209,6 +212,18 @@ def tally_number(text):
     if load_library().sre_hip_tally_number(text, len(text), ctypes.byref(value)) != 1:
         return None
     return value.value
+
+
+def sort_text_plan(minlen, maxlen, rest=False):
+    """sre_hip_sort_text_plan: the digit passes of Scanner.sort_lines_text as a list of (chunk, digit) in the order they
+    run, from the minlen and maxlen its info reports and rest (all_lines with at least one line without a match); digit 0
+    is a chunk's count byte, digit 7 - j its byte j.  SortTextInfo.passes is its length.  Needs no device."""
+    lib = load_library()
+    n = lib.sre_hip_sort_text_plan(minlen, maxlen, int(bool(rest)), None, 0)
+    pairs = (ctypes.c_uint64 * (2 * max(n, 1)))()
+    if lib.sre_hip_sort_text_plan(minlen, maxlen, int(bool(rest)), pairs, n) != n:
+        raise RuntimeError("sre_hip_sort_text_plan failed")
+    return [(pairs[2 * i], pairs[2 * i + 1]) for i in range(n)]
 
 
 def keyset_hash(row, nfields=1, fsep=0x09):
@@ -751,6 +766,26 @@ class Scanner:
             raise RuntimeError("sre_hip_sort_lines failed")
         return SortInfo(*(getattr(info, name) for name in SortInfo._fields))
 
+    def sort_lines_text(self, ptr, length, out_ptr, out_cap, group, delim=0x0A, max_bytes=0, descending=False, all_lines=False,
+                        limit=0, index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_sort_lines_text: the lines of the device buffer (ptr, length) that have a match, ordered by the bytes of
+        capture group `group` of the first match (memcmp order, a proper prefix first; an unset group is the empty text),
+        ascending or descending; equal texts stay in line order either way.  max_bytes != 0 compares only the first
+        max_bytes bytes.  The device buffer (out_ptr, out_cap) receives the lines, each followed by one delimiter.  With
+        all_lines every line: the lines without a match follow all others in line order.  limit != 0 keeps the first
+        `limit` rows of that order.  index_ptr: an optional device array of index_cap rows [line no, offset in the buffer,
+        length, offset in the output, offset of the field in the buffer, its full length], the last two -1, -1 for an
+        unset group or a line without a match.  The sort is stable, so sorting the output again by another group, by text
+        or with sort_lines, orders by (second, first, line).  The cost is linear in the longest compared text
+        (sort_text_plan lists the passes).  The scanner's mode must be HIP_PIKE_FIRST.  Returns SortTextInfo(nlines,
+        nkeyed, nselected, need_bytes, nwritten, out_bytes, passes, minlen, maxlen)."""
+        info = SortTextInfoStruct()
+        flags = (HIP_LINES_ALL if all_lines else 0) | (HIP_SORT_DESC if descending else 0)
+        if self.lib.sre_hip_sort_lines_text(self.h, ptr, length, delim, group, max_bytes, flags, limit, out_ptr, out_cap, index_ptr,
+                                            index_cap, ctypes.byref(info), hip_stream) != 0:
+            raise RuntimeError("sre_hip_sort_lines_text failed")
+        return SortTextInfo(*(getattr(info, name) for name in SortTextInfo._fields))
+
     def tally_top_lines(self, ptr, length, out_ptr, out_cap, groups, vgroups, max_keys, by=HIP_TOP_COUNT, by_col=0,
                         descending=True, limit=0, delim=0x0A, fsep=0x09, all_lines=False, counts_ptr=None, counts_cap=0,
                         sums_ptr=None, sums_cap=0, rank_ptr=None, rank_cap=0, index_ptr=None, index_cap=0, hip_stream=None):
@@ -810,6 +845,14 @@ TallyTopInfo = collections.namedtuple("TallyTopInfo", "nlines nselected nkeys no
 class TallyTopInfoStruct(ctypes.Structure):
     """sre_hip_tally_top_info_t"""
     _fields_ = [(name, ctypes.c_int64 if name in ("vmin", "vmax") else ctypes.c_size_t) for name in TallyTopInfo._fields]
+
+
+SortTextInfo = collections.namedtuple("SortTextInfo", "nlines nkeyed nselected need_bytes nwritten out_bytes passes minlen maxlen")
+
+
+class SortTextInfoStruct(ctypes.Structure):
+    """sre_hip_sort_text_info_t"""
+    _fields_ = [(name, ctypes.c_size_t) for name in SortTextInfo._fields]
 
 
 class SortInfoStruct(ctypes.Structure):

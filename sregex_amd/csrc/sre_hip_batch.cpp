@@ -24,6 +24,7 @@
 #include "sre_lines_route.h"
 #include "sre_lines_route_key.h"
 #include "sre_lines_sort.h"
+#include "sre_lines_sort_text.h"
 #include "sre_lines_tally.h"
 #include "sre_lines_tally_top.h"
 #include "sre_lines_sums.h"
@@ -197,7 +198,8 @@ struct sre_hip_scanner_s {
     /* the line sort (sre_hip_sort_lines): the value table is the lookup's key table (d_vval, d_vstart), the compact table the
      * route's (d_fstart, d_rval), the result words d_rres's.  Its items are also the ordered tally's, over keys in the place of
      * lines (sort_passes): the values d_jkey's words, the keys d_kitem's, the counts of a pass d_rcnt's, the scans' sums
-     * d_fblk's; it adds */
+     * d_fblk's.  The sort by text (sre_hip_sort_lines_text) has the same arrays: d_jkey's words hold the compared lengths, then
+     * the keys of the lines in the first chunk; it adds */
     int8_t                   *d_sclass;         /* the class of every item */
     size_t                    sclass_cap;
     uint32_t                 *d_sline[2];       /* the lines of the items, moved with their keys: selected items words each */
@@ -3222,34 +3224,53 @@ hip_failed:
     return -1;
 }
 
-/* The digit passes of the sort and of the ordered tally, queued behind the read of the totals of the values pass (vmin, vmax,
- * nnum; compact_reserve has the counts of a pass): the item arrays of the nsel items selected (at least one); pass 0 over the n
- * values and classes (d_jkey, d_sclass) makes the items and drops the unselected, the later passes move them from one pair of
- * arrays to the other.  Returns the pair that holds the sorted items, -1 on failure */
+/* The digit passes of the sort, of the ordered tally and of one chunk of the sort by text, queued behind the read of the totals
+ * of the values pass (vmin, vmax, nnum; compact_reserve has the counts of a pass): the passes over the digits digits[0 ..
+ * ndigits), at least one, in that order.  from < 0: the items do not exist yet; the item arrays of the nsel items selected (at
+ * least one) are sized, the first digit's pass makes the items in pair 0 and drops the unselected, over the n values and classes
+ * (d_jkey, d_sclass; the digit is 0) or, d_lkeys != NULL, over the keys of the n lines.  from >= 0: the n == nsel items are in
+ * that pair.  The later passes move them from one pair of arrays to the other.  Returns the pair that holds the sorted items,
+ * -1 on failure */
 static int
 sort_passes(sre_hip_scanner_t *sc, uint64_t n, uint64_t nsel, int64_t vmin, int64_t vmax, uint64_t nnum, int desc, int all,
-            uint32_t passes, hipStream_t stream)
+            const uint32_t *digits, uint32_t ndigits, const uint64_t *d_lkeys, int from, hipStream_t stream)
 {
     const uint64_t nd = (uint64_t) 1 << SRE_LSO_DIGIT_BITS, per = SRE_LINES_ITEMS;
-    uint32_t       cur = 0;
-    for (int h = 0; h < 2; h++) {
-        if (lines_grow(&sc->d_kitem[h], &sc->kitem_cap[h], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
-        if (lines_grow(&sc->d_sline[h], &sc->sline_cap[h], nsel * sizeof(uint32_t)) != 0) return -1;
+    uint32_t       cur = from < 0 ? 0u : (uint32_t) from, p = 0;
+    if (ndigits == 0 || (from >= 0 && n != nsel)) return -1;
+    if (from < 0) {
+        for (int h = 0; h < 2; h++) {
+            if (lines_grow(&sc->d_kitem[h], &sc->kitem_cap[h], (nsel + 1) * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_sline[h], &sc->sline_cap[h], nsel * sizeof(uint32_t)) != 0) return -1;
+        }
+        if (d_lkeys) SRE_HIP_TRY(sre_launch_sort_text_count(d_lkeys, n, digits[0], sc->d_rcnt, stream));
+        else {
+            SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, n, vmin, vmax, nnum, desc, all, digits[0], sc->d_rcnt,
+                                              stream));
+        }
+        SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, nd * ((n + per - 1) / per), sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
+        if (d_lkeys) {
+            SRE_HIP_TRY(sre_launch_sort_text_scatter(d_lkeys, n, digits[0], sc->d_rcnt, nsel, sc->d_kitem[0], sc->d_sline[0], stream));
+        } else {
+            SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, n, vmin, vmax, nnum, desc, all, digits[0], sc->d_rcnt,
+                                                nsel, sc->d_kitem[0], sc->d_sline[0], stream));
+        }
+        p = 1;
     }
-    SRE_HIP_TRY(sre_launch_sort_count(sc->d_jkey, sc->d_sclass, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt, stream));
-    SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, nd * ((n + per - 1) / per), sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
-    SRE_HIP_TRY(sre_launch_sort_scatter(sc->d_jkey, sc->d_sclass, NULL, NULL, n, vmin, vmax, nnum, desc, all, 0, sc->d_rcnt, nsel,
-                                        sc->d_kitem[0], sc->d_sline[0], stream));
-    for (uint32_t p = 1; p < passes; p++, cur ^= 1u) {
-        SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nsel, vmin, vmax, nnum, desc, all, p, sc->d_rcnt, stream));
+    for (; p < ndigits; p++, cur ^= 1u) {
+        SRE_HIP_TRY(sre_launch_sort_count(NULL, NULL, sc->d_kitem[cur], nsel, vmin, vmax, nnum, desc, all, digits[p], sc->d_rcnt,
+                                          stream));
         SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rcnt, nd * ((nsel + per - 1) / per), sc->d_fblk, ~(uint64_t) 0, sc->d_linfo, stream));
-        SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nsel, vmin, vmax, nnum, desc, all, p,
-                                            sc->d_rcnt, nsel, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
+        SRE_HIP_TRY(sre_launch_sort_scatter(NULL, NULL, sc->d_kitem[cur], sc->d_sline[cur], nsel, vmin, vmax, nnum, desc, all,
+                                            digits[p], sc->d_rcnt, nsel, sc->d_kitem[cur ^ 1u], sc->d_sline[cur ^ 1u], stream));
     }
     return (int) cur;
 hip_failed:
     return -1;
 }
+
+/* the digit list of a sort whose key is one word: 0 .. passes - 1 */
+static const uint32_t sort_digits[SRE_LSO_MAX_PASSES] = {0, 1, 2, 3, 4, 5, 6, 7};
 
 /* The line sort: the lookup's call with the one sort group as its value group; then the values pass,
  * which leaves the value and the class of every line and the four totals; one read of those, which sizes the item arrays and
@@ -3301,7 +3322,7 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
         if (nsel != 0) {
             if (lines_grow(&sc->d_fstart, &sc->fstart_cap, nout * sizeof(uint64_t)) != 0) return -1;
             if (lines_grow(&sc->d_rval, &sc->rval_cap, (nout + 1) * sizeof(uint64_t)) != 0) return -1;
-            const int cur = sort_passes(sc, n, nsel, vmin, vmax, nnum, desc, all, passes, stream);
+            const int cur = sort_passes(sc, n, nsel, vmin, vmax, nnum, desc, all, sort_digits, passes, NULL, -1, stream);
             if (cur < 0) return -1;
             /* the compact table of the rows in front of the limit; its scan leaves the words of d_linfo as the cut at out_cap
              * gives them */
@@ -3319,6 +3340,129 @@ sre_hip_sort_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int del
         if (nrows != 0) {
             SRE_HIP_TRY(sre_launch_sort_index(lines, sc->d_fstart, sc->d_rval, sc->d_rres, sc->d_jkey, sc->d_sclass, n, nrows, index_cap,
                                               reinterpret_cast<int64_t *>(d_index), stream));
+        }
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* the plan of the sort by text on the host (sre_lines_sort_text.h): pairs[2 i], pairs[2 i + 1] = chunk and digit of pass i for
+ * i < min(cap, length); returns the length */
+extern "C" SRE_API size_t
+sre_hip_sort_text_plan(size_t minlen, size_t maxlen, int rest, uint64_t *pairs, size_t cap)
+{
+    const uint64_t              len = sre_lst_plan(minlen, maxlen, rest != 0, NULL, 0);
+    const uint64_t              take = pairs == NULL ? 0 : len < cap ? len : cap;
+    std::vector<sre_lst_pass_t> plan((size_t) take);
+    (void) sre_lst_plan(minlen, maxlen, rest != 0, plan.data(), take);
+    for (uint64_t i = 0; i < take; i++) {
+        pairs[2 * i] = plan[(size_t) i].chunk;
+        pairs[2 * i + 1] = plan[(size_t) i].digit;
+    }
+    return (size_t) len;
+}
+
+/* The passes of the sort by text, queued behind the read of the totals: chunk by chunk in the plan's order the keys of the
+ * chunk (for the first chunk those of the n lines into d_jkey's words, whose lengths have been read; later those of the items
+ * into the pair that holds them), then the chunk's digits through sort_passes.  An empty plan still has to make the items:
+ * one pass over digit 0 of chunk 0, in which all keys are equal then.  Returns the pair that holds the sorted items */
+static int
+sort_text_passes(sre_hip_scanner_t *sc, const void *d_buf, uint64_t len, uint64_t n, uint64_t nsel, uint64_t max_bytes, int desc, int all,
+                 const std::vector<sre_lst_pass_t> &plan, hipStream_t stream)
+{
+    static const sre_lst_pass_t only = {0, 0};
+    const sre_lst_pass_t       *pl = plan.empty() ? &only : plan.data();
+    const size_t                npl = plan.empty() ? 1 : plan.size();
+    uint64_t                   *lkeys = reinterpret_cast<uint64_t *>(sc->d_jkey);
+    int                         cur = -1;
+    for (size_t at = 0; at < npl;) {
+        uint32_t digits[SRE_LSO_MAX_PASSES], nd = 0;
+        const uint64_t chunk = pl[at].chunk;
+        while (at < npl && pl[at].chunk == chunk && nd < SRE_LSO_MAX_PASSES) digits[nd++] = pl[at++].digit;
+        if (cur < 0) {
+            SRE_HIP_TRY(sre_launch_sort_text_keys(d_buf, len, sc->d_vval, sc->d_vstart, n, max_bytes, NULL, n, chunk, desc, all, lkeys,
+                                                  stream));
+            cur = sort_passes(sc, n, nsel, 0, 0, 0, desc, all, digits, nd, lkeys, -1, stream);
+        } else {
+            SRE_HIP_TRY(sre_launch_sort_text_keys(d_buf, len, sc->d_vval, sc->d_vstart, n, max_bytes, sc->d_sline[cur], nsel, chunk, desc,
+                                                  all, sc->d_kitem[cur], stream));
+            cur = sort_passes(sc, nsel, nsel, 0, 0, 0, desc, all, digits, nd, NULL, cur, stream);
+        }
+        if (cur < 0) return -1;
+    }
+    return cur;
+hip_failed:
+    return -1;
+}
+
+/* The line sort by text: the numeric sort's call with another value and another key.  The values pass
+ * leaves the compared length of every keyed line and the totals (keyed, keyed, minlen, maxlen); the one read of those sizes
+ * the item arrays and fixes the plan; then per chunk the keys and the digit passes, and the numeric sort's table, scan and
+ * cut, finish, read and gather; the index rows are the call's own. */
+extern "C" SRE_API int
+sre_hip_sort_lines_text(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int group, size_t max_bytes, int flags,
+    size_t limit, void *d_out, size_t out_cap, sre_int_t *d_index, size_t index_cap, sre_hip_sort_text_info_t *info, void *hip_stream)
+{
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    if ((flags & ~(SRE_HIP_LINES_ALL | SRE_HIP_SORT_DESC)) != 0) return -1;
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0;
+    if (keyed_call(sc, "line sort by text", d_buf, len, delim, &group, 1, d_out, out_cap, d_index, index_cap, 0, 0, NULL, &sink, &gr, &n,
+                   stream) != 0)
+    {
+        return -1;
+    }
+    sre_hip_sort_text_info_t res;
+    memset(&res, 0, sizeof(res));
+    res.minlen = SIZE_MAX;
+    if (n > SRE_LRK_MAX_LINES) {
+        fprintf(stderr, "[sregex-hip] line sort by text: %llu lines, at most 2^32 - 1\n", (unsigned long long) n);
+        return -1;
+    }
+    if (n != 0) {
+        const int all = (flags & SRE_HIP_LINES_ALL) != 0, desc = (flags & SRE_HIP_SORT_DESC) != 0;
+        uint64_t  nrows = 0;
+        if (compact_reserve(sc, n, (uint64_t) 1 << SRE_LSO_DIGIT_BITS) != 0) return -1;
+        if (lines_grow(&sc->d_jkey, &sc->jkey_cap, n * sizeof(int64_t)) != 0) return -1;
+        if (lines_grow(&sc->d_sclass, &sc->sclass_cap, n * sizeof(int8_t)) != 0) return -1;
+        /* the compared length of every keyed line, and the totals: the one read that sizes everything behind it */
+        SRE_HIP_TRY(sre_launch_sort_text_values(d_buf, len, sc->d_vval, sc->d_vstart, n, max_bytes, sc->d_jkey, sc->d_sclass,
+                                                &sc->d_linfo->skeyed, stream));
+        SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(skeyed), LINFO(snumbered), LINFO(svmin), LINFO(svmax)}));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        const uint64_t nkeyed = sc->h_linfo->skeyed;
+        const int64_t  vmin = (int64_t) sc->h_linfo->svmin, vmax = (int64_t) sc->h_linfo->svmax;
+        if (sc->h_linfo->snumbered != nkeyed || nkeyed > n || (nkeyed != 0 && (vmin < 0 || vmin > vmax || (uint64_t) vmax > len))) {
+            return -1;      /* (cannot happen) */
+        }
+        const uint64_t minlen = nkeyed ? (uint64_t) vmin : SIZE_MAX, maxlen = nkeyed ? (uint64_t) vmax : 0;
+        const uint64_t nsel = sre_lst_selected(n, nkeyed, all), nout = sre_lso_limited(nsel, limit);
+        const int      rest = all && nkeyed < n;
+        std::vector<sre_lst_pass_t> plan((size_t) sre_lst_plan(minlen, maxlen, rest, NULL, 0));
+        (void) sre_lst_plan(minlen, maxlen, rest, plan.data(), plan.size());
+        const uint32_t *lines = NULL;
+        if (nsel != 0) {
+            if (lines_grow(&sc->d_fstart, &sc->fstart_cap, nout * sizeof(uint64_t)) != 0) return -1;
+            if (lines_grow(&sc->d_rval, &sc->rval_cap, (nout + 1) * sizeof(uint64_t)) != 0) return -1;
+            const int cur = sort_text_passes(sc, d_buf, len, n, nsel, max_bytes, desc, all, plan, stream);
+            if (cur < 0) return -1;
+            lines = sc->d_sline[cur];
+            SRE_HIP_TRY(sre_launch_sort_table(lines, sc->d_ends, nout, n, sc->d_fstart, sc->d_rval, stream));
+            SRE_HIP_TRY(sre_launch_filter_offsets(sc->d_rval, nout, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        }
+        SRE_HIP_TRY(sre_launch_sort_finish(sc->d_rval, nout, out_cap, sc->d_rres, stream));
+        if (compact_finish(sc, &sink, d_buf, n, SRE_LSO_RES_WORDS, nout, &res, &nrows, stream) != 0) return -1;
+        res.nkeyed = (size_t) nkeyed;
+        res.passes = plan.size();
+        res.minlen = (size_t) minlen;
+        res.maxlen = (size_t) maxlen;
+        if (nrows != 0) {
+            SRE_HIP_TRY(sre_launch_sort_text_index(d_buf, len, sc->d_vval, sc->d_vstart, n, lines, sc->d_fstart, sc->d_rval, sc->d_rres,
+                                                   nrows, index_cap, reinterpret_cast<int64_t *>(d_index), stream));
         }
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
@@ -3407,7 +3551,8 @@ sre_hip_tally_top_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, in
             }
             const uint32_t passes = sre_ltt_passes(nkeys, nordered, vmin, vmax);
             /* the sort's passes over the keys: every key is selected */
-            const int cur = sort_passes(sc, nkeys, nkeys, vmin, vmax, nordered, (flags & SRE_HIP_SORT_DESC) != 0, 1, passes, stream);
+            const int cur = sort_passes(sc, nkeys, nkeys, vmin, vmax, nordered, (flags & SRE_HIP_SORT_DESC) != 0, 1, sort_digits, passes,
+                                        NULL, -1, stream);
             if (cur < 0) return -1;
             const uint32_t *keys = sc->d_sline[cur];
             /* the ordered table of the rows in front of the limit (its source is the entry table: d_fval, d_fstart), the

@@ -322,6 +322,29 @@ hipError_t sre_launch_sort_finish(const uint64_t *d_coff, uint64_t nout, uint64_
 hipError_t sre_launch_sort_index(const uint32_t *d_lines, const uint64_t *d_cstart, const uint64_t *d_coff, const uint64_t *d_res,
     const int64_t *d_value, const int8_t *d_class, uint64_t nlines, uint64_t nrows, uint64_t index_cap, int64_t *d_index,
     hipStream_t stream);
+/* ---- the line sort by text (sre_hip_lines_sort_text.hip, sre_lines_sort_text.h) ---- */
+/* the values pass of the sort over the texts of the ONE sort group (d_vval / d_vstart as above; d_buf of len bytes): a line with
+ * a match has class SRE_LSO_NUMBER and as its value its compared length (sre_lst_cut under max_bytes), any other
+ * SRE_LSO_NOMATCH; d_totals[0 .. 4) = the keyed lines, twice, the shortest and the longest compared length */
+hipError_t sre_launch_sort_text_values(const void *d_buf, uint64_t len, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n,
+    uint64_t max_bytes, int64_t *d_value, int8_t *d_class, uint64_t *d_totals, hipStream_t stream);
+/* a lane per item: d_keys[i] = the key of chunk `chunk` of item i (sre_lst_line_key).  d_lines == NULL: the nitems == n lines
+ * in line order, SRE_LSO_DROPPED for a line that is not selected; otherwise item i is line d_lines[i].  No byte at or past
+ * len is read */
+hipError_t sre_launch_sort_text_keys(const void *d_buf, uint64_t len, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n,
+    uint64_t max_bytes, const uint32_t *d_lines, uint64_t nitems, uint64_t chunk, int desc, int all, uint64_t *d_keys,
+    hipStream_t stream);
+/* the digit pass that makes the items, count then (behind sre_launch_filter_offsets, as for sre_launch_sort_count) scatter, over
+ * the keys d_lkeys of the n lines in line order: key and line number of every line whose key is not SRE_LSO_DROPPED go to its
+ * rank of d_dkey / d_dline, which hold `total` items; the digit is bits pass * 8 .. pass * 8 + 7, pass < 8 */
+hipError_t sre_launch_sort_text_count(const uint64_t *d_lkeys, uint64_t n, uint32_t pass, uint64_t *d_cnt, hipStream_t stream);
+hipError_t sre_launch_sort_text_scatter(const uint64_t *d_lkeys, uint64_t n, uint32_t pass, const uint64_t *d_first, uint64_t total,
+    uint64_t *d_dkey, uint32_t *d_dline, hipStream_t stream);
+/* rows [line, start, len, output offset, field start, field length] (sre_lst_index_row) of the first min(index_cap, d_res[2])
+ * ranks; nrows: that number */
+hipError_t sre_launch_sort_text_index(const void *d_buf, uint64_t len, const uint64_t *d_vval, const uint64_t *d_vstart, uint64_t n,
+    const uint32_t *d_lines, const uint64_t *d_cstart, const uint64_t *d_coff, const uint64_t *d_res, uint64_t nrows,
+    uint64_t index_cap, int64_t *d_index, hipStream_t stream);
 /* ---- the ordered tally (sre_hip_lines_tally_top.hip, sre_lines_tally_top.h) ---- */
 /* behind the tally's ranks (d_cnt[slot] is the key's number), a lane per line: d_first[key] = the line the keep pass left
  * selected for the key, the one line i with d_tab[d_lslot[i]] == i; nkeys words */
