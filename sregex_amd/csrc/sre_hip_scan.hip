@@ -218,7 +218,8 @@ enum : uint32_t {
     F_PEND_LAZY = 512u, /* COUNT: the last fast span ended in a FRESH state: a match is pending whose event was not
                            recorded — it ends with that span's last byte (settle() replays the span) */
     F_NO_EOF = 2048u,   /* the stream's own "more chunks follow" (sre_scan_geom_t.sentry) */
-    F_LZ_GROUP = 1024u  /* ... and that span was a 16-byte group, not a 64-byte round */
+    F_LZ_GROUP = 1024u, /* ... and that span was a 16-byte group, not a 64-byte round */
+    F_SPLIT_MISS = 4096u /* the lane's last split walk walked a sub-chain again (sre_k_scan's throttle) */
 };
 
 /* the search a lane is currently following */
@@ -573,6 +574,26 @@ byte_x4(uint32_t v, uint32_t sh)
 #ifndef SRE_SCAN_PREFETCH
 #define SRE_SCAN_PREFETCH 1         /* stages of HBM loads in flight per lane (1 or 2), see sre_k_scan */
 #endif
+/* SRE_SCAN_SPLIT: sub-chains the lookups of a common round are walked as (1 = one serial chain, 2, 4; "the split
+ * walk" in sre_k_scan, sre_scan_split.h).  Undefined: scan_split_of() picks per instantiation, from same-box A/B runs
+ * (profiles/scan_split_rate.json); -DSRE_SCAN_SPLIT=K builds every instantiation with K for such runs. */
+#ifndef SRE_SCAN_SPLIT_HOLD
+#define SRE_SCAN_SPLIT_HOLD 3       /* rounds a wave walks serially after a round in which a lane's guess missed */
+#endif
+constexpr int
+scan_split_of(int mode, int bits, bool wide, bool grow)
+{
+#ifdef SRE_SCAN_SPLIT
+    (void) mode; (void) bits; (void) wide; (void) grow;
+    return SRE_SCAN_SPLIT;
+#else
+    /* K > 1 where a measured workload gains beyond the run-to-run spread of the serial build; a form no workload of
+     * bench.py runs on, or one that a workload loses on (COUNT 1-bit GROW: words; COUNT 2-bit GROW: floor), keeps the
+     * serial chain (figures: DESIGN.md 4.3) */
+    if (mode != SRE_HIP_PIKE_COUNT) return (bits == 2 || bits == 4) ? 4 : 1;
+    return (bits == 4 && !wide && grow) ? 4 : 1;
+#endif
+}
 #ifndef SRE_FIRST_BLOCKS
 #define SRE_FIRST_BLOCKS 4          /* workgroups per CU the FIRST / Thompson kernels' registers are budgeted for */
 #endif
@@ -949,8 +970,23 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
      * a stage's loads fly while the previous round is walked.  2: two sets, taking turns — a
      * load has a whole iteration more to arrive before the wave needs it. */
     constexpr uint32_t DIST = SRE_SCAN_PREFETCH;
+    constexpr int      NLOOK = TILE * BITS / 8;     /* table lookups of a common round */
+    constexpr int      SPLIT = scan_split_of(MODE, BITS, WIDE, GROW);
+    static_assert(SPLIT == 1 || SPLIT == 2 || SPLIT == 4, "SRE_SCAN_SPLIT is 1, 2 or 4");
+    /* the split walk's throttle, one count per wave: rounds still to be walked serially */
+    uint32_t           hold = 0;
     __syncthreads();                        /* row tables are complete */
     auto round = [&](const uint32_t s, uint4 (&regs)[4]) __attribute__((always_inline)) {
+        if (SPLIT > 1) {
+            /* a wave pays for the one lane whose guess misses: after such a round it keeps to the serial walk for
+             * SRE_SCAN_SPLIT_HOLD rounds, then tries again (all lanes meet here, the count stays wave-uniform) */
+            if (__builtin_amdgcn_ballot_w64((w.fl & F_SPLIT_MISS) != 0)) {
+                hold = SRE_SCAN_SPLIT_HOLD;
+                w.fl &= ~F_SPLIT_MISS;
+            } else if (hold) {
+                hold--;
+            }
+        }
         /* LDS operations of one wave execute in order; the fences only stop the
          * compiler from moving tile reads across the stores */
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1008,19 +1044,87 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
                 }
                 if (w.f(F_SHADOW)) t = sha;
             }
-#pragma unroll
-            for (int j = 0; j < TILE * BITS / 8; j++) {
-                uint32_t a;
+            /* address of the entry that index j of the round selects in the row entry e points to */
+            auto look = [&](const uint32_t e, const int j) __attribute__((always_inline)) -> uint32_t {
                 if (WIDE) {
-                    a = (j & 1) ? add_w0_w<1>(t, roww[j >> 1]) : add_w0_w<0>(t, roww[j >> 1]);
+                    return (j & 1) ? add_w0_w<1>(e, roww[j >> 1]) : add_w0_w<0>(e, roww[j >> 1]);
                 } else {
                     const uint32_t wj = roww[j >> 2];
                     const uint32_t ix = (j & 3) == 0 ? byte_x4<0>(wj, two) : (j & 3) == 1 ? byte_x4<1>(wj, two)
                                       : (j & 3) == 2 ? byte_x4<2>(wj, two) : byte_x4<3>(wj, two);
-                    a = add_w0_w<2>(t, ix);
+                    return add_w0_w<2>(e, ix);
                 }
-                t = *(lds_u32_t) (uintptr_t) a;
-                if (MODE == SRE_HIP_PIKE_COUNT) cnt = add_b3(cnt, t);
+            };
+            /* lookups [j0, j1) of the round, one after the other */
+            auto serial = [&](const int j0, const int j1) __attribute__((always_inline)) {
+#pragma unroll
+                for (int j = j0; j < j1; j++) {
+                    t = *(lds_u32_t) (uintptr_t) look(t, j);
+                    if (MODE == SRE_HIP_PIKE_COUNT) cnt = add_b3(cnt, t);
+                }
+            };
+            if (SPLIT > 1 && hold == 0) {
+                /* the split walk: sre_split_walk of sre_scan_split.h, line by line */
+                constexpr int  L = NLOOK / SPLIT;               /* lookups per chain */
+                const uint32_t t0 = t;                          /* the guess: the round's own entry row (low half) */
+                uint32_t       tc[SPLIT], cc[SPLIT];
+#pragma unroll
+                for (int c = 0; c < SPLIT; c++) {
+                    tc[c] = t0;
+                    cc[c] = 0;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int j = 0; j < L; j++) {
+                    /* every chain's address, then every chain's read: LDS answers in order, the reads of a step overlap */
+                    uint32_t ad[SPLIT];
+#pragma unroll
+                    for (int c = 0; c < SPLIT; c++) ad[c] = look(tc[c], c * L + j);
+#pragma unroll
+                    for (int c = 0; c < SPLIT; c++) tc[c] = *(lds_u32_t) (uintptr_t) ad[c];
+                    if (MODE == SRE_HIP_PIKE_COUNT) {
+#pragma unroll
+                        for (int c = 0; c < SPLIT; c++) cc[c] = add_b3(cc[c], tc[c]);
+                    }
+                    /* (left to itself the scheduler runs chain 0 three steps ahead, on the half of the row that
+                     * arrives first, and the last chain as many behind: steps of one read in flight again) */
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                /* every guess hit iff every chain but the last ended in row t0 (a SLOW entry points to the trap row,
+                 * where no round starts: the row's address says it all) */
+                uint32_t off = 0;
+                t = tc[SPLIT - 1];
+#pragma unroll
+                for (int c = 0; c < SPLIT - 1; c++) off |= tc[c] ^ t0;
+#pragma unroll
+                for (int c = 0; c < SPLIT; c++) cnt += cc[c];
+                if (__builtin_amdgcn_ballot_w64((off & 0xffffu) != 0)) {
+                    if (off & 0xffffu) {
+                        w.fl |= F_SPLIT_MISS;                   /* the wave's next rounds are walked serially */
+                        /* chain c counts iff chain c - 1 counts and ended in row t0 */
+                        uint32_t nv = 1;                        /* chains that count */
+                        t = tc[0];
+                        cnt = cc[0];
+#pragma unroll
+                        for (int c = 1; c < SPLIT; c++) {
+                            if (nv == (uint32_t) c && ((t ^ t0) & 0xffffu) == 0) {
+                                t = tc[c];
+                                cnt += cc[c];
+                                nv = c + 1;
+                            }
+                        }
+                        /* the first chain that does not count and all behind it, from the end of the chain in front;
+                         * a SLOW end stays SLOW whatever follows (the trap row): nothing to walk */
+                        if (!(t & LDS_SLOW)) {
+#pragma unroll
+                            for (int c = 1; c < SPLIT; c++) {
+                                if (nv <= (uint32_t) c) serial(c * L, (c + 1) * L);
+                            }
+                        }
+                    }
+                }
+            } else {
+                serial(0, NLOOK);
             }
             if (!(t & LDS_SLOW)) {
                 /* matches completed in the round, each followed by a restart at
