@@ -818,6 +818,101 @@ SRE_API int sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_
     sre_int_t *d_index, size_t index_cap,
     sre_hip_lookup_info_t *info, void *hip_stream);
 
+/* ---- the line distinct: select lines by first, last or count of their key ---- */
+
+enum { SRE_HIP_DISTINCT_FIRST = 0, SRE_HIP_DISTINCT_LAST = 1, SRE_HIP_DISTINCT_EVERY = 2 };
+
+typedef struct {
+    size_t nlines;      /* lines of the buffer */
+    size_t nkeyed;      /* lines with a match, i.e. with a key */
+    size_t nkeys;       /* distinct keys */
+    size_t nkeys_kept;  /* distinct keys whose count is within [min_count, max_count] */
+    size_t nselected;   /* lines the rule and the flags select */
+    size_t need_bytes;  /* sum of (len + 1) over them */
+    size_t nwritten;    /* selected lines written (whole lines only) */
+    size_t out_bytes;
+} sre_hip_distinct_info_t;
+
+/*
+ * Line distinct: the lines of d_buf deduplicated by a captured key: the first or the last line of
+ * every key, or every line of the keys that occur a given number of times.  It writes whole lines
+ * where sre_hip_tally_lines writes one row of key fields per key:
+ *   awk '!seen[k]++', and sort -u behind a sort      SRE_HIP_DISTINCT_FIRST, min 1, max 0
+ *   the latest record per key                        SRE_HIP_DISTINCT_LAST,  min 1, max 0
+ *   uniq -u (keys that occur once)                   SRE_HIP_DISTINCT_FIRST, min 1, max 1
+ *   uniq -d (one line per repeated key)              SRE_HIP_DISTINCT_FIRST, min 2, max 0
+ *   uniq -D, GROUP BY key HAVING COUNT(*) >= n       SRE_HIP_DISTINCT_EVERY, min n, max 0
+ *
+ * What is the lookup's.  The split of d_buf, the matching of every line, the routing to an engine,
+ * the batching and the diagnostics are exactly those of sre_hip_lookup_lines on the same (sc,
+ * d_buf, len, delim); so are the demand for an SRE_HIP_PIKE_FIRST scanner (Thompson and COUNT
+ * scanners return -1 with a diagnostic), the range rule of groups (1 to
+ * SRE_HIP_EXTRACT_MAX_FIELDS of them) and the overlap check of d_out.
+ *
+ * Key.  A line is KEYED when it has a match; its key is the tuple of the texts of the capture
+ * groups `groups` of its first match, compared as sre_hip_tally_lines compares keys: field by
+ * field, lengths first, so ("ab", "c") and ("a", "bc") differ.  An unset group is an empty field.
+ * A line without a match has no key and is never selected.
+ *
+ * Count range.  The count c of a key is the number of keyed lines that carry it, over the WHOLE
+ * buffer: equal keys need not be adjacent, unlike uniq's.  A key QUALIFIES when min_count <= c
+ * and (max_count == 0 or c <= max_count).  min_count == 0, and a nonzero max_count below
+ * min_count, return -1.
+ *
+ * Rule.  A keyed line is PICKED when its key qualifies and, with SRE_HIP_DISTINCT_FIRST, it is the
+ * lowest line of its key; with SRE_HIP_DISTINCT_LAST the highest; with SRE_HIP_DISTINCT_EVERY
+ * always.  Any other `which` returns -1.
+ *
+ * Flags.  flags == 0 selects the picked lines; SRE_HIP_LINES_INVERT selects the keyed lines that
+ * are NOT picked (with FIRST, 1, 0: the duplicates the plain call removes).  Any other flag bit,
+ * SRE_HIP_LINES_ALL included, returns -1.
+ *
+ * Output, truncation, the sizing call and d_index are those of sre_hip_filter_lines byte for byte:
+ * the selected lines in line order, each followed by one delim, whole lines only, nothing at or
+ * beyond out_bytes touched, d_out == NULL with out_cap == 0 sizes the output, index rows of the
+ * filter's four words.  The output is a line buffer again.
+ *
+ * Per-line arrays.  d_keycount and d_keyline are optional DEVICE arrays.  d_keycount[i], i <
+ * min(keycount_cap, nlines), is the count of line i's key, 0 for a line without a key.
+ * d_keyline[i], i < min(keyline_cap, nlines), is the lowest line that carries line i's key, -1
+ * for a line without one: a deterministic name of the key, and the line whose row
+ * sre_hip_tally_lines writes for it.  Neither depends on which, the range, flags or out_cap.  A
+ * NULL pointer with a nonzero capacity returns -1.
+ *
+ * Totals.  info->nkeyed, nkeys, nkeys_kept, nselected and need_bytes are totals over the buffer
+ * whatever out_cap is.  With FIRST or LAST and no INVERT, nselected == nkeys_kept.
+ *
+ * max_keys and overflow are the tally's: 1 <= max_keys <= 2^30, else -1; a buffer with more than
+ * max_keys distinct keys returns SRE_HIP_TALLY_OVERFLOW, nothing is written to d_out, d_keycount,
+ * d_keyline or d_index, and info holds nlines and nkeyed and zeros elsewhere; nkeys == max_keys
+ * succeeds.  SRE_HIP_TALLY_HASH_BITS is the tally's knob here too.
+ *
+ * len == 0 gives all zeros and success.  The call is synchronous and all its work runs on
+ * hip_stream; the result does not depend on the order in which the device meets the lines.  The
+ * host waits exactly as often as in sre_hip_lookup_lines: the overflow flag and the totals travel
+ * in the one read of the filter's four words.  On the device routes nothing per line or per key
+ * travels to the host.
+ *
+ * Memory.  Beyond what sre_hip_lookup_lines takes, a scanner keeps the table of
+ * sre_hip_tally_lines (16 bytes per slot, slots = the power of two at or above max(1024, 2 x
+ * max_keys), and 4 bytes per line for the slots of the lines; the same memory), and for
+ * SRE_HIP_DISTINCT_LAST 8 bytes per slot more.  All grow-only device memory, freed with the
+ * scanner.
+ *
+ * Not offered: SRE_HIP_LINES_ALL; adjacency-only uniq semantics (keys are counted over the whole
+ * buffer); caseless keys; key numbers in first-appearance order (sre_hip_tally_lines gives
+ * those); a fifth index word; every match of a line; Thompson and COUNT scanners; stream sets.
+ * Returns 0 on success, SRE_HIP_TALLY_OVERFLOW, or -1 on bad arguments or failure; a call that
+ * returns -1 for its arguments leaves info untouched.
+ */
+SRE_API int sre_hip_distinct_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim,
+    const int *groups, size_t ngroups, int which, size_t min_count, size_t max_count, int flags,
+    size_t max_keys, void *d_out, size_t out_cap,
+    uint64_t *d_keycount, size_t keycount_cap,
+    sre_int_t *d_keyline, size_t keyline_cap,
+    sre_int_t *d_index, size_t index_cap,
+    sre_hip_distinct_info_t *info, void *hip_stream);
+
 /* ---- the line join: append a key map's value columns to each matching line ---- */
 
 enum { SRE_HIP_JOIN_MAX_VALUES = 31 };

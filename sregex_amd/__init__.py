@@ -37,6 +37,7 @@ HIP_ROUTE_MAX_BUCKETS = 256
 HIP_TALLY_OVERFLOW = 1
 HIP_TALLY_MAX_KEYS = 1 << 30
 HIP_TALLY_MAX_VALUES = 8
+HIP_DISTINCT_FIRST, HIP_DISTINCT_LAST, HIP_DISTINCT_EVERY = 0, 1, 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -118,6 +119,8 @@ API = {
     "sre_hip_keyset_hash": (ctypes.c_uint64, [ctypes.c_char_p, _sz, _sz, ctypes.c_int]),
     "sre_hip_lookup_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp, ctypes.c_int, _vp,
                                             _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "sre_hip_distinct_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, _sz, _sz,
+                                              ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_join_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, _vp,
                                           ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _sz,
                                           _vp, _vp]),
@@ -709,6 +712,42 @@ class Scanner:
             raise RuntimeError("sre_hip_lookup_lines failed")
         return LookupInfo(*info)
 
+    def distinct_lines(self, ptr, length, out_ptr, out_cap, groups, max_keys, which=HIP_DISTINCT_FIRST, min_count=1, max_count=0,
+                       delim=0x0A, invert=False, keycount_ptr=None, keycount_cap=0, keyline_ptr=None, keyline_cap=0,
+                       index_ptr=None, index_cap=0, hip_stream=None):
+        """sre_hip_distinct_lines: the matching lines of the device buffer (ptr, length) deduplicated by their key, the
+        tuple of the texts of the capture groups `groups` of the first match.  A key qualifies when the number of lines
+        that carry it, over the whole buffer, is at least min_count and (max_count != 0) at most max_count; of a
+        qualifying key the call picks the first line (which=HIP_DISTINCT_FIRST), the last (HIP_DISTINCT_LAST) or every
+        line (HIP_DISTINCT_EVERY), and with invert it selects the keyed lines that are not picked.  The device buffer
+        (out_ptr, out_cap) receives the selected lines in line order as filter_lines writes them.  FIRST, 1, 0 is
+        awk '!seen[k]++'; LAST, 1, 0 the latest record per key; FIRST, 1, 1 uniq -u; FIRST, 2, 0 uniq -d; EVERY, n, 0
+        uniq -D / HAVING COUNT(*) >= n.  keycount_ptr: an optional device array of keycount_cap uint64, per line the count
+        of its key or 0; keyline_ptr: an optional device array of keyline_cap int64, per line the first line of its key
+        or -1; index_ptr: the filter's index rows.  The scanner's mode must be HIP_PIKE_FIRST.  Returns
+        DistinctInfo(nlines, nkeyed, nkeys, nkeys_kept, nselected, need_bytes, nwritten, out_bytes).  More than max_keys
+        distinct keys raise TallyOverflow, whose .info is a DistinctInfo with nlines and nkeyed and zeros elsewhere;
+        nothing was written then.  Arguments the call refuses without a device raise ValueError."""
+        groups = list(groups)
+        if (which not in (HIP_DISTINCT_FIRST, HIP_DISTINCT_LAST, HIP_DISTINCT_EVERY) or min_count < 1
+                or (max_count != 0 and max_count < min_count) or not 1 <= max_keys <= HIP_TALLY_MAX_KEYS
+                or not 1 <= len(groups) <= HIP_EXTRACT_MAX_FIELDS or (keycount_cap and not keycount_ptr)
+                or (keyline_cap and not keyline_ptr) or (index_cap and not index_ptr) or (out_cap and not out_ptr)):
+            raise ValueError("sre_hip_distinct_lines: which, the count range, max_keys, the groups or a NULL pointer with a "
+                             "capacity is out of range")
+        arr = (ctypes.c_int * len(groups))(*groups)
+        info = DistinctInfoStruct()
+        rc = self.lib.sre_hip_distinct_lines(self.h, ptr, length, delim, arr, len(groups), which, min_count, max_count,
+                                             HIP_LINES_INVERT if invert else 0, max_keys, out_ptr, out_cap, keycount_ptr,
+                                             keycount_cap, keyline_ptr, keyline_cap, index_ptr, index_cap, ctypes.byref(info),
+                                             hip_stream)
+        res = DistinctInfo(*(getattr(info, name) for name in DistinctInfo._fields))
+        if rc == HIP_TALLY_OVERFLOW:
+            raise TallyOverflow(res, max_keys)
+        if rc != 0:
+            raise RuntimeError("sre_hip_distinct_lines failed")
+        return res
+
     def join_lines(self, ptr, length, out_ptr, out_cap, groups, keyset, vcols, jsep=0x09, delim=0x0A, all_lines=False,
                    keyid_ptr=None, keyid_cap=0, index_ptr=None, index_cap=0, hip_stream=None):
         """sre_hip_join_lines: the lines of the device buffer (ptr, length) whose key (lookup_lines) is in the key map
@@ -858,6 +897,14 @@ class SortTextInfoStruct(ctypes.Structure):
 class SortInfoStruct(ctypes.Structure):
     """sre_hip_sort_info_t"""
     _fields_ = [(name, ctypes.c_int64 if name in ("vmin", "vmax") else ctypes.c_size_t) for name in SortInfo._fields]
+
+
+DistinctInfo = collections.namedtuple("DistinctInfo", "nlines nkeyed nkeys nkeys_kept nselected need_bytes nwritten out_bytes")
+
+
+class DistinctInfoStruct(ctypes.Structure):
+    """sre_hip_distinct_info_t"""
+    _fields_ = [(name, ctypes.c_size_t) for name in DistinctInfo._fields]
 
 
 class TallyInfoStruct(ctypes.Structure):

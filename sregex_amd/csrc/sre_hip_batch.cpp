@@ -27,6 +27,7 @@
 #include "sre_lines_sort_text.h"
 #include "sre_lines_tally.h"
 #include "sre_lines_tally_top.h"
+#include "sre_lines_distinct.h"
 #include "sre_lines_sums.h"
 #include "sre_lines_keyset.h"
 #include "sre_lines_join.h"
@@ -174,7 +175,8 @@ struct sre_hip_scanner_s {
     uint64_t                 *d_rres, *h_rres;  /* the words the host reads: SRE_LR_RES_WORDS + 2 x SRE_LR_MAX_BUCKETS */
     /* the tallies (sre_hip_tally_lines, _sums_lines, _top_lines; tally_front): the entry table is the extract's (d_fval, d_fstart,
      * d_fblk); they add */
-    uint64_t                 *d_ttab;           /* the table of keys: nslots words of line numbers, then nslots counts or key numbers */
+    uint64_t                 *d_ttab;           /* the table of keys: nslots words of line numbers, then nslots counts or key numbers;
+                                                   the line distinct's LAST adds a third run, the last line of every slot */
     size_t                    ttab_cap;
     uint32_t                 *d_tslot;          /* the slot of every line */
     size_t                    tslot_cap;
@@ -2549,6 +2551,27 @@ tally_open(sre_hip_scanner_t *sc, const char *call, const void *d_buf, size_t le
     return lines_call(sc, d_buf, len, delim, 0, NULL, 0, &t->sink, &t->n, &nrep, stream);
 }
 
+/* The table of the tallies and of the line distinct for n lines and max_keys keys, grown and cleared, three memsets queued:
+ * the keys' run of d_ttab to SRE_LT_EMPTY, the `zero_runs` runs behind it (the counts; the distinct's last lines) and the
+ * first `words` of the info words tsel, tclaims, tover, dkept to 0.  Returns the slots of a run, 0 on failure */
+static uint64_t
+tally_table(sre_hip_scanner_t *sc, uint64_t n, size_t max_keys, uint32_t zero_runs, uint32_t words, hipStream_t stream)
+{
+    const uint64_t nslots = sre_lt_nslots(max_keys);
+    if (lines_grow(&sc->d_ttab, &sc->ttab_cap, (1 + zero_runs) * nslots * sizeof(uint64_t)) != 0) return 0;
+    if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return 0;
+    SRE_HIP_TRY(hipMemsetAsync(sc->d_ttab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
+    SRE_HIP_TRY(hipMemsetAsync(sc->d_ttab + nslots, 0, zero_runs * nslots * sizeof(uint64_t), stream));
+    static_assert(offsetof(sre_lines_info_t, tclaims) == offsetof(sre_lines_info_t, tsel) + sizeof(uint64_t)
+                      && offsetof(sre_lines_info_t, tover) == offsetof(sre_lines_info_t, tsel) + 2 * sizeof(uint64_t)
+                      && offsetof(sre_lines_info_t, dkept) == offsetof(sre_lines_info_t, tsel) + 3 * sizeof(uint64_t),
+                  "tsel, tclaims, tover, dkept are zeroed as one run");
+    SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, words * sizeof(uint64_t), stream));
+    return nslots;
+hip_failed:
+    return 0;
+}
+
 /* Behind the line-mode call (t->n != 0): the table grown and cleared, the insert of every selected line and the keep pass
  * that leaves the first line of every key selected, the extract's scan with the cut at `cut` bytes and the one read (its
  * four words and the tally's three) into res.  0, SRE_HIP_TALLY_OVERFLOW (nothing is to be written) or -1 */
@@ -2556,19 +2579,12 @@ template <class Info>
 static int
 tally_front(sre_hip_scanner_t *sc, TallyCall *t, const void *d_buf, size_t max_keys, size_t cut, Info *res, hipStream_t stream)
 {
-    const uint64_t n = t->n, nslots = sre_lt_nslots(max_keys);
+    const uint64_t n = t->n, nslots = tally_table(sc, n, max_keys, 1, 3, stream);
     LinesSink      whole = t->sink;
     whole.out_cap = cut;
-    if (lines_grow(&sc->d_ttab, &sc->ttab_cap, 2 * nslots * sizeof(uint64_t)) != 0) return -1;
-    if (lines_grow(&sc->d_tslot, &sc->tslot_cap, n * sizeof(uint32_t)) != 0) return -1;
+    if (nslots == 0) return -1;
     t->tab = sc->d_ttab;
     t->cnt = sc->d_ttab + nslots;
-    SRE_HIP_TRY(hipMemsetAsync(t->tab, 0xFF, nslots * sizeof(uint64_t), stream));         /* SRE_LT_EMPTY */
-    SRE_HIP_TRY(hipMemsetAsync(t->cnt, 0, nslots * sizeof(uint64_t), stream));
-    static_assert(offsetof(sre_lines_info_t, tclaims) == offsetof(sre_lines_info_t, tsel) + sizeof(uint64_t)
-                      && offsetof(sre_lines_info_t, tover) == offsetof(sre_lines_info_t, tsel) + 2 * sizeof(uint64_t),
-                  "tsel, tclaims, tover are zeroed as one run");
-    SRE_HIP_TRY(hipMemsetAsync(&sc->d_linfo->tsel, 0, 3 * sizeof(uint64_t), stream));
     SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_fval, sc->d_fstart, n, t->gr.k, nslots, max_keys, tally_hash_mask(), t->tab, t->cnt,
                                         sc->d_tslot, sc->d_linfo, stream));
     if (sink_offsets(sc, &whole, n, stream) != 0) return -1;
@@ -2861,6 +2877,71 @@ sre_hip_lookup_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int d
                                        ks->nslots, ks->hash_mask, (flags & SRE_HIP_LINES_INVERT) != 0, sc->d_fval,
                                        reinterpret_cast<int64_t *>(d_keyid), keyid_cap, sc->d_linfo, stream);
     });
+}
+
+/* The line distinct (rules in sre_lines_distinct.h): the lookup's call (keyed_call), then on the device
+ * the tally's table and insert over the KEY table, which leave every line's slot and every slot's first line and count; for
+ * LAST the pass that leaves every slot's highest line; the pick pass, which clears the values of the lines the rule and the
+ * flags drop; then the filter's scan, cut, one read (its four words, the tally's three and the qualifying keys), gather and
+ * index; and the per-line arrays. */
+extern "C" SRE_API int
+sre_hip_distinct_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, const int *groups, size_t ngroups, int which,
+    size_t min_count, size_t max_count, int flags, size_t max_keys, void *d_out, size_t out_cap, uint64_t *d_keycount,
+    size_t keycount_cap, sre_int_t *d_keyline, size_t keyline_cap, sre_int_t *d_index, size_t index_cap,
+    sre_hip_distinct_info_t *info, void *hip_stream)
+{
+    static_assert(SRE_HIP_DISTINCT_FIRST == SRE_LD_FIRST && SRE_HIP_DISTINCT_LAST == SRE_LD_LAST
+                      && SRE_HIP_DISTINCT_EVERY == SRE_LD_EVERY,
+                  "sre_lines_distinct.h mirrors the public rule numbers");
+    LinesSink            sink;
+    sre_extract_groups_t gr;
+    if (which < SRE_HIP_DISTINCT_FIRST || which > SRE_HIP_DISTINCT_EVERY || !sre_ld_range_ok(min_count, max_count)
+        || (flags & ~SRE_HIP_LINES_INVERT) != 0 || max_keys < 1 || max_keys > SRE_LT_MAX_KEYS || groups == NULL || ngroups < 1
+        || ngroups > SRE_HIP_EXTRACT_MAX_FIELDS || (keycount_cap != 0 && d_keycount == NULL)
+        || (keyline_cap != 0 && d_keyline == NULL))
+    {
+        return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0;
+    if (keyed_call(sc, "line distinct", d_buf, len, delim, groups, ngroups, d_out, out_cap, d_index, index_cap, 0, 0, NULL, &sink, &gr,
+                   &n, stream) != 0)
+    {
+        return -1;
+    }
+    sre_hip_distinct_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        const bool     last = which == SRE_HIP_DISTINCT_LAST;
+        const uint64_t nslots = tally_table(sc, n, max_keys, last ? 2 : 1, 4, stream);
+        if (nslots == 0) return -1;
+        uint64_t *tab = sc->d_ttab, *cnt = tab + nslots, *lastrun = last ? cnt + nslots : NULL;
+        /* (the insert's keep pass clears the key table's entries of every line but a key's first: nothing reads them again) */
+        SRE_HIP_TRY(sre_launch_tally_insert(d_buf, sc->d_vval, sc->d_vstart, n, gr.k, nslots, max_keys, tally_hash_mask(), tab, cnt,
+                                            sc->d_tslot, sc->d_linfo, stream));
+        if (last) SRE_HIP_TRY(sre_launch_distinct_last(sc->d_tslot, n, nslots, lastrun, stream));
+        SRE_HIP_TRY(sre_launch_distinct_pick(sc->d_tslot, n, nslots, tab, cnt, lastrun, which, min_count, max_count,
+                                             (flags & SRE_HIP_LINES_INVERT) != 0, sc->d_fval, sc->d_linfo, stream));
+        if (sink_offsets(sc, &sink, n, stream) != 0) return -1;
+        if (sink_read(sc, &sink, n, &res, stream, LINFO(tsel), LINFO(tclaims), LINFO(tover), LINFO(dkept)) != 0) return -1;
+        res.nkeyed = (size_t) sc->h_linfo->tsel;
+        if (sc->h_linfo->tover != 0 || sc->h_linfo->tclaims > max_keys) {
+            /* (only the two counts of lines stand; nothing is written) */
+            res.nselected = res.need_bytes = res.nwritten = res.out_bytes = 0;
+            if (info) *info = res;
+            return SRE_HIP_TALLY_OVERFLOW;
+        }
+        res.nkeys = (size_t) sc->h_linfo->tclaims;
+        res.nkeys_kept = (size_t) sc->h_linfo->dkept;
+        if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
+        SRE_HIP_TRY(sre_launch_distinct_perline(sc->d_tslot, n, nslots, tab, cnt, d_keycount, keycount_cap,
+                                                reinterpret_cast<int64_t *>(d_keyline), keyline_cap, stream));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
 }
 
 /* The line join: the lookup's call, key groups and host waits; in the probe's place the join pass, which

@@ -55,6 +55,8 @@ typedef struct {
     uint64_t tsel;          /* lines that have a key */
     uint64_t tclaims;       /* slots of the table claimed */
     uint64_t tover;         /* not 0: more than max_keys distinct keys, or the table is full */
+    /* the line distinct (sre_hip_distinct_lines): the tally's three and one more word, read with the four (zeroed with them) */
+    uint64_t dkept;         /* distinct keys whose count is within the call's range */
     /* the line lookup (sre_hip_lookup_lines): two more words, read with the four (zeroed in front of the probe) */
     uint64_t knkeyed;       /* lines that have a key */
     uint64_t knmembers;     /* of those, lines whose key is in the set */
@@ -321,6 +323,22 @@ hipError_t sre_launch_sort_finish(const uint64_t *d_coff, uint64_t nout, uint64_
 /* rows [line, start, len, output offset, value, class] of the first min(index_cap, d_res[2]) ranks; nrows: that number */
 hipError_t sre_launch_sort_index(const uint32_t *d_lines, const uint64_t *d_cstart, const uint64_t *d_coff, const uint64_t *d_res,
     const int64_t *d_value, const int8_t *d_class, uint64_t nlines, uint64_t nrows, uint64_t index_cap, int64_t *d_index,
+    hipStream_t stream);
+/* ---- the line distinct (sre_hip_lines_distinct.hip, sre_lines_distinct.h) ---- */
+/* behind sre_launch_tally_insert over the key table (d_lslot, and the table of nslots words it took), a lane per line:
+ * d_last[slot] (nslots words, zero before) = the highest line of the slot, one atomic maximum per distinct slot of a wave */
+hipError_t sre_launch_distinct_last(const uint32_t *d_lslot, uint64_t n, uint64_t nslots, uint64_t *d_last, hipStream_t stream);
+/* behind it, in front of sre_launch_filter_offsets, a lane per line: d_fval[i] stays for a line sre_ld_picks selects from its
+ * slot's d_tab, d_cnt and (SRE_LD_LAST only; else d_last may be NULL) d_last words, and becomes 0 for every other; a line
+ * with d_lslot[i] == SRE_LT_NONE reads nothing through it.  info->dkept (zero before) += the qualifying keys, counted at
+ * their first lines, one add per workgroup */
+hipError_t sre_launch_distinct_pick(const uint32_t *d_lslot, uint64_t n, uint64_t nslots, const uint64_t *d_tab, const uint64_t *d_cnt,
+    const uint64_t *d_last, int which, uint64_t min_count, uint64_t max_count, int invert, uint64_t *d_fval,
+    sre_lines_info_t *d_info, hipStream_t stream);
+/* a lane per line: d_keycount[i] = d_cnt[slot], 0 without a slot, for i < min(keycount_cap, n); d_keyline[i] = d_tab[slot], -1
+ * without one, for i < min(keyline_cap, n).  Nothing is launched when both capacities are 0 */
+hipError_t sre_launch_distinct_perline(const uint32_t *d_lslot, uint64_t n, uint64_t nslots, const uint64_t *d_tab,
+    const uint64_t *d_cnt, uint64_t *d_keycount, uint64_t keycount_cap, int64_t *d_keyline, uint64_t keyline_cap,
     hipStream_t stream);
 /* ---- the line sort by text (sre_hip_lines_sort_text.hip, sre_lines_sort_text.h) ---- */
 /* the values pass of the sort over the texts of the ONE sort group (d_vval / d_vstart as above; d_buf of len bytes): a line with
