@@ -70,7 +70,8 @@ struct sre_hip_scanner_s {
     sre_scan_geom_t           geom;
     uint64_t                 *d_seg_first, *h_seg_first;
     sre_seg_summary_t        *d_sum;
-    sre_seg_digest_t         *d_digest;                 /* SRE_VERIFY_ONE_SEGS entries, see sre_scan_geom_t.digest */
+    sre_seg_digest_t         *d_digest;                 /* digest_cap entries, see sre_scan_geom_t.digest */
+    uint64_t                  digest_cap;
     size_t                    sum_cap;
     sre_stream_status_t      *d_status, *h_status;
     void                     *d_acc;
@@ -1044,8 +1045,8 @@ scan_geometry(sre_hip_scanner_t *sc, size_t nstreams, uint32_t init_variant, uin
     return scan_buffers(sc, nstreams, seg, nsegs);
 }
 
-/* the table-driven scanner's per-call buffers: summaries, the chain check's digest (small
- * batches, not COUNT: sets geom.digest), the capture walker's scratch */
+/* the table-driven scanner's per-call buffers: summaries, their digests (not COUNT: sets
+ * geom.digest), the capture walker's scratch */
 static int
 scan_buffers(sre_hip_scanner_t *sc, size_t nstreams, uint64_t seg, uint64_t nsegs)
 {
@@ -1056,13 +1057,22 @@ scan_buffers(sre_hip_scanner_t *sc, size_t nstreams, uint64_t seg, uint64_t nseg
         SRE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sc->d_sum), nsegs * sizeof(sre_seg_summary_t)));
         sc->sum_cap = nsegs;
     }
-    /* the digest for the one-workgroup chain check: small batches only */
+    /* FIRST / Thompson: a digest per segment (sre_scan_record.h).  The scan writes it for every segment and the
+     * record only where the digest does not say it all; the chain check reads digests alone.  Without the buffer
+     * (COUNT, or no memory for it) every record is stored and read as it is. */
     sc->geom.digest = NULL;
-    if (nsegs <= SRE_VERIFY_ONE_SEGS && sc->mode != SRE_HIP_PIKE_COUNT) {
-        if (sc->d_digest == NULL
-            && hipMalloc(reinterpret_cast<void **>(&sc->d_digest), SRE_VERIFY_ONE_SEGS * sizeof(sre_seg_digest_t)) != hipSuccess)
-        {
+    if (sc->mode != SRE_HIP_PIKE_COUNT) {
+        if (nsegs > sc->digest_cap) {
+            const uint64_t want = nsegs > SRE_VERIFY_ONE_SEGS ? nsegs : SRE_VERIFY_ONE_SEGS;
+            if (sc->d_digest) (void) hipFree(sc->d_digest);
             sc->d_digest = NULL;
+            sc->digest_cap = 0;
+            if (hipMalloc(reinterpret_cast<void **>(&sc->d_digest), want * sizeof(sre_seg_digest_t)) == hipSuccess) {
+                sc->digest_cap = want;
+            } else {
+                sc->d_digest = NULL;
+                (void) hipGetLastError();
+            }
         }
         sc->geom.digest = sc->d_digest;
     }
@@ -1686,7 +1696,13 @@ sre_hip_scan_results(sre_hip_scanner_t *sc, sre_int_t *results)
         /* ... and what the lanes of the first segments recorded */
         const size_t ns = sc->geom.nsegs < 16 ? (size_t) sc->geom.nsegs : 16;
         std::vector<sre_seg_summary_t> hs(ns);
-        if (hipMemcpy(hs.data(), sc->d_sum, ns * sizeof(sre_seg_summary_t), hipMemcpyDeviceToHost) == hipSuccess) {
+        std::vector<sre_seg_digest_t>  hd(ns);
+        const bool                     dig = sc->geom.digest != NULL;
+        if (hipMemcpy(hs.data(), sc->d_sum, ns * sizeof(sre_seg_summary_t), hipMemcpyDeviceToHost) == hipSuccess
+            && (!dig || hipMemcpy(hd.data(), sc->geom.digest, ns * sizeof(sre_seg_digest_t), hipMemcpyDeviceToHost) == hipSuccess))
+        {
+            /* (a plain segment's record is its digest: sre_scan_record.h) */
+            for (size_t k = 0; k < ns; k++) hs[k] = sre_scan_record_load(dig ? hd.data() : NULL, hs.data(), k, sc->geom.seg_bytes);
             for (size_t k = 0; k < ns; k++) {
                 fprintf(stderr, "[sregex-hip]   seg %zu: s_in %x s_out %x flags %x count %lld cur_sp %lld term %lld "
                                 "pe_pos %lld lm_pos %lld lm_sp %lld\n",
@@ -1960,7 +1976,7 @@ lines_scan_device(sre_hip_scanner_t *sc, const void *d_buf, uint64_t n, int all,
         const uint64_t i1 = sc->h_linfo->i1, nb = i1 - i0, seg = sc->h_linfo->seg, nsegs = sc->h_linfo->nsegs;
         call_begin(sc);         /* (to the diagnostics a batch is a call: tot sums them) */
         geom_device(sc, nb, seg, nsegs);
-        if (scan_buffers(sc, nb, seg, nsegs) != 0) return -1;       /* (a small batch: geom.digest) */
+        if (scan_buffers(sc, nb, seg, nsegs) != 0) return -1;       /* (not COUNT: geom.digest) */
         /* scan, chain check and captures queued as for a batch of streams */
         SRE_HIP_TRY(hipEventRecord(sc->ev0, stream));
         SRE_HIP_TRY(sre_launch_scan(sc->tab->d_tab, sc->tab->h, sc->geom, sc->d_sum, NULL, NULL, stream));

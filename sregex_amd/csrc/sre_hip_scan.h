@@ -104,48 +104,8 @@ typedef struct {
                                            without a save, in every STABLE step of the state (0: none) */
 } sre_scan_tables_t;
 
-/* what one lane learnt about its segment */
-typedef struct {
-    uint32_t s_in;          /* state assumed at the segment start (after warm-up) */
-    uint32_t s_out;         /* state at the segment end */
-    uint32_t flags;         /* SRE_SUM_* */
-    uint32_t pad;
-    /* SRE_SUM_PENDING: the search in flight at the segment end holds a match */
-    uint32_t pe_state, pe_sym;      /* state before the event's transition, its symbol */
-    int64_t  pe_pos, pe_sp;         /* event position; start of its search (-1 unknown) */
-    /* SRE_SUM_LASTEV: FIRST: last match event seen here; COUNT: last completed match */
-    uint32_t lm_state, lm_sym;
-    int64_t  lm_pos, lm_sp;
-    /* a known state shortly before that event (start of its 64-byte round), so
-     * the capture walker need not replay the segment: -1 if none */
-    int64_t  lm_apos, pe_apos;
-    uint32_t lm_astate, pe_astate;
-    int64_t  term_pos;      /* position where the scan of this stream ended, -1 none */
-    int64_t  count;         /* COUNT: searches completed with a match in this segment */
-    int64_t  cur_sp;        /* start of the search in flight at the segment end, -1 unknown */
-    /* COUNT, SRE_SUM_IN_PENDING: the pending match the lane believed it ENTERED with (from its
-     * warm-up, or the exact carry).  Equal entry states do not imply equal pending events, so the
-     * chain check compares this with the predecessor's pe_* as well. */
-    int64_t  in_pe_pos;
-    uint32_t in_pe_state, in_pe_sym;
-    /* FIRST: the byte steps [0, stable_until) of the segment, counted from its start, were
-     * STABLE steps of the entry state s_in, and so were the steps [stable_from, length) of
-     * the exit state s_out (whole 64-byte rounds; stable_until == length: the whole segment,
-     * flag SRE_SUM_STABLE). */
-    uint32_t stable_until, stable_from;
-} sre_seg_summary_t;
-
-/* bits: [1] SRE_SUM_TERM [2] SRE_SUM_LASTEV [3] cur_sp >= 0 [4] not SRE_SUM_STABLE (as verify_one_stream keeps them) */
-typedef struct sre_seg_digest_s {
-    uint32_t s_in, s_out, bits, count;
-} sre_seg_digest_t;
-
-#define SRE_SUM_PENDING   1u
-#define SRE_SUM_TERM      2u   /* the scan of this stream ended inside this segment */
-#define SRE_SUM_LASTEV    4u
-#define SRE_SUM_ERROR     8u   /* COUNT: ... and the iteration ended with SRE_ERROR */
-#define SRE_SUM_IN_PENDING 16u /* COUNT: the lane entered its segment holding a pending match (in_pe_*) */
-#define SRE_SUM_STABLE    32u  /* every byte step of the segment was a STABLE step of s_in == s_out */
+/* what one lane learnt about its segment (sre_seg_summary_t), its digest, and how the two are kept and read */
+#include "sre_scan_record.h"
 
 /* COUNT: an empty match ended on the segment's last byte boundary, so the
  * caller's one-byte skip (sre_vm_pike.c:179-196) falls on the first byte of the
@@ -243,9 +203,11 @@ typedef struct {
      * the reference arrives at offset 0 (bit 0 of sre_nfa_summary_t.last_clean's mode), whether
      * the buffer ends before the stream does.  NULL: init_variant / flags hold for every stream. */
     const uint8_t *sflags;
-    /* FIRST / Thompson: what the chain check of a small batch reads of every summary, 16 bytes a segment
-     * (sre_seg_digest_t; NULL: none is written).  One workgroup checks up to 8192 segments: out of the
-     * 144-byte summaries that was 14 us for the 4096 segments of a 1 MiB chunk. */
+    /* FIRST / Thompson: a digest per segment, nsegs entries (sre_scan_record.h; NULL: none, every record is stored
+     * whole: COUNT, stream sets).  The scan kernel writes it for every segment, coalesced, and the 136-byte record
+     * only where the digest does not say it all; the chain check reads digests alone (one workgroup checks up to
+     * 8192 segments: out of the summaries that was 14 us for the 4096 segments of a 1 MiB chunk; grid-wide, three
+     * passes over 33 MB of records for a 4 GiB stream), every other reader goes through sre_scan_record_load(). */
     struct sre_seg_digest_s *digest;
     /* stream sets (sre_hip_streams.hip): per stream, instead of entry_state / init_variant and the
      * SRE_GEOM_CONTINUES / SRE_GEOM_NO_EOF bits — SRE_SENTRY_*: the automaton state in front of the

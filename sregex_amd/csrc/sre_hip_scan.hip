@@ -601,6 +601,26 @@ scan_split_of(int mode, int bits, bool wide, bool grow)
 #define SRE_COUNT_BLOCKS 3          /* workgroups per CU the COUNT kernel's registers are budgeted for */
 #endif
 
+/* SRE_SCAN_COMPACT: 0 is the A/B build that stores every record and runs the chain check on the records, as before
+ * the digests (profiles/scan_launch_rate.json) */
+#ifndef SRE_SCAN_COMPACT
+#define SRE_SCAN_COMPACT 1
+#endif
+
+/* the digests of a scan's records, NULL where every record is stored (COUNT; no digest buffer) */
+template <int MODE>
+__device__ inline sre_seg_digest_t *
+scan_digest(const sre_scan_geom_t &G)
+{
+    return (SRE_SCAN_COMPACT && MODE != SRE_HIP_PIKE_COUNT) ? G.digest : nullptr;
+}
+/* ... for the kernels behind the scan, which take the mode at run time */
+__device__ inline sre_scan_records_t
+scan_records(const sre_scan_geom_t &G, const sre_seg_summary_t *sum)
+{
+    return sre_scan_records_t{sum, SRE_SCAN_COMPACT ? G.digest : nullptr, G.seg_bytes};
+}
+
 /*
  * BITS = class bits per input byte: one fast-table lookup advances 8 / BITS
  * bytes (BITS == 8: the index is the byte itself).  A lane consumes
@@ -743,6 +763,8 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
 
     int64_t  seg_a = 0, seg_b = 0;
     uint32_t s_in = 0, seed = 0;
+    /* (records of earlier rounds, wherever they are kept: sre_scan_record.h) */
+    const sre_scan_records_t rec{sum, scan_digest<MODE>(G), G.seg_bytes};
     /* COUNT: the pending match this lane enters its segment with (see sre_seg_summary_t) */
     int64_t  in_pe_pos = -1;
     uint32_t in_pe_state = 0, in_pe_sym = 0;
@@ -769,7 +791,7 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
             w.cur_sp = 0;
         } else if (lo_s >= 0 && (int64_t) k == lo_s) {
             /* exact carry from the verified predecessor */
-            const sre_seg_summary_t &c = sum[g - 1];
+            const sre_seg_summary_t c = rec[g - 1];
             w.st = c.s_out & ~SRE_STATE_SKIP;
             w.set(F_SKIP_NEXT, MODE == SRE_HIP_PIKE_COUNT && (c.s_out & SRE_STATE_SKIP) != 0);
             w.cur_sp = c.cur_sp;
@@ -796,7 +818,7 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
             w.st = entry[g];
             if (MODE == SRE_HIP_PIKE_COUNT && lo_s > 0 && (T.state_flags[w.st] & 1)) {
                 /* (COUNT: the match such a state holds is taken from the verified prefix, as below) */
-                const sre_seg_summary_t &c = sum[geom_first(G, sidx) + lo_s - 1];
+                const sre_seg_summary_t c = rec[geom_first(G, sidx) + lo_s - 1];
                 if (c.flags & SRE_SUM_PENDING) {
                     w.fl |= F_HAS_EV | F_IN_PENDING;
                     w.ev_state = c.pe_state;
@@ -819,7 +841,7 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
             warm = true;
             seed = T.init[0];
             if (lo_s > 0) {
-                const sre_seg_summary_t &c = sum[geom_first(G, sidx) + lo_s - 1];
+                const sre_seg_summary_t c = rec[geom_first(G, sidx) + lo_s - 1];
                 const uint32_t           cs = c.s_out & ~SRE_STATE_SKIP;
                 if (cs != 0) {
                     if (!(MODE == SRE_HIP_PIKE_COUNT && (T.state_flags[cs] & 1))) {
@@ -1268,15 +1290,16 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     out.lm_astate = w.lm_astate;
     out.pe_apos = w.ev_apos;
     out.pe_astate = w.ev_astate;
-    sum[g] = out;
-    if (MODE != SRE_HIP_PIKE_COUNT && G.digest != nullptr) {
-        sre_seg_digest_t dg;
-        dg.s_in = out.s_in;
-        dg.s_out = out.s_out;
-        dg.bits = ((out.flags & SRE_SUM_TERM) ? 2u : 0u) | ((out.flags & SRE_SUM_LASTEV) ? 4u : 0u) | (out.cur_sp >= 0 ? 8u : 0u)
-                  | ((out.flags & SRE_SUM_STABLE) ? 0u : 16u);
-        dg.count = (uint32_t) out.count;
-        G.digest[g] = dg;
+    /* FIRST / Thompson with a digest: the digest always (16 bytes, coalesced), the record itself only where the
+     * digest does not give all of it back (sre_scan_record.h) */
+    sre_seg_digest_t *const dig = scan_digest<MODE>(G);
+    if (dig != nullptr) {
+        bool                   plain;
+        const sre_seg_digest_t dg = sre_scan_record_pack(out, G.seg_bytes, &plain);
+        dig[g] = dg;
+        if (!plain) sum[g] = out;
+    } else {
+        sum[g] = out;
     }
 }
 
@@ -1428,7 +1451,7 @@ sre_k_fn_resolve(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum,
     if (s >= G.nstreams || status[s].done || status[s].first_bad < 1) return;
     const uint64_t first = geom_first(G, s), g_hi = geom_first(G, s + 1);
     uint64_t       g = first + (uint64_t) status[s].first_bad;
-    uint32_t       v = sum[g - 1].s_out & 63u;          /* the verified prefix's exit state */
+    uint32_t       v = scan_records(G, sum)[g - 1].s_out & 63u;          /* the verified prefix's exit state */
     while (g < g_hi) {
         if (g % SRE_FN_CHUNK == 0 && g + SRE_FN_CHUNK <= g_hi) {
             chunk_entry[g / SRE_FN_CHUNK] = (uint8_t) v;
@@ -1483,22 +1506,30 @@ sre_k_verify_a(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum, Ver
     unsigned long long kb = ~0ull, ke = ~0ull;      /* this lane's candidates for acc[s].bad / .end */
     if (valid) {
         const uint64_t k = g - geom_first(G, s);
-        const uint32_t s_in = sum[g].s_in;
-        bool           bad = s_in == 0xffffffffu;
-        if (k > 0) {
-            const sre_seg_summary_t &p = sum[g - 1], &c = sum[g];
-            if (s_in != p.s_out) bad = true;
-            if (mode == SRE_HIP_PIKE_COUNT) {
-                /* the same entry state can hold different pending matches */
-                const bool pp = (p.flags & SRE_SUM_PENDING) != 0, cp = (c.flags & SRE_SUM_IN_PENDING) != 0;
-                if (pp != cp) bad = true;
-                if (pp && cp && (p.pe_pos != c.in_pe_pos || p.pe_state != c.in_pe_state || p.pe_sym != c.in_pe_sym)) {
-                    bad = true;
+        const sre_seg_digest_t *const dig = mode == SRE_HIP_PIKE_COUNT ? nullptr : scan_records(G, sum).dig;
+        if (dig != nullptr) {
+            /* FIRST / Thompson: all the chain check compares is in the digests, 16 bytes a segment */
+            const sre_seg_digest_t c = dig[g];
+            if (c.s_in == 0xffffffffu || (k > 0 && c.s_in != dig[g - 1].s_out)) kb = k;
+            if (c.bits & SRE_DIGEST_TERM) ke = k;
+        } else {
+            const uint32_t s_in = sum[g].s_in;
+            bool           bad = s_in == 0xffffffffu;
+            if (k > 0) {
+                const sre_seg_summary_t &p = sum[g - 1], &c = sum[g];
+                if (s_in != p.s_out) bad = true;
+                if (mode == SRE_HIP_PIKE_COUNT) {
+                    /* the same entry state can hold different pending matches */
+                    const bool pp = (p.flags & SRE_SUM_PENDING) != 0, cp = (c.flags & SRE_SUM_IN_PENDING) != 0;
+                    if (pp != cp) bad = true;
+                    if (pp && cp && (p.pe_pos != c.in_pe_pos || p.pe_state != c.in_pe_state || p.pe_sym != c.in_pe_sym)) {
+                        bad = true;
+                    }
                 }
             }
+            if (bad) kb = k;
+            if (sum[g].flags & SRE_SUM_TERM) ke = k;
         }
-        if (bad) kb = k;
-        if (sum[g].flags & SRE_SUM_TERM) ke = k;
     }
     /* One atomic per wave at most, and none when the word already holds less: with a match in reach of
      * every segment (`foo` over "foo foo ..", first match) each of the 262 144 lanes of a 64 MiB stream
@@ -1541,6 +1572,7 @@ sre_k_verify_b(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum, Ver
     /* whole span inside one stream (the usual case): reduce in the wave first — a
      * shared-memory atomic per lane serialises 256 ways when every segment counts */
     unsigned long long my_count = 0, my_ev = 0, my_sp = 0;
+    const sre_seg_digest_t *const dig = scan_records(G, sum).dig;
     for (uint32_t it = 0; it < SRE_VERIFY_SPAN / 256; it++) {
         const uint64_t g = g0 + it * 256u + threadIdx.x;
         if (g >= G.nsegs) break;
@@ -1552,15 +1584,28 @@ sre_k_verify_b(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum, Ver
         if (end > nseg) end = nseg;
         const uint64_t limit = end < bad ? end + 1 : bad;
         if (k < limit) {
-            const sre_seg_summary_t &c = sum[g];
-            if (uniform) {
-                my_count += (unsigned long long) c.count;
-                if (c.flags & SRE_SUM_LASTEV) my_ev = (unsigned long long) k + 1;
-                if (c.cur_sp >= 0) my_sp = (unsigned long long) k + 1;     /* latest segment at whose end a search start is known */
+            /* (with digests — never COUNT — from them alone: count, LASTEV and "a search start is known") */
+            unsigned long long c_count;
+            bool               c_ev, c_sp;
+            if (dig != nullptr) {
+                const sre_seg_digest_t c = dig[g];
+                c_count = c.count;
+                c_ev = (c.bits & SRE_DIGEST_LASTEV) != 0;
+                c_sp = (c.bits & SRE_DIGEST_SP) != 0;
             } else {
-                if (c.count) atomicAdd(&acc[s].count, (unsigned long long) c.count);
-                if (c.flags & SRE_SUM_LASTEV) atomicMax(&acc[s].evseg, (unsigned long long) k + 1);
-                if (c.cur_sp >= 0) atomicMax(&acc[s].spseg, (unsigned long long) k + 1);
+                const sre_seg_summary_t &c = sum[g];
+                c_count = (unsigned long long) c.count;
+                c_ev = (c.flags & SRE_SUM_LASTEV) != 0;
+                c_sp = c.cur_sp >= 0;
+            }
+            if (uniform) {
+                my_count += c_count;
+                if (c_ev) my_ev = (unsigned long long) k + 1;
+                if (c_sp) my_sp = (unsigned long long) k + 1;     /* latest segment at whose end a search start is known */
+            } else {
+                if (c_count) atomicAdd(&acc[s].count, c_count);
+                if (c_ev) atomicMax(&acc[s].evseg, (unsigned long long) k + 1);
+                if (c_sp) atomicMax(&acc[s].spseg, (unsigned long long) k + 1);
             }
         }
     }
@@ -1600,6 +1645,7 @@ sre_k_verify_b2(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum, Ve
     if (threadIdx.x == 0) sh_max = sh_max_end = 0;
     __syncthreads();
     unsigned long long mine = 0, mine_end = 0;
+    const sre_seg_digest_t *const dig = scan_records(G, sum).dig;
     for (uint32_t it = 0; it < SRE_VERIFY_SPAN / 256; it++) {
         const uint64_t g = g0 + it * 256u + threadIdx.x;
         if (g >= G.nsegs) break;
@@ -1607,7 +1653,7 @@ sre_k_verify_b2(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum, Ve
         const uint64_t k = g - geom_first(G, s);
         const uint64_t evseg = acc[s].evseg;        /* 1 + the event's segment, 0 none */
         const uint64_t nseg = geom_first(G, s + 1) - geom_first(G, s);
-        if (!(sum[g].flags & SRE_SUM_STABLE)) {
+        if (dig != nullptr ? (dig[g].bits & SRE_DIGEST_UNSTABLE) != 0 : !(sum[g].flags & SRE_SUM_STABLE)) {
             unsigned long long m1 = 0, m2 = 0;
             if (evseg != 0 && k + 1 < evseg) m1 = k + 1;
             /* (streaming: the walks that start at the end of a chunk; its last segment is
@@ -1644,7 +1690,7 @@ sre_k_verify_b2(sre_scan_geom_t G, const sre_seg_summary_t *__restrict__ sum, Ve
  * stream's first summary */
 #define SRE_EV_SP_SEARCH ((int64_t) -2)
 __device__ inline sre_stream_status_t
-assemble_status(const sre_scan_tables_t &T, const sre_seg_summary_t *__restrict__ sum, uint64_t nseg, const VerifyAcc &acc,
+assemble_status(const sre_scan_tables_t &T, const sre_scan_records_t sum, uint64_t nseg, const VerifyAcc &acc,
                 bool defer_search = false)
 {
     uint64_t       bad = acc.bad, end = acc.end;
@@ -1672,7 +1718,7 @@ assemble_status(const sre_scan_tables_t &T, const sre_seg_summary_t *__restrict_
     st.unst_seg = acc.unst ? (int64_t) acc.unst - 1 : -1;
     st.unst_end = acc.unst_end ? (int64_t) acc.unst_end - 1 : -1;
     if (done && evseg > 0) {
-        const sre_seg_summary_t &c = sum[evseg - 1];
+        const sre_seg_summary_t c = sum[evseg - 1];
         st.ev_apos = c.lm_apos;
         st.ev_astate = c.lm_astate;
         st.ev_state = c.lm_state;
@@ -1696,8 +1742,9 @@ assemble_status(const sre_scan_tables_t &T, const sre_seg_summary_t *__restrict_
                 sp = SRE_EV_SP_SEARCH;      /* the caller looks for it with the whole wave (sre_k_verify_c) */
             } else {
                 for (int64_t q = (int64_t) evseg - 2; q >= 0; q--) {
-                    if (sum[q].cur_sp >= 0) {
-                        sp = sum[q].cur_sp;
+                    const int64_t q_sp = sum[q].cur_sp;
+                    if (q_sp >= 0) {
+                        sp = q_sp;
                         break;
                     }
                 }
@@ -1728,7 +1775,7 @@ sre_k_verify_c(sre_scan_tables_t T, sre_scan_geom_t G, const sre_seg_summary_t *
         accs[s].count = accs[s].evseg = accs[s].spseg = accs[s].unst = accs[s].unst_end = 0;
         first = geom_first(G, s);
         const uint64_t nseg = geom_first(G, s + 1) - first;
-        st = assemble_status(T, sum + first, nseg, acc, true);
+        st = assemble_status(T, scan_records(G, sum) + first, nseg, acc, true);
     }
     /* COUNT: the search of the last match began in an earlier segment and a later one knows a start too
      * (`a+` over a stream of a: the match spans it, the search behind it starts at its end): the latest
@@ -1747,7 +1794,7 @@ sre_k_verify_c(sre_scan_tables_t T, sre_scan_geom_t G, const sre_seg_summary_t *
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const int64_t q = hi - (int64_t) lane - 64 * j;
-                v[j] = q >= 0 ? sum[f + (uint64_t) q].cur_sp : (int64_t) -1;
+                v[j] = q >= 0 ? scan_records(G, sum)[f + (uint64_t) q].cur_sp : (int64_t) -1;
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -1774,10 +1821,11 @@ sre_k_verify_c(sre_scan_tables_t T, sre_scan_geom_t G, const sre_seg_summary_t *
 
 template <int NT>
 __device__ void
-verify_one_stream(const sre_scan_tables_t &T, const sre_seg_summary_t *__restrict__ sum, uint64_t nseg,
-                  sre_stream_status_t *__restrict__ status, VerifyAcc *sh_acc, sre_stream_status_t *out,
-                  const sre_seg_digest_t *__restrict__ dig = nullptr)
+verify_one_stream(const sre_scan_tables_t &T, const sre_scan_records_t R, uint64_t nseg,
+                  sre_stream_status_t *__restrict__ status, VerifyAcc *sh_acc, sre_stream_status_t *out)
 {
+    const sre_seg_summary_t *const sum = R.sum;
+    const sre_seg_digest_t *const  dig = R.dig;
     constexpr int  PER = SRE_VERIFY_ONE_MAX / NT;
     const uint32_t tid = threadIdx.x;
     if (tid == 0) {
@@ -1882,7 +1930,7 @@ verify_one_stream(const sre_scan_tables_t &T, const sre_seg_summary_t *__restric
     }
     __syncthreads();
     if (tid == 0) {
-        *out = assemble_status(T, sum, nseg, *sh_acc);
+        *out = assemble_status(T, R, nseg, *sh_acc);
         *status = *out;
     }
     __syncthreads();
@@ -1896,7 +1944,7 @@ verify_one_stream(const sre_scan_tables_t &T, const sre_seg_summary_t *__restric
  * segment on that ends with cur_sp == sp.  One search per stream (FIRST /
  * Thompson): the lane of sp's segment itself. */
 __device__ inline int64_t
-first_valid_segment(const sre_seg_summary_t *sum, int64_t sp, int64_t seg_bytes, int64_t ev_seg)
+first_valid_segment(const sre_scan_records_t sum, int64_t sp, int64_t seg_bytes, int64_t ev_seg)
 {
     for (int64_t k = sp / seg_bytes; k <= ev_seg; k++) {
         if (sum[k].cur_sp == sp) return k + 1;
@@ -1918,7 +1966,7 @@ first_valid_segment(const sre_seg_summary_t *sum, int64_t sp, int64_t seg_bytes,
  * a call lives in scratch memory — a microsecond per field access) */
 struct Tracer {
     const sre_scan_tables_t *T;         /* cls / trans / fast point into LDS */
-    const sre_seg_summary_t *sum;       /* this stream's summaries */
+    sre_scan_records_t       sum;       /* this stream's records */
     const uint8_t           *data;
     int64_t                  n, sp;
     uint32_t                 seg_bytes, init_state;
@@ -2203,7 +2251,7 @@ sre_k_lineage_maps(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G
     const uint8_t *data = geom_ptr(G, s);
     const int64_t  n = (int64_t) geom_len(G, s);
     int64_t        lo = k * (int64_t) G.seg_bytes, hi = lo + G.seg_bytes;
-    uint32_t       cur = sum[g].s_in & ~SRE_STATE_SKIP;
+    uint32_t       cur = scan_records(G, sum)[g].s_in & ~SRE_STATE_SKIP;
     if (hi > n) hi = n;
     if (k == st.ev_seg && st.ev_pos < hi) hi = st.ev_pos;      /* list at the event position */
     if (sp >= lo) {
@@ -2578,7 +2626,7 @@ sre_k_captures(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     if (NT != 64) {
         __shared__ VerifyAcc sh_acc;
         __shared__ sre_stream_status_t sh_st;
-        verify_one_stream<NT>(Ts, sum, geom_first(G, 1), status, &sh_acc, &sh_st, G.digest);
+        verify_one_stream<NT>(Ts, scan_records(G, sum), geom_first(G, 1), status, &sh_acc, &sh_st);
     }
     /* one WORKGROUP per stream, lane 0 walks: the walks of a batch run side by side on
      * different CUs instead of as 64 divergent lanes of one wave (128 streams: 51 us -> see
@@ -2618,7 +2666,7 @@ sre_k_captures(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
 
     Tracer tr;
     tr.T = &T;
-    tr.sum = sum + geom_first(G, s);
+    tr.sum = scan_records(G, sum) + geom_first(G, s);
     tr.data = geom_ptr(G, s);
     tr.n = (int64_t) geom_len(G, s);
     tr.sp = st.ev_sp;
@@ -2757,7 +2805,7 @@ struct TailCtxRow {
 struct TailChunk {
     const uint8_t           *data;
     int64_t                  n, base;
-    const sre_seg_summary_t *sum;
+    sre_scan_records_t       sum;
     uint64_t                 nseg;
     uint32_t                 seg_bytes, variant, entry_state, ovec_slots;
     bool                     continues, eof;
@@ -2775,7 +2823,7 @@ stream_tail_body(const sre_scan_tables_t &T, const sre_scan_tables_t *__restrict
                  const TailChunk &K, const Ctx &ctx, sre_stream_result_t *__restrict__ res)
 {
     int64_t                  rc_out = RC_ERROR;
-    const sre_seg_summary_t *sum = K.sum;
+    const sre_scan_records_t sum = K.sum;
     const uint64_t           nseg = K.nseg;
     const int64_t            base = K.base;
     const bool               eof = K.eof;
@@ -2993,7 +3041,7 @@ sre_k_stream_tail(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     const unsigned long long dbg_t1 = wall_clock64();
 #endif
     const uint64_t             nseg = geom_first(G, 1) - geom_first(G, 0);
-    if (verify) verify_one_stream<SRE_TAIL_THREADS>(Ts, sum, nseg, status, &sh_acc, &sh_st, G.digest);
+    if (verify) verify_one_stream<SRE_TAIL_THREADS>(Ts, scan_records(G, sum), nseg, status, &sh_acc, &sh_st);
 #ifdef SRE_DEBUG_TAIL
     const unsigned long long dbg_t2 = wall_clock64();
 #endif
@@ -3005,7 +3053,7 @@ sre_k_stream_tail(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     K.data = geom_ptr(G, 0);
     K.n = (int64_t) geom_len(G, 0);
     K.base = base;
-    K.sum = sum;
+    K.sum = scan_records(G, sum);
     K.nseg = nseg;
     K.seg_bytes = G.seg_bytes;
     K.variant = G.init_variant;
@@ -3067,7 +3115,7 @@ sre_k_streams_tail(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G
         K.data = G.streams[s];
         K.n = (int64_t) G.lens[s];
         K.base = processed;
-        K.sum = sum + first;
+        K.sum = scan_records(G, sum) + first;
         K.nseg = nseg;
         K.seg_bytes = G.seg_bytes;
         K.variant = 0;                          /* one search per stream: it starts at offset 0 of the stream */
