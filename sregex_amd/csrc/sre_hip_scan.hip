@@ -594,6 +594,78 @@ scan_split_of(int mode, int bits, bool wide, bool grow)
     return (bits == 4 && !wide && grow) ? 4 : 1;
 #endif
 }
+/* SRE_SCAN_PRIO: how a scan wave sets its issue priority (s_setprio; the SIMD's arbiter serves priority first, age
+ * second — four workgroups of different age share every SIMD for the whole launch).
+ *   0  never (the arbiter goes by age alone)
+ *   1  phase: 1 from the top of a round until the next stage's loads are issued, 0 for the walk behind them
+ *   2  turn:  a level 0..2 that moves on every SRE_SCAN_PRIO_TURN rounds, offset by SRE_SCAN_PRIO_KEY(blockIdx.x) so
+ *             that the workgroups sharing a CU hold different levels and each holds every level equally often
+ *   3  both:  the turn's level (0..1) during the walk, one above it in the load-gating phase
+ * Level 3 stays with the kernels behind the scan (SRE_TAIL_PRIO); the epilogue runs at 0.  Undefined: scan_prio_of()
+ * picks per instantiation as scan_split_of() does; -DSRE_SCAN_PRIO=P builds every instantiation with P for A/B runs.
+ * Measured with tools/scan_stamps.py and tools/ab_bench.py: DESIGN.md 4.3, profiles/scan_prio_*. */
+#ifndef SRE_SCAN_PRIO_TURN
+#define SRE_SCAN_PRIO_TURN 8
+#endif
+#ifndef SRE_SCAN_PRIO_KEY
+/* workgroups b and b + 256 k share a CU of a 256-CU device (MI355X) when a launch fits the chip in one go: on every CU
+ * of both stamped shapes the co-resident workgroups differ in b / 256 and in no other function tried
+ * (profiles/scan_prio_stamps.json, key_functions).  On another CU count, or in a launch of several rounds, workgroups
+ * sharing a CU may hold the same level: the turn policies then do less, results do not depend on it. */
+#define SRE_SCAN_PRIO_KEY(b) ((b) / 256u)
+#endif
+constexpr int
+scan_prio_of(int mode, int bits, bool wide, bool grow)
+{
+#ifdef SRE_SCAN_PRIO
+    (void) mode; (void) bits; (void) wide; (void) grow;
+    return SRE_SCAN_PRIO;
+#else
+    /* a policy only where a workload of bench.py separates from policy 0 in two same-box calls and none on the form
+     * is slower (figures: DESIGN.md 4.3, profiles/scan_prio_rate.json); ties between policies go to the simpler one.
+     * FIRST / Thompson, 2 and 4 bits (headline, 128 streams, cfg2m, densef; cfg4): phase.  COUNT GROW wide at 1 and
+     * 2 bits (words; dense, floor): turn — phase loses 2 % on floor.  COUNT 4-bit narrow GROW (cfg3) moves with no
+     * policy; the other forms run no workload of bench.py. */
+    if (mode != SRE_HIP_PIKE_COUNT) return ((bits == 2 && wide && !grow) || (bits == 4 && !wide && !grow)) ? 1 : 0;
+    return (grow && wide && (bits == 1 || bits == 2)) ? 2 : 0;
+#endif
+}
+/* s_setprio takes an immediate and ignores EXEC: `level` must be wave-uniform (scalar branches around the three forms) */
+__device__ inline void
+scan_setprio(const uint32_t level)
+{
+    if (level == 0) __builtin_amdgcn_s_setprio(0);
+    else if (level == 1) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(2);
+}
+
+/* SRE_SCAN_STAMPS=1 (measurement build, tools/scan_stamps.py): lane 0 of every sre_k_scan workgroup leaves one record
+ * of when and where it ran in the buffer given to sre_hip_debug_scan_stamps(); records are taken in start order over
+ * all launches since the buffer was set, a null buffer stores nothing. */
+#ifndef SRE_SCAN_STAMPS
+#define SRE_SCAN_STAMPS 0
+#endif
+#if SRE_SCAN_STAMPS
+struct sre_scan_stamp_t {
+    uint32_t block, grid;           /* blockIdx.x, gridDim.x */
+    uint32_t hw_id, xcc_id;         /* the HW_ID and XCC_ID registers as read (CU, SE, SIMD ...: decoded by the tool) */
+    uint64_t t_entry, t_tables, t_end;      /* wall_clock64(): entry, tables copied (before the first load), end */
+};
+__device__ sre_scan_stamp_t *sre_scan_stamp_buf;
+__device__ uint32_t          sre_scan_stamp_cap, sre_scan_stamp_n;
+
+extern "C" __attribute__((visibility("default"))) hipError_t
+sre_hip_debug_scan_stamps(void *buf, uint32_t cap)
+{
+    const uint32_t zero = 0;
+    hipError_t     e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(sre_scan_stamp_n), &zero, sizeof zero);
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(sre_scan_stamp_cap), &cap, sizeof cap);
+    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(sre_scan_stamp_buf), &buf, sizeof buf);
+    return e;
+}
+#endif
+
 #ifndef SRE_FIRST_BLOCKS
 #define SRE_FIRST_BLOCKS 4          /* workgroups per CU the FIRST / Thompson kernels' registers are budgeted for */
 #endif
@@ -650,6 +722,22 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     __shared__ sre_scan_tables_t Ts;
 
     const uint32_t tid = threadIdx.x;
+#if SRE_SCAN_STAMPS
+    /* lane 0's record, in start order; bounded by the capacity the host gave with the buffer */
+    sre_scan_stamp_t *stamp = nullptr;
+    if (tid == 0 && sre_scan_stamp_buf != nullptr) {
+        const uint32_t slot = atomicAdd(&sre_scan_stamp_n, 1u);
+        if (slot < sre_scan_stamp_cap) {
+            stamp = sre_scan_stamp_buf + slot;
+            stamp->block = blockIdx.x;
+            stamp->grid = gridDim.x;
+            stamp->hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);       /* HW_ID, 32 bits */
+            stamp->xcc_id = __builtin_amdgcn_s_getreg((31 << 11) | 20);     /* XCC_ID */
+            stamp->t_entry = wall_clock64();
+            stamp->t_tables = stamp->t_end = 0;
+        }
+    }
+#endif
     /* LDS: [fast table: states, trap row, shadow rows][class map 256][transitions, 2 B each]
      *      [state flags][tile] */
     const uint32_t nst = tabp->nstates, nrows = tabp->fast_rows, nsh = tabp->nshadow;
@@ -997,8 +1085,23 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     static_assert(SPLIT == 1 || SPLIT == 2 || SPLIT == 4, "SRE_SCAN_SPLIT is 1, 2 or 4");
     /* the split walk's throttle, one count per wave: rounds still to be walked serially */
     uint32_t           hold = 0;
+    constexpr int      PRIO = scan_prio_of(MODE, BITS, WIDE, GROW);
+    static_assert(PRIO >= 0 && PRIO <= 3, "SRE_SCAN_PRIO is 0, 1, 2 or 3");
+    /* the wave's level in stage s under the turn policies (wave-uniform: the stage counter and blockIdx.x) */
+    const uint32_t     prio_key = PRIO >= 2 ? __builtin_amdgcn_readfirstlane(SRE_SCAN_PRIO_KEY(blockIdx.x)) : 0u;
+    auto turn_level = [&](const uint32_t s) __attribute__((always_inline)) -> uint32_t {
+        const uint32_t t = s / SRE_SCAN_PRIO_TURN + prio_key;
+        return PRIO == 2 ? t % 3u : t & 1u;
+    };
     __syncthreads();                        /* row tables are complete */
+#if SRE_SCAN_STAMPS
+    if (stamp != nullptr) stamp->t_tables = wall_clock64();
+#endif
     auto round = [&](const uint32_t s, uint4 (&regs)[4]) __attribute__((always_inline)) {
+        /* the load-gating phase: wait for the staged pieces, classify them, issue the next stage's loads */
+        if (PRIO == 1) __builtin_amdgcn_s_setprio(1);
+        if (PRIO == 2 && s % SRE_SCAN_PRIO_TURN == 0) scan_setprio(turn_level(s));
+        if (PRIO == 3) scan_setprio(turn_level(s) + 1u);
         if (SPLIT > 1) {
             /* a wave pays for the one lane whose guess misses: after such a round it keeps to the serial walk for
              * SRE_SCAN_SPLIT_HOLD rounds, then tries again (all lanes meet here, the count stays wave-uniform) */
@@ -1018,6 +1121,9 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
         __builtin_amdgcn_wave_barrier();
         /* the next stage's HBM loads fly while this round is consumed from LDS */
         if (s + DIST <= nrounds) tile_fetch(regs, rows, tid, s + DIST);
+        /* ... the walk runs under the loads' flight */
+        if (PRIO == 1) __builtin_amdgcn_s_setprio(0);
+        if (PRIO == 3) scan_setprio(turn_level(s));
 
         if (s < lag || s - lag >= nrounds) return;
         const uint32_t r = s - lag;                     /* this lane's round */
@@ -1243,6 +1349,10 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
         }
     }
 
+    if (PRIO >= 2) __builtin_amdgcn_s_setprio(0);       /* the epilogue runs at priority 0 */
+#if SRE_SCAN_STAMPS
+    if (!active && stamp != nullptr) stamp->t_end = wall_clock64();
+#endif
     if (!active) return;
 
     /* the lane that owns the end of the stream performs the EOF step(s) — unless more
@@ -1301,6 +1411,9 @@ sre_k_scan(const sre_scan_tables_t *__restrict__ tabp, sre_scan_geom_t G,
     } else {
         sum[g] = out;
     }
+#if SRE_SCAN_STAMPS
+    if (stamp != nullptr) stamp->t_end = wall_clock64();
+#endif
 }
 
 /* ============================================================ exact entry states */
