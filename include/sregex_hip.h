@@ -369,6 +369,92 @@ SRE_API int sre_hip_filter_lines_context(sre_hip_scanner_t *sc, const void *d_bu
     int flags, size_t before, size_t after, void *d_out, size_t out_cap,
     sre_int_t *d_index, size_t index_cap, sre_hip_context_info_t *info, void *hip_stream);
 
+/* ---- line fold: continuation lines joined into multi-line records ---- */
+
+enum { SRE_HIP_FOLD_NEXT = 8 };   /* a marked line continues into the FOLLOWING line (default: it belongs to the line in front of it) */
+
+typedef struct {
+    size_t nlines, nmarked, nrecords, longest, need_bytes, nwritten, out_bytes;
+} sre_hip_fold_info_t;
+
+/*
+ * Line fold: the lines of d_buf joined into multi-line records, from one device buffer to
+ * another (logstash's multiline codec, Filebeat's multiline.pattern / negate / match, Fluent
+ * Bit's multiline parser, awk '/^[0-9]{4}-/{if (r) print r; r=$0; next} {r = r "\x01" $0}').
+ * A stack trace, a wrapped message or a pretty-printed object becomes ONE line of the output,
+ * its source lines separated by the byte `join`, so that every other line call sees it as one
+ * record.  The split of d_buf, the matching of every line and the engine a scanner routes to
+ * are exactly those of sre_hip_filter_lines on the same (sc, d_buf, len, delim): only match /
+ * no match of a line is used, and every scanner mode and every engine route is accepted.
+ *
+ * The rule, over the n lines of the split.  Line i is MARKED when it has a match (its rc is not
+ * SRE_DECLINED), with SRE_HIP_LINES_INVERT when it has none.
+ *   - default (logstash what => previous): a marked line is a continuation of the record in
+ *     front of it.  Line i is a natural head when i == 0 or line i is not marked.
+ *   - SRE_HIP_FOLD_NEXT (what => next): a marked line is joined to the line behind it.  Line i is
+ *     a natural head when i == 0 or line i - 1 is not marked.
+ * With h(i) the nearest natural head at or in front of line i (line 0 always is one), line i is
+ * a HEAD when it is a natural head, or when max_lines != 0 and (i - h(i)) % max_lines == 0:
+ * max_lines caps the lines of a record and splits a runaway record into pieces of at most
+ * max_lines lines; 0 means no cap.  A RECORD is a head and the lines up to the next head.
+ *
+ * The four combinations of logstash's pattern / negate / what:
+ *   - lines that do not start with a timestamp belong to the previous line:
+ *     pattern ^\d{4}-\d\d-\d\d, flags SRE_HIP_LINES_INVERT;
+ *   - indented lines and "Caused by:" belong to the previous line:
+ *     pattern ^(\s|Caused by:), flags 0;
+ *   - a line ending in a backslash continues into the next:
+ *     pattern \\$, flags SRE_HIP_FOLD_NEXT;
+ *   - everything up to a terminator line is one record:
+ *     the terminator's pattern, flags SRE_HIP_FOLD_NEXT | SRE_HIP_LINES_INVERT.
+ * Any flag bit outside SRE_HIP_LINES_INVERT | SRE_HIP_FOLD_NEXT returns -1.
+ *
+ * Output.  d_out is a DEVICE pointer at any alignment to out_cap bytes that do not overlap
+ * [d_buf, d_buf + len) (an overlap returns -1).  EVERY line of the buffer is written, in line
+ * order: line i's bytes, then `delim` when line i is the last line of its record (i == n - 1 or
+ * line i + 1 is a head), otherwise the byte `join` (0 .. 255, else -1).  The output is a
+ * well-formed line buffer with one record per line; when `join` occurs in no line and is not
+ * the delimiter, folding it again with the same scanner reproduces it.  join == delim is allowed:
+ * the output is then the input with a final delimiter, and the call is useful for its tables.
+ * info->need_bytes is the sum of the line lengths plus n, whatever out_cap is.
+ *
+ * Truncation.  Only whole RECORDS are written: info->nwritten is the largest number of leading
+ * records whose bytes fit out_cap, info->out_bytes their size.  No byte of d_out at or beyond
+ * out_bytes is touched and nothing in front of d_out.  d_out == NULL with out_cap == 0 is the
+ * sizing call; d_out == NULL with out_cap != 0 returns -1.
+ *
+ * Tables, both optional DEVICE arrays.  A table pointer must be NULL exactly when its capacity
+ * is 0, else -1.
+ *   - d_recid[i], for the first min(recid_cap, n) lines: the record number of line i (the heads at
+ *     or in front of i, minus 1), whatever out_cap is.
+ *   - d_records: for each of the first min(records_cap, nwritten) records FIVE sre_int_t,
+ *       [0] first line   [1] lines   [2] offset of the first line in d_buf
+ *       [3] bytes of the record in d_out without its final delimiter   [4] offset in d_out.
+ *
+ * Counts.  info->nlines, nmarked (marked lines), nrecords (heads), longest (the lines of the
+ * longest record) and need_bytes are totals over the whole buffer.  info may be NULL.
+ *
+ * Not offered: SRE_HIP_LINES_ALL; a join string of more or fewer than one byte (so the
+ * backslash of a continuation line is not stripped); a cap on a record's bytes; unfolding, that
+ * is translating `join` back to the delimiter; records across calls or stream sets (the last
+ * record of a buffer may continue in the next); selecting records in the same call: filter the
+ * output instead.
+ *
+ * The call is synchronous and all its work runs on hip_stream; the host waits as often as in
+ * sre_hip_filter_lines and reads three words more in the same copy.  Nothing per line or per
+ * record travels to the host on the device routes; the other routes keep their per-line host
+ * work as for the filter, and the fold pass runs behind them on the device.  Batch cuts need no
+ * care: the pass runs once, over the values of the whole call.  The call replaces the scanner's
+ * last call and the diagnostics describe it exactly as for sre_hip_filter_lines.  len == 0 gives
+ * all zeros in info and success.  Beyond what sre_hip_filter_lines takes, a scanner keeps 16
+ * bytes and two bits per line plus 40 bytes per 1024 lines of the largest fold call of device
+ * memory, grow-only, freed with the scanner.  Returns 0 on success, -1 on bad arguments or
+ * failure, with info untouched.
+ */
+SRE_API int sre_hip_fold_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, int join,
+    size_t max_lines, void *d_out, size_t out_cap, sre_int_t *d_recid, size_t recid_cap,
+    sre_int_t *d_records, size_t records_cap, sre_hip_fold_info_t *info, void *hip_stream);
+
 /* ---- line extract: capture groups of each matching line as delimited rows in a device buffer ---- */
 
 enum { SRE_HIP_EXTRACT_MAX_FIELDS = 32 };

@@ -38,6 +38,7 @@ HIP_TALLY_OVERFLOW = 1
 HIP_TALLY_MAX_KEYS = 1 << 30
 HIP_TALLY_MAX_VALUES = 8
 HIP_DISTINCT_FIRST, HIP_DISTINCT_LAST, HIP_DISTINCT_EVERY = 0, 1, 2
+HIP_FOLD_NEXT = 8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SREGEX_AMD_LIB") or os.path.join(_HERE, "lib", "libsregex.so")
@@ -93,6 +94,8 @@ API = {
     "sre_hip_filter_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_filter_lines_context": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, _sz, _sz, _vp, _sz, _vp, _sz, _vp,
                                                     _vp]),
+    "sre_hip_fold_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.c_int, ctypes.c_int, _sz, _vp, _sz, _vp, _sz, _vp, _sz,
+                                          _vp, _vp]),
     "sre_hip_extract_lines": (ctypes.c_int, [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int), _sz, ctypes.c_int,
                                              ctypes.c_int, _vp, _sz, _vp, _sz, _vp, _vp]),
     "sre_hip_subst_template_check": (ctypes.c_int, [ctypes.c_char_p, _sz, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
@@ -586,6 +589,26 @@ class Scanner:
             raise RuntimeError("sre_hip_filter_lines_context failed")
         return ContextInfo(*info)
 
+    def fold_lines(self, ptr, length, out_ptr, out_cap, join=0x01, max_lines=0, delim=0x0A, invert=False, fold_next=False,
+                   recid_ptr=None, recid_cap=0, records_ptr=None, records_cap=0, hip_stream=None):
+        """sre_hip_fold_lines: the lines of the device buffer (ptr, length) joined into multi-line records in the device
+        buffer (out_ptr, out_cap): every line is written in line order, followed by the delimiter when it is the last of
+        its record and by the byte `join` otherwise.  A line with a match (with invert: without one) is MARKED: it
+        belongs to the record of the line in front of it, with fold_next it continues into the line behind it;
+        max_lines caps the lines of a record (0: no cap).  Only whole records are written.  recid_ptr: an optional
+        device array of recid_cap words, the record number of each line; records_ptr: an optional device array of
+        records_cap rows [first line, lines, offset in the buffer, bytes in the output without the final delimiter,
+        offset in the output].  Returns FoldInfo(nlines, nmarked, nrecords, longest, need_bytes, nwritten, out_bytes)."""
+        if (not 0 <= join <= 255 or max_lines < 0 or (recid_ptr is None) != (recid_cap == 0)
+                or (records_ptr is None) != (records_cap == 0) or (out_ptr is None and out_cap != 0)):
+            raise ValueError("sre_hip_fold_lines: join outside 0..255, or a pointer that does not stand for its capacity")
+        flags = (HIP_LINES_INVERT if invert else 0) | (HIP_FOLD_NEXT if fold_next else 0)
+        info = FoldInfoStruct()
+        if self.lib.sre_hip_fold_lines(self.h, ptr, length, delim, flags, join, max_lines, out_ptr, out_cap, recid_ptr, recid_cap,
+                                       records_ptr, records_cap, ctypes.byref(info), hip_stream) != 0:
+            raise RuntimeError("sre_hip_fold_lines failed")
+        return FoldInfo(*(getattr(info, name) for name in FoldInfo._fields))
+
     def extract_lines(self, ptr, length, groups, out_ptr, out_cap, delim=0x0A, fsep=0x09, all_lines=False, index_ptr=None,
                       index_cap=0, hip_stream=None):
         """sre_hip_extract_lines: for every matching line of the device buffer (ptr, length) (every line with
@@ -905,6 +928,14 @@ DistinctInfo = collections.namedtuple("DistinctInfo", "nlines nkeyed nkeys nkeys
 class DistinctInfoStruct(ctypes.Structure):
     """sre_hip_distinct_info_t"""
     _fields_ = [(name, ctypes.c_size_t) for name in DistinctInfo._fields]
+
+
+FoldInfo = collections.namedtuple("FoldInfo", "nlines nmarked nrecords longest need_bytes nwritten out_bytes")
+
+
+class FoldInfoStruct(ctypes.Structure):
+    """sre_hip_fold_info_t"""
+    _fields_ = [(name, ctypes.c_size_t) for name in FoldInfo._fields]
 
 
 class TallyInfoStruct(ctypes.Structure):

@@ -154,6 +154,12 @@ struct sre_hip_scanner_s {
     size_t                    cbits_cap;
     uint64_t                 *d_cblk;           /* block words and counts of the context pass: 4 words per SRE_LINES_ITEMS lines */
     size_t                    cblk_cap;
+    uint64_t                 *d_gbits;          /* the fold's two bitmaps (marked lines, heads): two bits per line */
+    size_t                    gbits_cap;
+    uint64_t                 *d_gblk;           /* block words and counts of the fold pass: 5 words per SRE_LINES_ITEMS lines */
+    size_t                    gblk_cap;
+    uint64_t                 *d_gaux;           /* the fold's word per line: a head's next head, else the record's first line */
+    size_t                    gaux_cap;
     /* the line extract (sre_hip_extract_lines) shares both, sized by its entries (lines x fields), and adds */
     uint64_t                 *d_fstart;         /* per-entry source offsets under their flags: lines x fields words */
     size_t                    fstart_cap;
@@ -280,6 +286,9 @@ scanner_release(void *data)
     if (sc->d_fblk) (void) hipFree(sc->d_fblk);
     if (sc->d_cbits) (void) hipFree(sc->d_cbits);
     if (sc->d_cblk) (void) hipFree(sc->d_cblk);
+    if (sc->d_gbits) (void) hipFree(sc->d_gbits);
+    if (sc->d_gblk) (void) hipFree(sc->d_gblk);
+    if (sc->d_gaux) (void) hipFree(sc->d_gaux);
     if (sc->d_fstart) (void) hipFree(sc->d_fstart);
     if (sc->d_lit) (void) hipFree(sc->d_lit);
     free(sc->h_lit);
@@ -2485,6 +2494,65 @@ sre_hip_filter_lines_context(sre_hip_scanner_t *sc, const void *d_buf, size_t le
         res.nmatched = context ? (size_t) sc->h_linfo->cmatched : res.nselected;
         res.ngroups = (size_t) sc->h_linfo->cgroups;
         if (sink_write(sc, &sink, d_buf, n, res.out_bytes, res.nwritten, stream) != 0) return -1;
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (info) *info = res;
+    return 0;
+hip_failed:
+    return -1;
+}
+
+/* The line fold (rules in sre_lines_fold.h): sre_hip_filter_lines up to the per-line values, which mark the
+ * continuation lines; then on the device the fold pass, which finds the heads of the records and turns the values into the
+ * extract's entry table with one entry a line; the extract's scan, the cut moved back to a record boundary, one read (the
+ * scan's four words and the fold's three), the extract's gather with `join` as its separator, and the two tables. */
+extern "C" SRE_API int
+sre_hip_fold_lines(sre_hip_scanner_t *sc, const void *d_buf, size_t len, int delim, int flags, int join, size_t max_lines,
+    void *d_out, size_t out_cap, sre_int_t *d_recid, size_t recid_cap, sre_int_t *d_records, size_t records_cap,
+    sre_hip_fold_info_t *info, void *hip_stream)
+{
+    static_assert(sizeof(sre_int_t) == sizeof(int64_t), "the tables are 64-bit words");
+    LinesSink sink;
+    if ((flags & ~(SRE_HIP_LINES_INVERT | SRE_HIP_FOLD_NEXT)) != 0 || join < 0 || join > 255 || (d_recid == NULL) != (recid_cap == 0)
+        || (d_records == NULL) != (records_cap == 0)
+        || !sink_open(&sink, sc, d_buf, len, delim, flags & SRE_HIP_LINES_INVERT, d_out, out_cap, NULL, 0))
+    {
+        return -1;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    uint64_t    n = 0, nrep = 0;
+    if (lines_call(sc, d_buf, len, delim, 0, NULL, 0, &sink, &n, &nrep, stream) != 0) return -1;
+    sre_hip_fold_info_t res;
+    memset(&res, 0, sizeof(res));
+    if (n != 0) {
+        const uint64_t nblk = (n + SRE_LINES_ITEMS - 1) / SRE_LINES_ITEMS;
+        if (lines_grow(&sc->d_fstart, &sc->fstart_cap, n * sizeof(uint64_t)) != 0
+            || lines_grow(&sc->d_fblk, &sc->fblk_cap, 2 * nblk * sizeof(uint64_t)) != 0
+            || lines_grow(&sc->d_gbits, &sc->gbits_cap, 2 * ((n + 63) / 64) * sizeof(uint64_t)) != 0
+            || lines_grow(&sc->d_gblk, &sc->gblk_cap, 5 * nblk * sizeof(uint64_t)) != 0
+            || lines_grow(&sc->d_gaux, &sc->gaux_cap, n * sizeof(uint64_t)) != 0)
+        {
+            return -1;
+        }
+        SRE_HIP_TRY(sre_launch_fold_select(sc->d_fval, sc->d_fstart, sc->d_ends, n, (flags & SRE_HIP_FOLD_NEXT) != 0, max_lines,
+                                           sc->d_gbits, sc->d_gaux, sc->d_gblk, sc->d_linfo, stream));
+        SRE_HIP_TRY(sre_launch_extract_offsets(sc->d_fval, n, 1, sc->d_fblk, out_cap, sc->d_linfo, stream));
+        SRE_HIP_TRY(sre_launch_fold_finish(sc->d_fval, n, sc->d_gbits, sc->d_gaux, sc->d_gblk, out_cap, sc->d_linfo, stream));
+        SRE_HIP_TRY(linfo_read(sc, stream, {LINFO(fneed), LINFO(fwritten), LINFO(fbytes), LINFO(gnrec), LINFO(gmarked), LINFO(glongest)}));
+        SRE_HIP_TRY(hipStreamSynchronize(stream));
+        res.nlines = (size_t) n;
+        res.nmarked = (size_t) sc->h_linfo->gmarked;
+        res.nrecords = (size_t) sc->h_linfo->gnrec;
+        res.longest = (size_t) sc->h_linfo->glongest;
+        res.need_bytes = (size_t) sc->h_linfo->fneed;
+        res.nwritten = (size_t) sc->h_linfo->fwritten;
+        res.out_bytes = (size_t) sc->h_linfo->fbytes;
+        if (res.out_bytes > out_cap) return -1;     /* (cannot happen: the cut is made against out_cap) */
+        SRE_HIP_TRY(sre_launch_extract_gather(d_buf, d_out, sc->d_fval, sc->d_fstart, n, res.out_bytes, (uint32_t) delim,
+                                              (uint32_t) join, stream));
+        SRE_HIP_TRY(sre_launch_fold_tables(sc->d_fval, sc->d_ends, n, sc->d_gbits, sc->d_gaux, sc->d_gblk, sc->d_linfo,
+                                           reinterpret_cast<int64_t *>(d_recid), recid_cap, reinterpret_cast<int64_t *>(d_records),
+                                           records_cap, res.nwritten, stream));
         SRE_HIP_TRY(hipStreamSynchronize(stream));
     }
     if (info) *info = res;

@@ -65,6 +65,10 @@ typedef struct {
     uint64_t snumbered;     /* of those, lines whose sort field is a number */
     uint64_t svmin;         /* the least of those numbers, an int64_t (INT64_MAX without one) */
     uint64_t svmax;         /* the greatest, an int64_t (INT64_MIN without one) */
+    /* the line fold (sre_hip_fold_lines): three more words, read with the four; fwritten counts records there */
+    uint64_t gnrec;         /* records: the heads */
+    uint64_t gmarked;       /* marked lines */
+    uint64_t glongest;      /* lines of the longest record */
 } sre_lines_info_t;
 
 #ifdef __cplusplus
@@ -140,6 +144,26 @@ hipError_t sre_launch_context_runs(const uint64_t *d_off, uint64_t n, uint64_t *
  * first line of a group.  d_blk: the words of sre_launch_filter_offsets */
 hipError_t sre_launch_context_index(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_blk,
     const uint64_t *d_bits, const sre_lines_info_t *d_info, uint64_t index_cap, int64_t *d_index, hipStream_t stream);
+/* ---- the line fold (sre_hip_lines_fold.hip, sre_lines_fold.h) ---- */
+/* between the last select pass and sre_launch_extract_offsets with k = 1 (marks, carry, apply, totals): line i is marked when
+ * d_val[i] > 0, and a marked line belongs to the record of the line in front of it, with `next` to the one behind it;
+ * max_lines caps the lines of a record (0: no cap).  Afterwards d_val / d_start are the extract's entry table with one entry a
+ * line: d_val[i] = len + 1, d_start[i] the line's source offset under SRE_LG_ENTRY_LAST where the delimiter follows the line
+ * (n words each).  d_bits: 2 x ceil(n / 64) words (the marked lines, the heads); d_aux: n words (a head: the head behind it,
+ * any other line: the first line of its record); d_blk: 5 x ceil(n / SRE_LINES_ITEMS) words of its own, the third run the
+ * heads in front of each workgroup; info->gnrec, gmarked, glongest */
+hipError_t sre_launch_fold_select(uint64_t *d_val, uint64_t *d_start, const uint64_t *d_ends, uint64_t n, int next,
+    uint64_t max_lines, uint64_t *d_bits, uint64_t *d_aux, uint64_t *d_blk, sre_lines_info_t *d_info, hipStream_t stream);
+/* behind sre_launch_extract_offsets: the cut at out_cap moved back to the first line of its record; info->fbytes, and
+ * info->fwritten = the records in front of the cut */
+hipError_t sre_launch_fold_finish(const uint64_t *d_off, uint64_t n, const uint64_t *d_bits, const uint64_t *d_aux,
+    const uint64_t *d_blk, uint64_t out_cap, sre_lines_info_t *d_info, hipStream_t stream);
+/* d_recid[i] = the record of line i for i < min(recid_cap, n); rows [first line, lines, source offset, bytes without the final
+ * delimiter, output offset] of the first min(records_cap, info->fwritten) records (nwritten: that word as the host read it).
+ * Nothing is launched for a capacity of 0 */
+hipError_t sre_launch_fold_tables(const uint64_t *d_off, const uint64_t *d_ends, uint64_t n, const uint64_t *d_bits,
+    const uint64_t *d_aux, const uint64_t *d_blk, const sre_lines_info_t *d_info, int64_t *d_recid, uint64_t recid_cap,
+    int64_t *d_records, uint64_t records_cap, uint64_t nwritten, hipStream_t stream);
 /* ---- the line extract (sre_hip_lines_gather.hip) ---- */
 /* select pass of the batch over its entries e = line * k + f: d_val[e] and d_start[e] as sre_sel_extract_entry gives
  * them.  A batch may have at most 2^32 - 1 entries */

@@ -34,56 +34,6 @@ static_assert(SRE_LC_ITEMS == SRE_LINES_ITEMS && SRE_LC_THREADS * SRE_LC_PER_LAN
 
 namespace {
 
-/* a wave's exclusive scans (sre_lc_wave_scan_fwd / _bwd run the same steps over an array): the lane's word over the
- * lanes in front of it, resp. behind it, and in `total` of lane 63, resp. lane 0, the wave's */
-template <class T>
-__device__ inline T
-wave_excl_fwd(T v, uint32_t lane, T &total)
-{
-    T x = __shfl_up(v, 1, 64);
-    if (lane == 0) x = 0;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) x = sre_lc_fwd(x, (T) __shfl_up(x, d, 64), lane, d);
-    total = x > v ? x : v;
-    return x;
-}
-
-template <class T>
-__device__ inline T
-wave_excl_bwd(T v, uint32_t lane, T &total)
-{
-    T x = __shfl_down(v, 1, 64);
-    if (lane == 63) x = (T) ~(T) 0;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) x = sre_lc_bwd(x, (T) __shfl_down(x, d, 64), lane, d);
-    total = x < v ? x : v;
-    return x;
-}
-
-/* ... and the workgroup's (NW waves; sre_lc_block_scan): p and q become exclusive over the workgroup, ptot / qtot its
- * totals; wp and wq hold NW words each */
-template <class T, uint32_t NW>
-__device__ inline void
-block_excl_marks(T &p, T &q, T *wp, T *wq, T &ptot, T &qtot)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    T              tp, tq;
-    p = wave_excl_fwd(p, lane, tp);
-    q = wave_excl_bwd(q, lane, tq);
-    if (lane == 63) wp[w] = tp;
-    if (lane == 0) wq[w] = tq;
-    __syncthreads();
-    const T pin = sre_lc_waves_fwd(wp, NW, w), qin = sre_lc_waves_bwd(wq, NW, w);
-    p = pin > p ? pin : p;
-    q = qin < q ? qin : q;
-    ptot = sre_lc_waves_fwd(wp, NW, NW);
-    T qt = wq[0];
-#pragma unroll
-    for (uint32_t i = 1; i < NW; i++) qt = wq[i] < qt ? wq[i] : qt;
-    qtot = qt;
-    __syncthreads();
-}
-
 /* lane x of workgroup b: lines b * 1024 + 4x .. + 3 (0 beyond n) */
 __device__ inline void
 load_values(const uint64_t *__restrict__ val, uint64_t n, uint64_t q0, uint64_t v[SRE_LC_PER_LANE])
